@@ -19,13 +19,22 @@ for every instance, and the result exchange (``sharding.pack_and_gather``: the r
 device and, with N > 1, ONE RCCL all_gather moves 32 B per instance).  Inputs are resident in HBM before
 the timed region.  ``value`` counts only instances that finished with status kSolved.
 
-Beside the headline the default line (N = 1) carries: ``cpu_baseline`` (the oracle on the host cores, pinned
-threads, instances built outside the timed region), ``host_boundary`` (the same step over host buffers),
-``other_configs`` (BASELINE configs 1, 3, 4: a few steps each after the headline) and ``latency`` (one solve of a
-batch of 1 / 8 / 64 -- the MPC use case -- next to one host core).
+A plain run sets up, warms up, times the K steps and prints the headline line (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` and the workload's ``config``).  ``--full`` adds everything else (N = 1):
+``roofline`` (one profiled solve), ``cpu_baseline`` (the oracle on the host cores, pinned threads, instances built
+outside the timed region), ``host_boundary`` (the same step over host buffers), ``other_configs`` (BASELINE configs
+1, 3, 4: a few steps each after the headline), ``latency`` (one solve of a batch of 1 / 8 / 64 -- the MPC use case --
+next to one host core), ``fast_forward``, ``pipeline_2`` and ``device_loop``; the ``--no-*`` switches drop single
+blocks of a full run.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--batch B] [--no-cpu-baseline]
-                        [--no-other-configs] [--no-latency] [--no-fast-forward] [--no-pipeline2] [--no-numa-bind]
+``--dump-outputs DIR`` writes what the last timed step computed, after the timed region: ``records.npy`` (the
+[global batch][4] float64 result records the step delivers: cost, violation, iterations, status) and ``X.npy`` /
+``U.npy`` (the float64 trajectories of this rank's instances; beyond 64 MB in all, a fixed seeded sample of
+instances, listed in ``instances.npy``).  Inputs are seeded: the same arguments give the same inputs in every run.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--batch B] [--dump-outputs DIR] [--full]
+                        [--no-cpu-baseline] [--no-other-configs] [--no-latency] [--no-fast-forward] [--no-pipeline2]
+                        [--no-numa-bind]
         (N > 1: one rank per GPU -- under torch.distributed.run as the driver launches it, or started plainly: bench.py
          then launches its N ranks itself, `self_launch`.  `--launch-check`: the rank plumbing alone, no GPU, gloo.)
 """
@@ -592,6 +601,29 @@ def measure_latency(A, P, device_id, with_cpu=True):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, records, solver):
+    """`--dump-outputs`: the result records of the last timed step and this rank's trajectories as float64 .npy files.
+    Trajectories that would take the dump past DUMP_LIMIT_BYTES are cut to a fixed seeded sample of instances."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    records = np.ascontiguousarray(records, dtype=np.float64)
+    X, U = solver.get_trajectory()
+    per_instance = (X[0].nbytes + U[0].nbytes) if len(X) else 1
+    keep = max(1, (DUMP_LIMIT_BYTES - records.nbytes) // per_instance)
+    files = {"records": records}
+    if keep < len(X):
+        idx = np.sort(np.random.default_rng(0).choice(len(X), size=keep, replace=False))
+        X, U = X[idx], U[idx]
+        files["instances"] = idx.astype(np.float64)
+    files.update(X=X, U=U)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(files)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -621,6 +653,11 @@ def main():
     ap.add_argument("--no-device-loop", action="store_true", help="skip the secondary `device_loop` key (k_sweep_loop against the sweeps, batch 1536)")
     ap.add_argument("--no-numa-bind", action="store_true",
                     help="multi-rank runs bind each rank's host threads to the NUMA node of its GPU; this switches it off")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, CPU baseline, host boundary, other configs, latency, "
+                         "fast-forward, two-handle pipeline and device-loop blocks (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result records and trajectories of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -783,24 +820,30 @@ def main():
     value = solved * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
 
+    if rank == 0 and args.dump_outputs:
+        # (before anything else solves again: the trajectories are those of the last timed step)
+        dump_outputs(args.dump_outputs, res, pool[(counter[0] - 1) % len(pool)] if args.pipeline > 1 else solver)
+
     out = None
     if rank == 0:
         # ---- roofline of the dominant kernel: one more (untimed) solve with per-kernel HIP events on the
         #      solver's own stream (altro_get_timing) ----
-        solver.set_options(profiler_enable=1)
-        solve(solver)
-        tm = solver.get_timing()
-        solver.set_options(profiler_enable=0)
-        roofline = dominant_kernel_roofline(cfg, tm, args.config)
+        roofline, tm = None, None
+        if args.full:
+            solver.set_options(profiler_enable=1)
+            solve(solver)
+            tm = solver.get_timing()
+            solver.set_options(profiler_enable=0)
+            roofline = dominant_kernel_roofline(cfg, tm, args.config)
         # ---- CPU baseline: the oracle (a port, see oracle/altro_oracle.cpp) on the host cores --------
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             cpu = cpu_baseline(A, P, cfg, B, seed)
         # ---- the same step with the problem handed over as HOST buffers (the C-ABI boundary of an MPC caller: a new
         #      initial state and a warm start per instance go up, trajectories and statistics come back), PCIe and
         #      the host-side layout conversion included.  Reported beside `value`, never as `value`. ----
         host = None
-        if args.pipeline == 1 and world == 1:
+        if args.full and args.pipeline == 1 and world == 1:
             solver.reset_trajectory()
             X0, U0 = solver.get_trajectory()
             x0 = np.ascontiguousarray(X0[:, 0, :])
@@ -829,7 +872,7 @@ def main():
                         "altro_get_trajectory + altro_get_stats into host arrays (the caller's buffers, reused)",
             }
         name, cus = solver.device_info()
-        if args.force_dist and world == 1 and dist_check is not None:
+        if args.full and args.force_dist and world == 1 and dist_check is not None:
             # the optional second collective (whole trajectories on every rank), outside the timed region
             Nk, nn, mm = solver.N, solver.n, solver.m
             xp = torch.empty((B, Nk + 1, nn), dtype=torch.float64, device=dev)
@@ -846,7 +889,7 @@ def main():
                                "trajectory_gather_ms": round(g_ms, 3),
                                "trajectory_bytes": int(xp.numel() * 8 + up.numel() * 8)})
         others, latency = None, None
-        if world == 1 and args.pipeline == 1 and (not args.no_other_configs or not args.no_latency):
+        if args.full and world == 1 and args.pipeline == 1 and (not args.no_other_configs or not args.no_latency):
             solver.close()  # (the other workloads get the device to themselves, like the headline had it)
             if not args.no_other_configs:
                 others = {}
@@ -859,7 +902,7 @@ def main():
         #      repetitions of a rejected line search are counted and logged instead of recomputed (results bit-identical,
         #      tests/test_fused_gpu.py), i.e. work the reference performs is skipped ----
         fast_forward = None
-        if (world == 1 and args.pipeline == 1 and cfg["mode"] == "al" and not args.no_fast_forward
+        if (args.full and world == 1 and args.pipeline == 1 and cfg["mode"] == "al" and not args.no_fast_forward
                 and not os.environ.get("ALTRO_HIP_FAST_FORWARD_STALLS")):
             if others is None and latency is None:
                 solver.close()
@@ -892,7 +935,7 @@ def main():
         #      Every step is still one complete solve of the headline's batch; the records of BOTH handles are compared
         #      with the headline's ----
         pipeline_2 = None
-        if world == 1 and args.pipeline == 1 and cfg["mode"] == "al" and not args.no_pipeline2:
+        if args.full and world == 1 and args.pipeline == 1 and cfg["mode"] == "al" and not args.no_pipeline2:
             if others is None and latency is None and fast_forward is None:
                 solver.close()
             pool = [new_solver(), new_solver()]
@@ -940,7 +983,8 @@ def main():
             for s_ in pool:
                 s_.close()
         device_loop = None
-        if world == 1 and args.pipeline == 1 and args.config == 2 and not args.no_device_loop and not os.environ.get("ALTRO_HIP_SWEEP_LOOP"):
+        if (args.full and world == 1 and args.pipeline == 1 and args.config == 2 and not args.no_device_loop
+                and not os.environ.get("ALTRO_HIP_SWEEP_LOOP")):
             if others is None and latency is None and fast_forward is None and pipeline_2 is None:
                 solver.close()
             try:
@@ -948,13 +992,14 @@ def main():
             except Exception as e:  # (never fail the line for a secondary key)
                 device_loop = {"error": str(e)[:300]}
         # ---- the achievable HBM ceiling of this device beside the data-sheet peak ----
-        try:
-            copy_gbs = measure_hbm_copy_gbs(torch, dev)
-            roofline["peak_measured_copy"] = round(copy_gbs, 1)
-            roofline["frac_of_measured_copy"] = round(roofline["achieved"] / copy_gbs, 5)
-        except Exception as e:  # (never fail the line for the side measurement)
-            roofline["peak_measured_copy"] = None
-            roofline["peak_measured_copy_error"] = str(e)[:200]
+        if args.full:
+            try:
+                copy_gbs = measure_hbm_copy_gbs(torch, dev)
+                roofline["peak_measured_copy"] = round(copy_gbs, 1)
+                roofline["frac_of_measured_copy"] = round(roofline["achieved"] / copy_gbs, 5)
+            except Exception as e:  # (never fail the line for the side measurement)
+                roofline["peak_measured_copy"] = None
+                roofline["peak_measured_copy_error"] = str(e)[:200]
         out = {
             "metric": "trajectories solved/sec (AL-iLQR to tol), unicycle 101 knots, batched" if args.config in (2, 3)
                       else "trajectories solved/sec (to tol), batched",
@@ -970,24 +1015,24 @@ def main():
                                f"{'RCCL' if args.dist_backend == 'nccl' else 'gloo (host)'} all_gather of result records)",
                 "host_cpu_cores_per_rank": round(host_cpu_cores, 3),
                 "solved_fraction": round(solved / total_inst, 5),
-                "ms_per_ilqr_iter_sweep": round(ms_per_step / max(tm["sweeps"], 1), 4),
+                **({"ms_per_ilqr_iter_sweep": round(ms_per_step / max(tm["sweeps"], 1), 4)} if tm is not None else {}),
                 "us_per_instance_iter": round(1e3 * ms_per_step / max(float(iters.sum()) / world, 1.0), 4),
                 "mean_iterations": round(float(iters.mean()), 3), "max_iterations": int(iters.max()),
-                "sweeps": tm["sweeps"], "device": name, "cus": cus,
+                **({"sweeps": tm["sweeps"]} if tm is not None else {}), "device": name, "cus": cus,
                 **({"pipeline": args.pipeline, "note": "NOT the headline configuration: solves of consecutive steps "
                     "overlap (asynchronous handles)"} if args.pipeline > 1 else {}),
                 **({"fast_forward_stalls": True, "note_ff": "NOT the headline configuration: ALTRO_HIP_FAST_FORWARD_STALLS "
                     "counts the bit-identical repetitions of a rejected line search instead of recomputing them"}
                    if os.environ.get("ALTRO_HIP_FAST_FORWARD_STALLS") else {}),
             },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "host_boundary": host,
-            "other_configs": others,
-            "latency": latency,
-            "fast_forward": fast_forward,
-            "pipeline_2": pipeline_2,
-            "device_loop": device_loop,
+            **({"roofline": roofline,
+                "cpu_baseline": cpu,
+                "host_boundary": host,
+                "other_configs": others,
+                "latency": latency,
+                "fast_forward": fast_forward,
+                "pipeline_2": pipeline_2,
+                "device_loop": device_loop} if args.full else {}),
             **({"dist_check": dist_check} if dist_check is not None else {}),
         }
         print(json.dumps(out), flush=True)

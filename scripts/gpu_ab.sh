@@ -4,7 +4,7 @@ a=$1; b=$2; shift 2
 for rep in 1 2; do
 for c in ${@:-2 3}; do
   for lib in $a $b; do
-    ALTRO_HIP_LIB=$lib python bench.py --config $c --no-cpu-baseline 2>&1 | python -c "
+    ALTRO_HIP_LIB=$lib python bench.py --config $c --full --no-cpu-baseline 2>&1 | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 {
 for src in global kdg global kdg; do
   echo "== ALTRO_HIP_FWD_SRC=$src"
-  ALTRO_HIP_FWD_SRC=$src timeout 600 python bench.py --config 4 --steps 10 --warmup 2 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+  ALTRO_HIP_FWD_SRC=$src timeout 600 python bench.py --config 4 --steps 10 --warmup 2 --full --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('  ms', d['ms_per_step'], 'kernel_ms', r['kernel_ms'], 'dominant', r['kernel'], 'avg_launch_us', r['avg_launch_us'], 'solved', d['config']['solved_fraction'])"

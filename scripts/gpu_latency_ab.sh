@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 for rep in 1 2; do
   for mode in merged split; do
-    ALTRO_HIP_BEGIN_SOLVE=$mode python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-fast-forward --no-pipeline2 --no-device-loop 2>/dev/null | tail -1 |
+    ALTRO_HIP_BEGIN_SOLVE=$mode python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-fast-forward --no-pipeline2 --no-device-loop 2>/dev/null | tail -1 |
       python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())

@@ -6,7 +6,7 @@ C=${1:-2}
 P=gpurun_out/pmc_diag_c$C
 rm -rf $P; mkdir -p $P
 case $C in 2|3) export ALTRO_HIP_CHAINS=4;; *) export ALTRO_HIP_CHAINS=1;; esac
-CMD="python bench.py --config $C --steps 1 --warmup 1 --no-cpu-baseline --no-other-configs --no-latency --no-fast-forward"
+CMD="python bench.py --config $C --steps 1 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-latency --no-fast-forward"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC --output-format csv -d $P/a -o bench -- $CMD > $P/a.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_IFETCH SQ_BUSY_CU_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $P/b -o bench -- $CMD > $P/b.log 2>&1
 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES_DUPLICATE SQC_DCACHE_REQ SQC_DCACHE_MISSES --output-format csv -d $P/c -o bench -- $CMD > $P/c.log 2>&1

@@ -10,7 +10,7 @@ rm -rf $P; mkdir -p $P
 # the size of the trace pass's.  ALTRO_HIP_CHAINS forces the count (and skips the check): what a fresh process picks
 # (4 for a batch >= 2048, else 1).
 case $C in 2|3) export ALTRO_HIP_CHAINS=4;; *) export ALTRO_HIP_CHAINS=1;; esac
-CMD="python bench.py --config $C --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-latency --no-fast-forward --no-pipeline2 --no-device-loop ${BENCH_EXTRA:-}"
+CMD="python bench.py --config $C --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-latency --no-fast-forward --no-pipeline2 --no-device-loop ${BENCH_EXTRA:-}"
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o bench -- $CMD > $P/trace_run.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/fetch -o bench -- $CMD > $P/fetch_run.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/write -o bench -- $CMD > $P/write_run.log 2>&1
@@ -52,8 +52,8 @@ PY
 for d in trace fetch write sq mfma f64 tcc; do rm -rf $P/$d; done
 unset ALTRO_HIP_CHAINS
 if [ "$C" = "2" ]; then
-  python bench.py --config $C --steps 5 --warmup 1 2>/dev/null | tail -1 > $P/bench_line.json
+  python bench.py --config $C --steps 5 --warmup 1 --full 2>/dev/null | tail -1 > $P/bench_line.json
 else
-  python bench.py --config $C --steps 5 --warmup 1 --no-other-configs --no-latency 2>/dev/null | tail -1 > $P/bench_line.json
+  python bench.py --config $C --steps 5 --warmup 1 --full --no-other-configs --no-latency 2>/dev/null | tail -1 > $P/bench_line.json
 fi
 ls $P

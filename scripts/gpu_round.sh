@@ -1,15 +1,16 @@
 # One GPU visit: parity tests, smoke, bench, rocprof kernel trace of the bench.
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+OUT=${OUT:-results}  # (where the logs and the trace go)
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-python -m pytest tests -q -m gpu 2>&1 | grep -v "^E  " | tail -12 | tee gpurun_out/pytest_gpu.log
-python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee gpurun_out/smoke.log
-python bench.py --steps 3 --warmup 1 2>&1 | tail -1 | tee gpurun_out/bench.log
-rm -rf gpurun_out/prof
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o bench -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline > gpurun_out/prof_run.log 2>&1
-python - <<'PY'
-import csv, glob, collections
-f = glob.glob('gpurun_out/prof/**/*kernel_trace.csv', recursive=True)[0]
+python -m pytest tests -q -m gpu 2>&1 | grep -v "^E  " | tail -12 | tee "$OUT/pytest_gpu.log"
+python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee "$OUT/smoke.log"
+python bench.py --steps 3 --warmup 1 --full 2>&1 | tail -1 | tee "$OUT/bench.log"
+rm -rf "$OUT/prof"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline > "$OUT/prof_run.log" 2>&1
+python - "$OUT" <<'PY'
+import csv, glob, collections, sys
+f = glob.glob(sys.argv[1] + '/prof/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 per = collections.defaultdict(list)
 for r in rows:

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 C=${1:-3}
 P=gpurun_out/timeline_c$C
 rm -rf $P; mkdir -p $P
-rocprofv3 --kernel-trace --output-format csv -d $P/trace -o bench -- python bench.py --config $C --steps 1 --warmup 1 --no-cpu-baseline --no-other-configs --no-latency > $P/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $P/trace -o bench -- python bench.py --config $C --steps 1 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-latency > $P/run.log 2>&1
 python - $P $C <<'PY'
 import csv, glob, sys, collections
 P, C = sys.argv[1], sys.argv[2]

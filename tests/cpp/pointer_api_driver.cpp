@@ -4,9 +4,8 @@
 //
 // This is the repository's OWN driver -- a table of scenarios run by one routine, checked against the reference's known
 // answers (test/examples/example_unicycle_test.cpp:65-80: 50 iterations, 5 outer, kSolved; example_triple_integrator_test.cpp:
-// 16-70: 2 iterations).  That the reference's real callers compile against include/ as they are is checked where the reference
-// exists: tests/test_facade_compile.py::test_reference_perf_drivers_compile_in_place compiles /root/reference/perf/*.cpp in
-// place; nothing of those files lives in this tree.
+// 16-70: 2 iterations).  Nothing of the reference's own callers lives in this tree: the facade's call style is checked by
+// this driver and the repository's perf/*.cpp (tests/test_facade_compile.py).
 #include <cstdio>
 #include <functional>
 #include <string>

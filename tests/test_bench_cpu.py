@@ -59,6 +59,10 @@ def test_cpu_baseline_block(A, P):
     bench = importlib.import_module("bench")
     cfg = bench.CONFIGS[2]
     r = bench.cpu_baseline(A, P, cfg, 64, P.SEED_BASE + cfg["seed"], budget_cpu_s=1.0)
-    assert r["kind"] == "port" and r["value"] > 0 and r["cores"] in (r["physical_cores"], r["hardware_threads"])
+    assert r["kind"] == "port" and r["value"] > 0
+    # the two team sizes cpu_baseline times: one thread per usable core and twice that (usable = the physical cores, or
+    # fewer under a container CPU quota)
+    assert 1 <= r["usable_cores"] <= r["physical_cores"]
+    assert r["cores"] in (r["usable_cores"], min(r["hardware_threads"], 2 * r["usable_cores"]))
     assert 0.05 < r["parallel_efficiency"] < 1.5
     assert r["single_thread_value"] > 0 and r["teams"]

@@ -18,7 +18,7 @@ def test_bench_nccl_path_with_one_rank(config):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(29610 + config), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--config", str(config), "--force-dist", "--no-cpu-baseline", "--no-other-configs", "--no-latency"]
+           "--config", str(config), "--force-dist", "--full", "--no-cpu-baseline", "--no-other-configs", "--no-latency"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     print(r.stdout[-3000:], r.stderr[-3000:])
     assert r.returncode == 0
