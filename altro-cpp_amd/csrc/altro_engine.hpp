@@ -1531,7 +1531,7 @@ class Engine final : public EngineBase {
     if constexpr (kMfmaBackward) {
       const char* e = std::getenv("ALTRO_HIP_SWEEP_LOOP");
       if (!(e && atoi(e) == 0) && fwd_lds_bytes_ > 0 && !kdg_ && fwd_per_wave_ == lanes_per_wave() && B_ > persist_at_) {
-        const size_t bwd_bytes = ((size_t)kBwdChunk * 4 * R::KP + kBlock) * sizeof(double);
+        const size_t bwd_bytes = ((size_t)kBwdChunk * 4 * RR::KP + kBlock) * sizeof(double);  // (backward_mfma_body's sKD)
         loop_lds_bytes_ = std::max(fwd_lds_bytes_, bwd_bytes);
         const void* fn = rg_ ? LoopKernel<kSrcGlb>() : LoopKernel<kSrcLds>();
         if (fn && loop_lds_bytes_ <= 160 * 1024) {

@@ -661,7 +661,7 @@ constexpr int kBwdFrontPad = 2 * kBwdAhead;  // records in front of knot 0 that 
 constexpr int kBwdChunk = 126;  // knots of gains buffered in LDS between two bulk stores (4 instances: 32 KiB)
 
 // Body of the MFMA backward pass for one wavefront (lane = 0..63; the instance of block blk is slot
-// slot_base + blk of the launch).  sKD: LDS buffer of kBwdChunk * 4 * KP + 64 doubles.
+// slot_base + blk of the launch).  sKD: LDS buffer of kBwdChunk * 4 * RR::KP + 64 doubles (RR: the stored record).
 // FUSED (k_sweep_fused): one instance per wavefront (block 0), the gains go straight into the forward
 // pass's LDS block sKDf[k * KP + e] (+ a junk slot at sKDf[fused_junk + lane]) and are also written to
 // A.KD at the end; the running cost J0 is summed by the other wave; dV0 / dV1 are handed over in fh[1..2].
@@ -690,7 +690,9 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
   using R = Rec<T, n, m>;
   using RS = rec_scalar_t<T, M>;  // storage type of the expansion / gain records in HBM
   using RR = Rec<RS, n, m>;
-  static_assert(RR::KP == R::KP, "the gain chunk in LDS is laid out like the stored record");
+  // the gain chunk in LDS (sKD) is laid out like the STORED record, RR::KP per instance and knot: fp32 records pad the gain
+  // record to 4 elements and fp64 ones to 2, so the two strides differ for m (n + 1) = 2 or 6 -- (1, 1) and (2, 2)
+  constexpr int KS = RR::KP;
   const int r = lane >> 4, c = lane & 3, blk = (lane >> 2) & 3;
   const int b0 = (FUSED && blk != 0) ? -1 : ((FUSED && b_fixed >= 0) ? b_fixed : instance_of_slot(A, slot_base + blk, all));
   const bool inst_on = b0 >= 0;
@@ -817,11 +819,18 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
     //  chunk; with N > kBwdChunk they are other knots' gains, and writing them out corrupted the finished instance's record.
     //  Found in round 6 by an experimental build with 32-knot chunks on the obstacle batch, whose Cholesky restarts are real.)
     int slot = 0, k_top = N - 1;
+    // The instance of each block (its lane r = 0, c = 0) and whether it takes part are gathered BEFORE the loop, with the
+    // whole wavefront active: in the loop's last pass only the lanes below the element count run, and a shuffle from a lane
+    // outside them does not return that lane's value.  (With a 2-element gain record -- n = m = 1 in fp64 -- a pass that
+    // ends with one buffered knot has 8 elements: lanes 8 and 12, which hold blocks 2 and 3, were idle, and those blocks'
+    // gains of that knot were never stored.  Found by tests/test_model_shapes_gpu.py at N = 127.)
     auto flush = [&]() __attribute__((always_inline)) {
-      for (int i = lane; i < slot * 4 * R::KP; i += kBlock) {
-        const int e = i % R::KP, ib = (i / R::KP) % 4, sl = i / (4 * R::KP);
-        const int bi = __shfl(b, ib * 4);  // instance of block ib (its lane r = 0, c = 0)
-        const int on = __shfl(in_sweep ? 1 : 0, ib * 4);
+      const int bq0 = __shfl(b, 0), bq1 = __shfl(b, 4), bq2 = __shfl(b, 8), bq3 = __shfl(b, 12);
+      const unsigned long long in_mask = __ballot(in_sweep);
+      for (int i = lane; i < slot * 4 * KS; i += kBlock) {
+        const int e = i % KS, ib = (i / KS) % 4, sl = i / (4 * KS);
+        const int bi = ib == 0 ? bq0 : ib == 1 ? bq1 : ib == 2 ? bq2 : bq3;
+        const bool on = ((in_mask >> (ib * 4)) & 1ull) != 0ull;
         if (on) ((RS*)A.KD)[((size_t)(unsigned)(k_top - sl) * Bp + (unsigned)bi) * RR::KP + e] = (RS)sKD[i];
       }
       k_top -= slot;
@@ -896,7 +905,7 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
         pin(idx);
         sKDf[idx] = (T)(RS)KD;  // as stored
       } else {
-        int idx = (commit && offKD >= 0) ? (slot * 4 + blk) * R::KP + offKD : kBwdChunk * 4 * R::KP + lane;
+        int idx = (commit && offKD >= 0) ? (slot * 4 + blk) * KS + offKD : kBwdChunk * 4 * KS + lane;
         pin(idx);
         sKD[idx] = KD;
       }
@@ -980,8 +989,8 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
 
 template <class T, class M, bool CTG>
 __global__ __launch_bounds__(kBlock) void k_backward_mfma(DevArrays<T> A, DevOpts o, int all) {
-  using R = Rec<T, M::n, M::m>;
-  __shared__ double sKD[kBwdChunk * 4 * R::KP + kBlock];  // + one junk slot per lane
+  using RR = Rec<rec_scalar_t<T, M>, M::n, M::m>;
+  __shared__ double sKD[kBwdChunk * 4 * RR::KP + kBlock];  // + one junk slot per lane (stride of the stored record)
   backward_mfma_body<T, M, CTG, false>(A, o, all, threadIdx.x, xcd_block((int)blockIdx.x, (int)gridDim.x, A.xcd_remap) * 4, sKD, nullptr, 0,
                                        nullptr);
 }

@@ -2,6 +2,9 @@
 """Stress of unusual shapes against the oracle (round 6, after the N > 126 restart bug): long horizons, odd batch sizes, fp32
 records, Cholesky restarts on part of the batch.  Prints one line per case; exit code 1 if any schedule differs.
 
+The restart mix at the horizons around the gain chunks of both MFMA backward kernels, across model shapes, is a test now:
+tests/test_model_shapes_gpu.py::test_gain_chunk_horizons.  This script keeps the unicycle's long horizons and odd batches.
+
 usage (GPU box): python scripts/probe_shapes.py"""
 import ctypes
 import importlib
