@@ -472,6 +472,60 @@ class BatchSolver:
             raise AltroError("get_history failed: " + self._errmsg(self._h))
         return out[:cnt].copy()
 
+    # -- receding-horizon loops (include/altro_mpc.h) ------------------------------------------------
+    def mpc_row_map(self, shift):
+        """Where every dual / penalty row comes from under a shift of ``shift`` knots: the source row, or -1 for a row
+        that starts afresh.  Host-only (needs no device for the built-in constraint kinds)."""
+        f = self._fn("mpc_num_rows")
+        f.restype = C.c_int
+        rows = f(self._h)
+        out = np.empty(max(rows, 1), dtype=np.int32)
+        self._call("mpc_row_map", C.c_int(shift), out.ctypes.data_as(C.POINTER(C.c_int)))  # (reports what mpc_num_rows met)
+        if rows < 0:
+            raise AltroError(f"{self._p}mpc_num_rows failed: {self._errmsg(self._h)}")
+        return out[:rows]
+
+    def mpc_advance(self, shift, x0=None, w=None):
+        """Move the solved handle ``shift`` knots forward on the device (one launch): controls, gains, duals and penalties
+        shift, the tail holds; the new initial state is ``x0`` ([n] or [B][n]; default: the plan's X[shift]) plus the
+        disturbance ``w`` ([B][n])."""
+        x0, w = _f64(x0), _f64(w)
+        if x0 is not None and x0.shape not in ((self.n,), (self.batch, self.n)):
+            raise ValueError(f"x0 must have shape ({self.n},) or ({self.batch}, {self.n})")
+        if w is not None and w.shape != (self.batch, self.n):
+            raise ValueError(f"w must have shape ({self.batch}, {self.n})")
+        self._call("mpc_advance", C.c_int(shift), _dp(x0), C.c_int(1 if x0 is not None and x0.ndim == 2 else 0), _dp(w))
+
+    def mpc_advance_device(self, shift, x0_ptr=0, w_ptr=0):
+        """mpc_advance with fp64 arrays [B][n] in memory of this handle's device (either pointer may be 0)."""
+        self._call("mpc_advance_device", C.c_int(shift), C.c_void_p(x0_ptr or None), C.c_void_p(w_ptr or None))
+
+    def mpc_run(self, cycles, shift, w=None):
+        """``cycles`` x (solve; mpc_advance(shift, w=w[c])) with the closed-loop log kept on the device.  Returns
+        dict(X_cl [B][cycles*shift+1][n], U_cl [B][cycles*shift][m], iterations [B][cycles], status [B][cycles])."""
+        w = _f64(w)
+        if w is not None and w.shape != (cycles, self.batch, self.n):
+            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {self.n})")
+        L = max(cycles, 0) * max(shift, 0)
+        X = np.zeros((self.batch, L + 1, self.n))
+        U = np.zeros((self.batch, L, self.m))
+        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        self._call("mpc_run", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(X), _dp(U),
+                   it.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int)))
+        return dict(X_cl=X, U_cl=U, iterations=it, status=st)
+
+    def get_initial_state(self):
+        """What the next solve starts from, [B][n]."""
+        out = np.empty((self.batch, self.n))
+        self._call("get_initial_state", _dp(out))
+        return out
+
+    def set_penalties(self, rho):
+        """Counterpart of set_duals for the penalties, [B][rows]."""
+        rho = _f64(rho)
+        self._call("set_penalties", _dp(rho))
+
     # -- device interop ---------------------------------------------------------------------------
     def pack_results_device(self, device_ptr):
         self._call("pack_results_device", C.c_void_p(device_ptr))

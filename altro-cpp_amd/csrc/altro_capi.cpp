@@ -11,6 +11,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cctype>
 #include <cerrno>
@@ -20,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -30,12 +32,13 @@
 #include <vector>
 
 #include "altro_common.hpp"
+#include "../../include/altro_mpc.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 7  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 8  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -892,6 +895,158 @@ altro_status altro_pack_results_device(altro_handle h, void* dst_device) {
 altro_status altro_pack_trajectory_device(altro_handle h, void* X_device, void* U_device) {
   if (!X_device && !U_device) return ALTRO_INVALID_ARG;
   return Forward(h, [&](EngineBase& e) { return e.PackTrajectoryDevice((double*)X_device, (double*)U_device); });
+}
+
+}  // extern "C"
+
+// ---- receding-horizon loops (include/altro_mpc.h) -------------------------------------------------------------------
+namespace {
+
+// what can be said about an advance without a device: the range of the shift, and the handles whose per-knot data would
+// have to move along the horizon too
+altro_status MpcCheck(altro_handle h, int shift, const char* who) {
+  const int N = h->spec.desc.N;
+  if (shift < 1 || shift > N - 1) {
+    h->err = std::string(who) + ": the shift must lie in [1, N - 1] = [1, " + std::to_string(N - 1) + "], got " + std::to_string(shift);
+    return ALTRO_INVALID_ARG;
+  }
+  if (!h->spec.hk.empty() || !h->spec.tk.empty() || !h->spec.knot_model.empty()) {
+    h->err = std::string(who) + ": per-knot steps, times or models (altro_set_steps, altro_set_times, altro_set_knot_models) do "
+             "not move along the horizon yet";
+    return ALTRO_UNSUPPORTED;
+  }
+  return ALTRO_OK;
+}
+// rows and cone of every registered constraint: the built-in kinds from the recorded calls, user types from the engine
+altro_status MpcConShapes(altro_handle h, std::vector<int>* p, std::vector<int>* eq) {
+  if (!h->uploaded) {
+    bool user = false;
+    for (const ConSpec& c : h->spec.cons) user = user || c.kind == ALTRO_CON_USER;
+    if (!user) {
+      const int m = h->spec.desc.m;
+      for (const ConSpec& c : h->spec.cons) {
+        int rows = 0;
+        if (c.kind == ALTRO_CON_GOAL) {
+          rows = h->spec.desc.n;
+        } else if (c.kind == ALTRO_CON_CIRCLE) {
+          rows = c.nparams / 3;
+        } else if (c.kind == ALTRO_CON_CONTROL_BOUND) {  // (the finite bounds: GetFiniteIndices, basic_constraints.hpp:138-145)
+          for (int j = 0; j < 2 * m && j < c.nparams; ++j) rows += std::abs(c.params[j]) < std::numeric_limits<double>::max() ? 1 : 0;
+        } else {
+          h->err = "unknown constraint kind";
+          return ALTRO_INVALID_ARG;
+        }
+        p->push_back(rows);
+        eq->push_back(c.kind == ALTRO_CON_GOAL ? 1 : 0);
+      }
+      return ALTRO_OK;
+    }
+    const altro_status st = Ensure(h);  // (rows and cone of a user type are the model source's)
+    if (st != ALTRO_OK) return st;
+  }
+  h->engine->ConShapes(p, eq);
+  return ALTRO_OK;
+}
+altro_status MpcRowMapOf(altro_handle h, int shift, std::vector<int>* out) {
+  std::vector<int> kb, ke, p, eq;
+  const altro_status st = MpcConShapes(h, &p, &eq);
+  if (st != ALTRO_OK) return st;
+  for (const ConSpec& c : h->spec.cons) {
+    kb.push_back(c.k_begin);
+    ke.push_back(c.k_end);
+  }
+  *out = MpcRowMap(h->spec.desc.N, shift, kb, ke, p, eq);
+  return ALTRO_OK;
+}
+// the advance behind both entry points; x0 is [B][n] here
+altro_status MpcAdvanceImpl(altro_handle h, int shift, const double* x0, const double* w, int on_device) {
+  const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
+  const altro_status st = Forward(h, [&](EngineBase& e) { return e.MpcAdvance(shift, x0, w, on_device, pen); });
+  if (st == ALTRO_OK) {
+    // the initial state now lives on the device alone (altro_get_initial_state reads it): the recorded one is out of date
+    h->spec.x0.clear();
+    h->spec.x0_per_instance = 0;
+  }
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int altro_mpc_num_rows(altro_handle h) {
+  if (!h || Busy(h)) return -1;
+  std::vector<int> map;
+  if (MpcRowMapOf(h, 1, &map) != ALTRO_OK) return -1;
+  return (int)map.size();
+}
+altro_status altro_mpc_row_map(altro_handle h, int shift, int* src_row) {
+  if (!h || !src_row) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  altro_status st = MpcCheck(h, shift, "altro_mpc_row_map");
+  if (st != ALTRO_OK) return st;
+  std::vector<int> map;
+  st = MpcRowMapOf(h, shift, &map);
+  if (st != ALTRO_OK) return st;
+  std::copy(map.begin(), map.end(), src_row);
+  return ALTRO_OK;
+}
+altro_status altro_mpc_advance(altro_handle h, int shift, const double* x0, int x0_per_instance, const double* w) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const altro_status st = MpcCheck(h, shift, "altro_mpc_advance");
+  if (st != ALTRO_OK) return st;
+  std::vector<double> all;
+  if (x0 && !x0_per_instance) {  // one state for the whole batch
+    const int n = h->spec.desc.n, B = h->spec.desc.batch;
+    all.resize((size_t)B * n);
+    for (int b = 0; b < B; ++b) std::copy(x0, x0 + n, all.begin() + (size_t)b * n);
+    x0 = all.data();
+  }
+  return MpcAdvanceImpl(h, shift, x0, w, 0);
+}
+altro_status altro_mpc_advance_device(altro_handle h, int shift, const void* x0_device, const void* w_device) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const altro_status st = MpcCheck(h, shift, "altro_mpc_advance_device");
+  if (st != ALTRO_OK) return st;
+  return MpcAdvanceImpl(h, shift, (const double*)x0_device, (const double*)w_device, 1);
+}
+altro_status altro_mpc_run(altro_handle h, int cycles, int shift, const double* w, double* X_cl, double* U_cl, int* iterations,
+                           int* status) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (cycles < 1) {
+    h->err = "altro_mpc_run: at least one cycle";
+    return ALTRO_INVALID_ARG;
+  }
+  altro_status st = MpcCheck(h, shift, "altro_mpc_run");
+  if (st != ALTRO_OK) return st;
+  st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
+  const size_t per_cycle = (size_t)h->spec.desc.batch * h->spec.desc.n;
+  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
+    st = altro_solve_al(h);
+    if (st == ALTRO_OK) st = MpcAdvanceImpl(h, shift, nullptr, w ? w + (size_t)c * per_cycle : nullptr, 0);
+  }
+  if (h->uploaded) {
+    const std::string err = h->err;
+    const altro_status es = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);  // (also after a failure: it frees the log)
+    if (st == ALTRO_OK && es != ALTRO_OK) {
+      h->err = h->engine->LastError();
+      st = es;
+    } else {
+      h->err = err;
+    }
+  }
+  return st;
+}
+altro_status altro_get_initial_state(altro_handle h, double* x0) {
+  if (!x0) return ALTRO_INVALID_ARG;
+  return Forward(h, [&](EngineBase& e) { return e.GetInitialState(x0); });
+}
+altro_status altro_set_penalties(altro_handle h, const double* rho) {
+  if (!rho) return ALTRO_INVALID_ARG;
+  return Forward(h, [&](EngineBase& e) { return e.SetPenalties(rho); });
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // templated device engines (altro_engine.hpp).  No HIP types in here.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <vector>
@@ -60,6 +61,34 @@ struct ProblemSpec {
   double penalty = -1.0;  // SetPenalty issued before the device state exists
   double phi = -1.0;
 };
+
+// ---- receding-horizon advance (include/altro_mpc.h) --------------------------------------------------
+// Where every dual / penalty row comes from when the horizon moves forward by `shift` knots: src[r] in [0, rows), or -1 for a
+// row that starts afresh.  PER CONSTRAINT, not per knot class: constraint j (the j-th altro_add_constraint call; knots
+// [kb[j], ke[j]), p[j] rows, eq[j] != 0 for an equality) keeps its rows wherever it is attached to both the knot and the knot
+// the shift reads (min(k + shift, N - 1)).  Rows of a knot: equalities first, then inequalities, each in insertion order
+// (al_cost.hpp:267-272).  The terminal knot's rows map to themselves.
+inline std::vector<int> MpcRowMap(int N, int shift, const std::vector<int>& kb, const std::vector<int>& ke, const std::vector<int>& p,
+                                  const std::vector<int>& eq) {
+  const int J = (int)kb.size();
+  std::vector<std::vector<int>> row_of(N + 1, std::vector<int>(J, -1));  // first row of constraint j at knot k
+  int rows = 0;
+  for (int k = 0; k <= N; ++k)
+    for (int pass = 0; pass < 2; ++pass)
+      for (int j = 0; j < J; ++j)
+        if (k >= kb[j] && k < ke[j] && (eq[j] != 0) == (pass == 0)) {
+          row_of[k][j] = rows;
+          rows += p[j];
+        }
+  std::vector<int> src(rows, -1);
+  for (int k = 0; k <= N; ++k) {
+    const int ks = k < N ? std::min(k + shift, N - 1) : N;
+    for (int j = 0; j < J; ++j)
+      if (row_of[k][j] >= 0 && row_of[ks][j] >= 0)
+        for (int i = 0; i < p[j]; ++i) src[row_of[k][j] + i] = row_of[ks][j] + i;
+  }
+  return src;
+}
 
 // ---- device-visible problem description (lives in global memory, read with scalar loads) ---------
 struct ConDesc {
@@ -188,6 +217,16 @@ class EngineBase {
   virtual altro_status PackResultsDevice(void* dst) = 0;
   virtual altro_status PackTrajectoryDevice(double* X, double* U) = 0;
   virtual altro_status DeviceInfo(char* name, int name_len, int* cu_count) = 0;
+  // receding-horizon advance (include/altro_mpc.h).  x0, w: fp64 [B][n] or nullptr, host arrays or (on_device) memory of the
+  // engine's device; reset_pen: the penalty of a row that starts afresh.
+  virtual altro_status MpcAdvance(int shift, const double* x0, const double* w, int on_device, double reset_pen) = 0;
+  // closed-loop log of altro_mpc_run: every advance between Begin and End appends what the loop applied
+  virtual altro_status MpcLogBegin(int cycles, int shift) = 0;
+  virtual altro_status MpcLogEnd(double* X_cl, double* U_cl, int* iterations, int* status) = 0;
+  virtual altro_status GetInitialState(double* x0) = 0;
+  virtual altro_status SetPenalties(const double* rho) = 0;
+  // rows and cone (1: equality) of every registered constraint, in registration order
+  virtual void ConShapes(std::vector<int>* p, std::vector<int>* eq) = 0;
   virtual const char* LastError() = 0;
 };
 

@@ -567,7 +567,143 @@ class Engine final : public EngineBase {
     return Sync();
   }
 
+  // ---- receding-horizon advance (include/altro_mpc.h) ----------------------------------------------
+  // One launch (k_mpc_advance) on the engine's stream; the row map of a shift is built once and stays on the device.
+  // Model-independent: the kernel never calls the dynamics.  Expansions, knot costs, stored constraint values and cost-to-go
+  // records stay where they are -- the next solve recomputes them -- so what a cost-to-go replay would read is gone.
+  altro_status MpcAdvance(int shift, const double* x0, const double* w, int on_device, double reset_pen) override {
+    if (shift < 1 || shift > N_ - 1) {
+      err_ = "altro_mpc_advance: the shift must lie in [1, N - 1]";
+      return ALTRO_INVALID_ARG;
+    }
+    if (kTimeVarying || A_.hk || A_.knot_model) {
+      err_ = "altro_mpc_advance: per-knot steps, times or models (a time-varying or discrete user model included) do not move "
+             "along the horizon yet";
+      return ALTRO_UNSUPPORTED;
+    }
+    constexpr int kdv = RR::KP * (int)sizeof(RS) / 16, xv = R::nP * (int)sizeof(T) / 16, uv = R::mP * (int)sizeof(T) / 16;
+    constexpr int widest = kdv > xv ? (kdv > uv ? kdv : uv) : (xv > uv ? xv : uv);
+    static_assert(widest <= kMpcThreads * kMpcItems, "one record must fit a chunk of k_mpc_advance");
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ctg_replayable_ = false;
+    ctg_fresh_ = false;
+    const int* map = nullptr;
+    {
+      altro_status st = MpcMap(shift, &map);
+      if (st != ALTRO_OK) return st;
+    }
+    MpcArgs g{};
+    g.shift = shift;
+    // columns per workgroup: one for a small batch (its knots spread over the lanes), up to 64 for a large one (the lanes
+    // run along the records of neighbouring columns); never more than one chunk of the widest record holds
+    g.tile = 1;
+    while (g.tile < 64 && g.tile * 128 < B_ && 2 * g.tile * widest <= kMpcThreads * kMpcItems) g.tile *= 2;
+    g.n = n;
+    g.m = m;
+    g.kd_vecs = kdv;
+    g.rows = pd_.total_rows;
+    g.row_src = map;
+    g.reset_pen = reset_pen;
+    if ((x0 || w) && !on_device) {
+      const size_t cnt = (size_t)B_ * n;
+      altro_status st = EnsureStage(2 * cnt);
+      if (st != ALTRO_OK) return st;
+      if (x0) ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, x0, cnt * sizeof(double), hipMemcpyHostToDevice, stream_));
+      if (w) ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_ + cnt, w, cnt * sizeof(double), hipMemcpyHostToDevice, stream_));
+      g.x0 = x0 ? d_stage_ : nullptr;
+      g.w = w ? d_stage_ + cnt : nullptr;
+    } else {
+      g.x0 = x0;
+      g.w = w;
+    }
+    if (mpc_log_X_ && shift == mpc_log_shift_ && mpc_log_cycle_ < mpc_log_cycles_) {
+      g.Xlog = mpc_log_X_;
+      g.Ulog = mpc_log_U_;
+      g.itlog = mpc_log_it_;
+      g.stlog = mpc_log_it_ + (size_t)B_ * mpc_log_cycles_;
+      g.cycle = mpc_log_cycle_++;
+      g.cycles = mpc_log_cycles_;
+    }
+    hipLaunchKernelGGL(k_mpc_advance<T>, dim3((B_ + g.tile - 1) / g.tile, 5), dim3(kMpcThreads), 0, stream_, A_, g);
+    return Sync();
+  }
+  altro_status MpcLogBegin(int cycles, int shift) override {
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    MpcLogDrop();
+    const size_t nx = (size_t)B_ * ((size_t)cycles * shift + 1) * n, nu = (size_t)B_ * cycles * shift * m;
+    ALTRO_HIP_CHECK(hipMalloc((void**)&mpc_log_X_, (nx + nu) * sizeof(double)));
+    mpc_log_U_ = mpc_log_X_ + nx;
+    if (hipMalloc((void**)&mpc_log_it_, 2 * (size_t)B_ * cycles * sizeof(int)) != hipSuccess) {
+      MpcLogDrop();
+      err_ = "altro_mpc_run: out of device memory for the closed-loop log";
+      return ALTRO_HIP_ERROR;
+    }
+    mpc_log_cycles_ = cycles;
+    mpc_log_shift_ = shift;
+    mpc_log_cycle_ = 0;
+    return ALTRO_OK;
+  }
+  altro_status MpcLogEnd(double* X_cl, double* U_cl, int* iterations, int* status) override {
+    hipError_t e = hipSetDevice(desc_.device_id);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (mpc_log_X_ && mpc_log_cycle_ == mpc_log_cycles_) {
+      const size_t L = (size_t)mpc_log_cycles_ * mpc_log_shift_, bc = (size_t)B_ * mpc_log_cycles_;
+      if (e == hipSuccess && X_cl) e = CopySync(X_cl, mpc_log_X_, (size_t)B_ * (L + 1) * n * sizeof(double), hipMemcpyDeviceToHost);
+      if (e == hipSuccess && U_cl) e = CopySync(U_cl, mpc_log_U_, (size_t)B_ * L * m * sizeof(double), hipMemcpyDeviceToHost);
+      if (e == hipSuccess && iterations) e = CopySync(iterations, mpc_log_it_, bc * sizeof(int), hipMemcpyDeviceToHost);
+      if (e == hipSuccess && status) e = CopySync(status, mpc_log_it_ + bc, bc * sizeof(int), hipMemcpyDeviceToHost);
+    }
+    MpcLogDrop();
+    ALTRO_HIP_CHECK(e);
+    return ALTRO_OK;
+  }
+  altro_status GetInitialState(double* x0) override { return DownloadRec(A_.x0, 1, R::nP, 0, n, x0); }
+  altro_status SetPenalties(const double* rho) override {
+    ctg_replayable_ = false;
+    const int R = pd_.total_rows;
+    if (R == 0) return ALTRO_OK;
+    std::vector<T> h((size_t)R * Bp_, T(0));
+    for (int b = 0; b < B_; ++b)
+      for (int r = 0; r < R; ++r) h[(size_t)r * Bp_ + b] = T(rho[(size_t)b * R + r]);
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    {
+      altro_status st = Sync();
+      if (st != ALTRO_OK) return st;
+    }
+    ALTRO_HIP_CHECK(CopySync(A_.pen, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return ALTRO_OK;
+  }
+  void ConShapes(std::vector<int>* p, std::vector<int>* eq) override {
+    *p = con_p_;
+    *eq = con_eq_;
+  }
+
  private:
+  // the device copy of MpcRowMap(shift), built at the first advance by that shift
+  altro_status MpcMap(int shift, const int** out) {
+    auto it = mpc_maps_.find(shift);
+    if (it == mpc_maps_.end()) {
+      const std::vector<int> src = MpcRowMap(N_, shift, con_kb_, con_ke_, con_p_, con_eq_);
+      if ((int)src.size() != pd_.total_rows) {
+        err_ = "altro_mpc_advance: the row map does not match the rows on the device";
+        return ALTRO_HIP_ERROR;
+      }
+      int* d = nullptr;
+      altro_status st = Alloc(&d, src.size());
+      if (st != ALTRO_OK) return st;
+      if (!src.empty()) ALTRO_HIP_CHECK(CopySync(d, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice));
+      it = mpc_maps_.emplace(shift, d).first;
+    }
+    *out = it->second;
+    return ALTRO_OK;
+  }
+  void MpcLogDrop() {
+    if (mpc_log_X_) hipFree(mpc_log_X_);
+    if (mpc_log_it_) hipFree(mpc_log_it_);
+    mpc_log_X_ = mpc_log_U_ = nullptr;
+    mpc_log_it_ = nullptr;
+    mpc_log_cycles_ = mpc_log_shift_ = mpc_log_cycle_ = 0;
+  }
   // ---- helpers ----------------------------------------------------------------------------------
   dim3 GridB() const { return dim3((B_ + kBlock - 1) / kBlock); }
   dim3 GridBK() const { return dim3((B_ + kBlock - 1) / kBlock, N_ + 1); }
@@ -712,6 +848,7 @@ class Engine final : public EngineBase {
     hipStreamSynchronize(stream_);
     for (void* p : allocs_) hipFree(p);
     allocs_.clear();
+    mpc_maps_.clear();
     d_hk_ = d_tk_ = nullptr;
     if (counted_chained_) ChainClaim(desc_.device_id, -1);
     counted_chained_ = false;
@@ -752,6 +889,7 @@ class Engine final : public EngineBase {
     allocs_.clear();
     if (A_.hist) hipFree(A_.hist);
     if (A_.hist_len) hipFree(A_.hist_len);
+    MpcLogDrop();
     if (d_stage_) hipFree(d_stage_);
     d_stage_ = nullptr;
     stage_cap_ = 0;
@@ -1108,6 +1246,13 @@ class Engine final : public EngineBase {
         d.param_off = first;
       }
       built[i].d = d;
+    }
+    con_kb_.clear(); con_ke_.clear(); con_p_.clear(); con_eq_.clear();
+    for (size_t i = 0; i < s.cons.size(); ++i) {  // (what the row map of a receding-horizon advance is built from: MpcRowMap)
+      con_kb_.push_back(s.cons[i].k_begin);
+      con_ke_.push_back(s.cons[i].k_end);
+      con_p_.push_back(built[i].d.p);
+      con_eq_.push_back(built[i].d.type == 0 ? 1 : 0);
     }
     std::vector<std::vector<int>> knot_cons(N_ + 1);
     for (size_t i = 0; i < s.cons.size(); ++i)
@@ -2361,6 +2506,11 @@ class Engine final : public EngineBase {
   int* d_scalarI_ = nullptr;
   double* d_phi_ = nullptr;
   std::vector<int> knot_class_, knot_rowbase_;
+  std::vector<int> con_kb_, con_ke_, con_p_, con_eq_;  // knots, rows and cone of every registered constraint
+  std::map<int, int*> mpc_maps_;                       // shift -> device row map of the advance (owned through allocs_)
+  double *mpc_log_X_ = nullptr, *mpc_log_U_ = nullptr;  // closed-loop log of altro_mpc_run (MpcLogBegin .. MpcLogEnd)
+  int* mpc_log_it_ = nullptr;                           // iterations [B][cycles], then statuses [B][cycles]
+  int mpc_log_cycles_ = 0, mpc_log_shift_ = 0, mpc_log_cycle_ = 0;
   std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;
   volatile int* h_counter_ = nullptr;  // pinned + mapped: one word per sweep

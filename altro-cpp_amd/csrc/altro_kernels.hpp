@@ -4799,4 +4799,126 @@ __global__ __launch_bounds__(kBlock) void k_pack_results(DevArrays<T> A, double*
   dst[4 * (size_t)b + 3] = (double)(ilqr_mode ? A.status[b] : A.status_al[b]);
 }
 
+// -------------------------------------------------------------------------------------------------
+// Receding-horizon advance (include/altro_mpc.h): ONE launch moves everything a warm-started solve reads forward by
+// `shift` knots -- X[k] <- X[min(k + s, N)], U / gain records [k] <- [min(k + s, N - 1)], every dual / penalty row from the
+// row the host-built map names (or afresh) -- writes the new initial state (x0 given, else X[s]; + w) and, while
+// altro_mpc_run is logging, what the loop applied: X, U[0 .. s) and the statistics of the solve behind them.
+//
+// Grid (column tiles, 5): blockIdx.y picks the array (X, U, gain records, duals, penalties), blockIdx.x a tile of
+// `tile` neighbouring instance columns, so every (array, column) has ONE owner.  The shift reads knots that it
+// overwrites; the owner works through its columns front to back in chunks of as many knots as its threads hold in
+// registers (kMpcItems 16-byte units each): load the chunk, barrier, store it.  Sources lie at or behind their
+// destinations (k + s > k, and a later knot's rows come later), so a chunk never reads what an earlier chunk wrote, and
+// the barrier keeps a chunk's own stores behind its loads: correct whatever order the workgroups run in.  Everything else
+// that reads the old X / U (initial state, log) is done by the same owner before its first store.
+// A batch of one: tile = 1, the knots of the column spread over the 256 lanes -- a couple of memory round trips, not N.
+// A large batch: the tile's records of one knot are contiguous (arr[(k * Bp + b) * EP + e]), lanes run along them.
+// -------------------------------------------------------------------------------------------------
+constexpr int kMpcThreads = 256, kMpcItems = 8;
+struct MpcArgs {
+  int shift, tile;
+  int n, m;                  // meaningful elements of an X / U record (the padding behind them is written as zero)
+  int kd_vecs;               // 16-byte units of one gain record (moved as stored: fp32 under WithRec32<>)
+  int rows;
+  const int* row_src;        // [rows]: source row, -1 = afresh
+  double reset_pen;
+  const double *x0, *w;      // [B][n] fp64, either may be null
+  double *Xlog, *Ulog;       // closed-loop log [B][cycles * shift + 1][n], [B][cycles * shift][m]; null: not logging
+  int *itlog, *stlog;        // [B][cycles]
+  int cycle, cycles;
+};
+// units [0, units) of `per_unit` V each, unit u at base + u * stride: unit u <- unit src(u) (src(u) >= u, or < 0: fix decides)
+template <class V, class SrcFn, class FixFn>
+__device__ __forceinline__ void mpc_shift_units(V* base, int units, int per_unit, size_t stride, SrcFn src, FixFn fix) {
+  const int chunk = max(1, kMpcThreads * kMpcItems / per_unit);  // (the host keeps per_unit <= kMpcThreads * kMpcItems)
+  for (int u0 = 0; u0 < units; u0 += chunk) {
+    const int cnt = min(chunk, units - u0) * per_unit;
+    V reg[kMpcItems];
+#pragma unroll
+    for (int j = 0; j < kMpcItems; ++j) {
+      const int idx = (int)threadIdx.x + j * kMpcThreads;
+      if (idx < cnt) {
+        const int ul = idx / per_unit, i = idx - ul * per_unit, su = src(u0 + ul);
+        reg[j] = su >= 0 ? base[(size_t)su * stride + i] : V{};
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kMpcItems; ++j) {
+      const int idx = (int)threadIdx.x + j * kMpcThreads;
+      if (idx < cnt) {
+        const int ul = idx / per_unit, i = idx - ul * per_unit;
+        base[(size_t)(u0 + ul) * stride + i] = fix(reg[j], src(u0 + ul), i);
+      }
+    }
+  }
+}
+template <class T>
+__global__ __launch_bounds__(kMpcThreads) void k_mpc_advance(DevArrays<T> A, MpcArgs g) {
+  constexpr int VN = 16 / (int)sizeof(T);
+  const int b0 = (int)blockIdx.x * g.tile, nb = min(g.tile, A.B - b0);
+  if (nb <= 0) return;
+  const int N = A.N, s = g.shift, job = (int)blockIdx.y, tid = (int)threadIdx.x;
+  const size_t Bp = (size_t)A.Bp;
+  const int nP = (g.n + VN - 1) / VN * VN, mP = (g.m + VN - 1) / VN * VN;
+  // a record of E meaningful elements as 16-byte units: the elements behind E leave as zero
+  auto keep = [](uint4 v, int vec, int E) {
+    T* e = reinterpret_cast<T*>(&v);
+#pragma unroll
+    for (int j = 0; j < VN; ++j)
+      if (vec * VN + j >= E) e[j] = T(0);
+    return v;
+  };
+  if (job == 0) {
+    const int L = g.cycles * s + 1;
+    for (int idx = tid; idx < nb * nP; idx += kMpcThreads) {
+      const int b = b0 + idx / nP, e = idx % nP;
+      T v = T(0);
+      if (e < g.n) {
+        double x = g.x0 ? g.x0[(size_t)b * g.n + e] : (double)A.X[((size_t)s * Bp + b) * nP + e];
+        if (g.w) x += g.w[(size_t)b * g.n + e];
+        v = T(x);
+        if (g.Xlog) g.Xlog[((size_t)b * L + (size_t)(g.cycle + 1) * s) * g.n + e] = (double)v;
+      }
+      A.x0[(size_t)b * nP + e] = v;
+    }
+    if (g.Xlog) {
+      for (int idx = tid; idx < s * nb * g.n; idx += kMpcThreads) {
+        const int j = idx / (nb * g.n), r = idx - j * (nb * g.n), b = b0 + r / g.n, e = r % g.n;
+        g.Xlog[((size_t)b * L + (size_t)g.cycle * s + j) * g.n + e] = (double)A.X[((size_t)j * Bp + b) * nP + e];
+      }
+      for (int idx = tid; idx < nb; idx += kMpcThreads) {
+        g.itlog[(size_t)(b0 + idx) * g.cycles + g.cycle] = A.it_total[b0 + idx];
+        g.stlog[(size_t)(b0 + idx) * g.cycles + g.cycle] = A.status_al[b0 + idx];
+      }
+    }
+    __syncthreads();  // (every read of the old X above is behind us)
+    const int vpr = nP / VN, n = g.n;
+    mpc_shift_units(reinterpret_cast<uint4*>(A.X) + (size_t)b0 * vpr, N + 1, nb * vpr, Bp * vpr,
+                    [=](int k) { return min(k + s, N); }, [=](uint4 v, int, int i) { return keep(v, i % vpr, n); });
+  } else if (job == 1) {
+    if (g.Ulog) {
+      const size_t L = (size_t)g.cycles * s;
+      for (int idx = tid; idx < s * nb * g.m; idx += kMpcThreads) {
+        const int j = idx / (nb * g.m), r = idx - j * (nb * g.m), b = b0 + r / g.m, e = r % g.m;
+        g.Ulog[((size_t)b * L + (size_t)g.cycle * s + j) * g.m + e] = (double)A.U[((size_t)j * Bp + b) * mP + e];
+      }
+    }
+    __syncthreads();
+    const int vpr = mP / VN, m = g.m;
+    mpc_shift_units(reinterpret_cast<uint4*>(A.U) + (size_t)b0 * vpr, N, nb * vpr, Bp * vpr,
+                    [=](int k) { return min(k + s, N - 1); }, [=](uint4 v, int, int i) { return keep(v, i % vpr, m); });
+  } else if (job == 2) {
+    const int vpr = g.kd_vecs;
+    mpc_shift_units(reinterpret_cast<uint4*>(A.KD) + (size_t)b0 * vpr, N, nb * vpr, Bp * vpr,
+                    [=](int k) { return min(k + s, N - 1); }, [](uint4 v, int, int) { return v; });
+  } else {
+    const int* __restrict__ map = g.row_src;
+    const T fresh = job == 3 ? T(0) : T(g.reset_pen);
+    mpc_shift_units((job == 3 ? A.lam : A.pen) + b0, g.rows, nb, Bp, [=](int r) { return map[r]; },
+                    [=](T v, int su, int) { return su >= 0 ? v : fresh; });
+  }
+}
+
 }  // namespace altro_hip

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../altro_hip.h"
+#include "../altro_mpc.h"
 
 namespace altro {
 
@@ -1294,6 +1295,17 @@ class AugmentedLagrangianiLQR {
     ilqr_solver_.Pull(true, true);
     status_ = ilqr_solver_.StatusAL();
     ilqr_solver_.AfterSolve();
+  }
+  // Receding horizon (include/altro_mpc.h): the solved handle moves `shift` knots forward ON THE DEVICE -- controls, gains,
+  // duals and penalties shift, the tail holds -- and the next Solve() starts from x0 ([B][n]; default: the plan's state at knot
+  // `shift`) plus the disturbance w ([B][n]).  With GetOptions().reset_duals = false (al_solver.hpp:292-297) that next
+  // solve is warm.  Solve() pushes the shared Trajectory again every time, so the mirror is refreshed here: it then holds
+  // the shifted guess, and the push puts back what the device already has.  (The Problem's initial state is applied once,
+  // at InitializeFromProblem; nothing pushes it again.)
+  void AdvanceHorizon(int shift, const double* x0 = nullptr, const double* w = nullptr) {
+    ilqr_solver_.PushOptions();  // (rows that start afresh take the caller's initial_penalty)
+    detail::Check(Handle(), altro_mpc_advance(Handle(), shift, x0, 1, w), "altro_mpc_advance");
+    ilqr_solver_.Pull(true, false);
   }
   // al_solver.hpp:287-302: duals and penalties reset as the options say, statistics reset, "viol" and "pen" logged
   void Init() {

@@ -1,0 +1,68 @@
+/* altro_mpc.h -- receding-horizon (model-predictive control) loops on a batched handle of include/altro_hip.h.
+ *
+ * The solver exists for MPC: solve, apply the first controls, move the horizon forward, warm-start, solve again.  The
+ * warm start itself is two options of the reference -- AugmentedLagrangianiLQR::Init keeps the duals with
+ * reset_duals = 0 and the penalties with initial_penalty = 0 (altro/augmented_lagrangian/al_solver.hpp:292-297) -- and
+ * the handle keeps trajectory, gains, duals and penalties on the device between solves.  This header adds the missing
+ * third part, the ADVANCE of a solved handle by `shift` knots, as one kernel launch on the handle's device: nothing of
+ * the warm start crosses to the host.  Exported by libaltro_hip.so.
+ *
+ * The advance, per instance b (N = segments, 1 <= shift <= N - 1, "old" = the device arrays when the call is made):
+ *   controls, gains   U_new[k] = U_old[min(k + shift, N - 1)], likewise the gain records K, d   (k = 0 .. N-1: the tail
+ *                     repeats the last stage knot)
+ *   states            X_new[k] = X_old[min(k + shift, N)]   (k = 0 .. N; a guess only: the next solve rolls X out again)
+ *   initial state     x0_new = (x0 if given, else X_old[shift]) + (w if given), evaluated in fp64
+ *   duals, penalties  per CONSTRAINT (the j-th altro_add_constraint / altro_add_user_constraint_type call), not per knot
+ *                     class: for a stage knot k with src = min(k + shift, N - 1), a constraint attached to both k and src
+ *                     takes lambda and rho of its rows at src; attached to k only, its rows start afresh -- lambda = 0,
+ *                     rho = options.initial_penalty if that is > 0, else 1 (a new ConstraintValues,
+ *                     altro/constraints/constraint_values.hpp:39-51).  The terminal knot's rows stay.
+ * Everything else stays: options, statistics, history, the guess altro_reset_trajectory restores, and the costs, which
+ * remain attached to knot indices.  Expansions, knot costs, stored constraint values and cost-to-go records are not moved;
+ * the next solve recomputes them (altro_get_ctg answers ALTRO_NOT_READY until then).
+ *
+ * Refused: shift out of range (ALTRO_INVALID_ARG); a handle with per-knot steps, times or models, or a time-varying or
+ * discrete user model (ALTRO_UNSUPPORTED); an asynchronous solve in flight (ALTRO_NOT_READY); no usable device
+ * (ALTRO_HIP_ERROR -- there is no CPU fallback). */
+#ifndef ALTRO_MPC_H_
+#define ALTRO_MPC_H_
+
+#include "altro_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Host-only: where every dual / penalty row comes from under a shift: src_row[r] in [0, rows), or -1 for a row that
+ * starts afresh; src_row holds altro_num_constraints(h) entries (altro_mpc_num_rows(h) says how many without a device).
+ * Needs no device for the built-in constraint kinds; works as soon as the constraints are registered. */
+altro_status altro_mpc_row_map(altro_handle h, int shift, int* src_row);
+int altro_mpc_num_rows(altro_handle h);
+
+/* The advance.  x0 ([n], or [B][n] with x0_per_instance) and w ([B][n]) are host arrays, either may be NULL; they are
+ * copied during the call. */
+altro_status altro_mpc_advance(altro_handle h, int shift, const double* x0, int x0_per_instance, const double* w);
+/* The same with fp64 arrays [B][n] in memory of the handle's device (either may be NULL): nothing crosses to the host.
+ * Like altro_pack_*_device it returns when the work on the handle's stream is done. */
+altro_status altro_mpc_advance_device(altro_handle h, int shift, const void* x0_device, const void* w_device);
+
+/* cycles x (altro_solve_al with the handle's options as they stand; record; advance with x0 = the plan, w = w[c]) --
+ * bit for bit the caller's own loop of altro_solve_al and altro_mpc_advance.  w: host [cycles][B][n] or NULL.
+ * Outputs (host, each may be NULL), instance-major like trajectories:
+ *   X_cl[B][cycles*shift + 1][n], U_cl[B][cycles*shift][m]: what the loop applied -- rows c*shift .. c*shift+shift-1 are
+ *   X, U[0 .. shift) of cycle c's solution (X_cl[b][c*shift] is the initial state cycle c was solved from); the last row
+ *   of X_cl is the initial state after the last advance;
+ *   iterations[B][cycles], status[B][cycles]: iterations_total and the AL status of every cycle's solve.
+ * The log is written on the device by the advance and downloaded once at the end. */
+altro_status altro_mpc_run(altro_handle h, int cycles, int shift, const double* w, double* X_cl, double* U_cl, int* iterations,
+                           int* status);
+
+/* What the next solve starts from, [B][n]. */
+altro_status altro_get_initial_state(altro_handle h, double* x0);
+/* Counterpart of altro_set_duals for the penalties, [B][rows]. */
+altro_status altro_set_penalties(altro_handle h, const double* rho);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ALTRO_MPC_H_ */
