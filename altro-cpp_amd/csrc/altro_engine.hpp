@@ -763,11 +763,12 @@ class Engine final : public EngineBase {
     hipLaunchKernelGGL((k_backward<T, M>), dim3((ninst + kBlock - 1) / kBlock), dim3(kBlock), 0, cur_, A, d, all);
   }
   // The fused sweep kernel needs the MFMA backward pass, the LDS-staged forward pass with one instance
-  // per workgroup, no cost-to-go recording and at most 20 line-search trials.
+  // per workgroup, no cost-to-go recording and 1 .. 20 line-search trials (with none the forward pass hands on the status
+  // the backward pass left, which the batched forward kernels read back from memory).
   bool FusedOk(const DevOpts& d) const {
     if constexpr (!kMfmaBackward) return false;
     return !force_valu_backward_ && !no_fused_ && mfma_offsets_ok_ && fwd_lds_bytes_ > 0 && !A_.record_ctg && !A_.hk &&
-           d.line_search_max_iterations <= kLineSearchLanes && fused_lds_bytes_ <= 160 * 1024;
+           d.line_search_max_iterations >= 1 && d.line_search_max_iterations <= kLineSearchLanes && fused_lds_bytes_ <= 160 * 1024;
   }
   // Forward pass launch: instances per wavefront and the LDS-staged variant are chosen from the size
   // of one instance's read-only block (X, U, K, d, lambda, rho); see k_forward.

@@ -673,6 +673,9 @@ constexpr int kBwdChunk = 126;  // knots of gains buffered in LDS between two bu
 // regularisation (spec_rho, spec_drho = what phase 3 will set).  Nothing is written to global memory: the gains go to
 // a second LDS block (sKDf), the hand-over values to fh[1], [2], [4], [5], the regularisation that was used to fh[6]
 // and fh[7] = 1 if the pass went through without a Cholesky failure (a failure simply invalidates the speculation).
+// lds_unset (FUSED, the first iteration of a launch): sKDf does not hold the instance's gains yet -- the kernel stages none,
+// every pass that reaches knot 0 writes them all.  A pass that GIVES UP leaves the knots from its lowest failing knot down
+// untouched (ilqr.hpp:409-427), so it fetches those from A.KD; in later iterations sKDf holds the previous pass's gains.
 // The wave takes part in the workgroup barriers of the forward pass: one after every knot with even index (the
 // forward waves sync once per pair of knots), counted in *nbar for the caller to top up.  Plain s_barrier: nothing
 // this wave writes is read before the kernel's own __syncthreads.  (Schedules that decouple the two paces -- 70 % or
@@ -681,7 +684,7 @@ constexpr int kBwdChunk = 126;  // knots of gains buffered in LDS between two bu
 template <class T, class M, bool CTG, bool FUSED, bool SPEC = false, int AHEAD = kBwdAhead>
 ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int all, int lane, int slot_base,
                                   double* sKD, T* sKDf, int fused_junk, double* fh, double spec_rho = 0.0,
-                                  double spec_drho = 0.0, int* nbar = nullptr, int b_fixed = -1) {
+                                  double spec_drho = 0.0, int* nbar = nullptr, int b_fixed = -1, bool lds_unset = false) {
   static_assert(!SPEC || FUSED, "the speculative pass is a variant of the fused one");
   // 4 x 4 tiles with the vectors riding as column n: n <= 3 states, m <= 2 controls (round 4: was n = 3, m = 2 only -- the
   // tile offsets below are generic; what m = 1 changes is the 2 x 2 inverse, see qc)
@@ -735,6 +738,7 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
   bool spec_bad = false;
   double dV0 = 0.0, dV1 = 0.0;  // zeroed once, NOT per retry (quirk Q4)
   int max_reg_count = 0;
+  int klow = N;  // (FUSED) the lowest knot at which a sweep of this pass failed
   int status = A.status[b];
   bool need = inst_on && N > 0;
   const unsigned verdict_bit = 1u << (blk * 4);
@@ -819,6 +823,12 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
     //  chunk; with N > kBwdChunk they are other knots' gains, and writing them out corrupted the finished instance's record.
     //  Found in round 6 by an experimental build with 32-knot chunks on the obstacle batch, whose Cholesky restarts are real.)
     int slot = 0, k_top = N - 1;
+    // Slots of the current chunk that hold this block's gains: all of them while its sweep runs; after a failed factorisation
+    // the ones above the failing knot, and none of the chunks that follow.  The block keeps walking to knot 0 and `slot` keeps
+    // counting, but the reference leaves the gains of the failing knot and of every knot below it untouched (ilqr.hpp:409-427)
+    // and those slots hold whatever an earlier chunk or sweep left there.  A retry writes the knots again; after the give-up
+    // (bp_reg_fail_threshold) nothing does, and the forward pass of the same iteration rolled out with what was flushed.
+    int good = kBwdChunk + 1;
     // The instance of each block (its lane r = 0, c = 0) and whether it takes part are gathered BEFORE the loop, with the
     // whole wavefront active: in the loop's last pass only the lanes below the element count run, and a shuffle from a lane
     // outside them does not return that lane's value.  (With a 2-element gain record -- n = m = 1 in fp64 -- a pass that
@@ -826,15 +836,18 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
     // gains of that knot were never stored.  Found by tests/test_model_shapes_gpu.py at N = 127.)
     auto flush = [&]() __attribute__((always_inline)) {
       const int bq0 = __shfl(b, 0), bq1 = __shfl(b, 4), bq2 = __shfl(b, 8), bq3 = __shfl(b, 12);
+      const int gq0 = __shfl(good, 0), gq1 = __shfl(good, 4), gq2 = __shfl(good, 8), gq3 = __shfl(good, 12);
       const unsigned long long in_mask = __ballot(in_sweep);
       for (int i = lane; i < slot * 4 * KS; i += kBlock) {
         const int e = i % KS, ib = (i / KS) % 4, sl = i / (4 * KS);
         const int bi = ib == 0 ? bq0 : ib == 1 ? bq1 : ib == 2 ? bq2 : bq3;
-        const bool on = ((in_mask >> (ib * 4)) & 1ull) != 0ull;
+        const int gi = ib == 0 ? gq0 : ib == 1 ? gq1 : ib == 2 ? gq2 : gq3;
+        const bool on = ((in_mask >> (ib * 4)) & 1ull) != 0ull && sl < gi;
         if (on) ((RS*)A.KD)[((size_t)(unsigned)(k_top - sl) * Bp + (unsigned)bi) * RR::KP + e] = (RS)sKD[i];
       }
       k_top -= slot;
       slot = 0;
+      good = running ? good : 0;
     };
     auto step = [&](int k, Tiles& S) __attribute__((always_inline)) {
       // The vector column / the gain rows ride along unmasked: used as a LEFT operand they only add
@@ -890,6 +903,14 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
         max_reg_count = failed ? cnt2 : max_reg_count;
         status = (failed && give) ? (int)ALTRO_BACKWARD_PASS_REGULARIZATION_FAILED : status;
         gave_up = failed && give;
+        good = failed ? slot : good;  // (the failing knot's slot and the ones behind it are not this sweep's)
+        if (FUSED && !SPEC) {
+          klow = (failed && k < klow) ? k : klow;
+          if (lds_unset && gave_up && offKD >= 0) {
+            for (int kk = 0; kk <= klow; ++kk)
+              sKDf[kk * R::KP + offKD] = (T)((const RS*)A.KD)[((size_t)(unsigned)kk * Bp + (unsigned)b) * RR::KP + offKD];
+          }
+        }
       }
       Pp = commit ? Pn : Pp;
       pin(Pp);
@@ -2296,7 +2317,9 @@ __global__ __launch_bounds__(kBlock) void k_forward(DevArrays<T> A, const Proble
   T alpha_sel = T(0);
   double J_sel = J0, z_sel = -1.0, g_sel = 0.0;
   int t_replay = -1;  // trial whose candidate defines c_ (and Z_ when accepted)
-  int last_status = ALTRO_UNSOLVED;
+  // (no trial at all -- line_search_max_iterations = 0: no rollout runs, and status_ stays what the backward pass left,
+  //  kBackwardPassRegularizationFailed included: ilqr.hpp:525)
+  int last_status = (ls_max > 0 || !valid) ? (int)ALTRO_UNSOLVED : A.status[b];
 
   T alpha_base = T(1);
   for (int base = 0; base < ls_max && !accepted; base += LS) {
@@ -3643,7 +3666,10 @@ ALTRO_DEV void forward2_body(const DevArrays<T>& A, const ProblemDesc* __restric
   } else {
     // the serial loop ran all trials; c_ holds the constraint values of the last trial whose rollout
     // succeeded (quirk Q6), and status_ is the outcome of the very last rollout
-    last_status = __shfl(st, grp * LS + (nlive - 1));
+    // (no trial at all -- line_search_max_iterations = 0, which the engine keeps away from the persistent kernels: no rollout
+    //  ran, and status_ stays what the backward pass left, ilqr.hpp:525)
+    if (nlive > 0) last_status = __shfl(st, grp * LS + (nlive - 1));
+    else if (!FUSED && valid) last_status = A.status[b];
     if (ok_g) t_replay = 31 - __clz(ok_g);
   }
   // ---- phase 2: copy the winner into Z_, evaluate the c_ it leaves behind; the knots are spread over
@@ -4165,7 +4191,7 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
       if (wave == 0) ALTRO_STAMP_ADD(16, st_cp);
     } else if (wave == 0) {
       // ---- B ----
-      backward_mfma_body<T, M, false, true>(A, o, 0, lane, blockIdx.x, nullptr, sKDf, fused_junk, fh, 0.0, 0.0, nullptr, b);
+      backward_mfma_body<T, M, false, true>(A, o, 0, lane, blockIdx.x, nullptr, sKDf, fused_junk, fh, 0.0, 0.0, nullptr, b, loops == 0);
       // (its own LDS writes of fh[4], fh[5]: program order)
     }
     // (the running cost J0 of the expansion step is summed by the auxiliary wave during the forward pass: aux_wave_run)

@@ -31,6 +31,12 @@ def _same(o, g, traj_tol=1e-9, only_solved=False):  # (bars pinned to profiles/r
     dict(max_iterations_total=7),
     dict(cost_tolerance=1e-6, gradient_tolerance=1e-4),
     dict(line_search_decrease_factor=3.0),
+    # (each of these changes the oracle's schedule: test_termination_gpu.py::test_new_option_variations_change_the_oracle_schedule)
+    dict(bp_reg_min=1e-6),
+    dict(bp_reg_increase_factor=2.5, bp_reg_initial=1e-3),
+    dict(line_search_lower_bound=0.2),
+    dict(line_search_upper_bound=1.0),  # (every instance runs into max_iterations_inner: the schedule is what is compared)
+    dict(line_search_upper_bound=1.05),
 ])
 def test_option_variations(P, oracle_make, hip_make, kw):
     o = P.batch_turn90(oracle_make, batch=12)
