@@ -68,6 +68,8 @@ struct Switches {
   OptInt loop_per_cu;              // ALTRO_HIP_LOOP_PER_CU: at most this many loop workgroups per CU
   int cand_front = 6;              // ALTRO_HIP_CAND_FRONT: line-search trials that own a candidate slot
   bool twin_debug = false;         // ALTRO_HIP_TWIN_DEBUG: mailbox dump of the twins
+  int twin_depth = kTwinDefaultDepth;  // ALTRO_HIP_TWIN_DEPTH=n: at most 2^n workers per rejection streak (1: one twin per primary)
+  int twin_misclaim = 0;           // ALTRO_HIP_TWIN_MISCLAIM=k (tests): every k-th claim assumes a regularisation one ulp off
   const char* sweep_log = nullptr; // ALTRO_HIP_SWEEP_LOG[=all]: timeline of the chains of sweeps
   bool loop_log = false;           // ALTRO_HIP_LOOP_LOG: phase log of the device-side loop
   bool force_valu_backward = false, force_coop_backward = false;  // ALTRO_HIP_BACKWARD = valu | coop: a fallback backward kernel (tests)
@@ -108,6 +110,8 @@ struct Switches {
     loop_per_cu = number("ALTRO_HIP_LOOP_PER_CU");
     if (const char* e = env("ALTRO_HIP_CAND_FRONT")) cand_front = std::max(0, std::min(kLineSearchLanes - 1, atoi(e)));
     twin_debug = env("ALTRO_HIP_TWIN_DEBUG") != nullptr;
+    if (const char* e = env("ALTRO_HIP_TWIN_DEPTH")) twin_depth = std::max(1, std::min(kTwinMaxDepth, atoi(e)));
+    if (const char* e = env("ALTRO_HIP_TWIN_MISCLAIM")) twin_misclaim = std::max(0, atoi(e));
     sweep_log = env("ALTRO_HIP_SWEEP_LOG");
     loop_log = env("ALTRO_HIP_LOOP_LOG") != nullptr;
     force_valu_backward = Is(env("ALTRO_HIP_BACKWARD"), "valu");
@@ -1011,7 +1015,8 @@ class Engine final : public EngineBase {
     if constexpr (kMfmaBackward) {
       if (sw_.twin && !sw_.fast_forward && !sw_.no_fused) {
         // (a solve that has split rejection streaks hands over at 3/2 of persist_at_, see Solve)
-        const int want = std::min(Bp_, ((persist_at_ * 3 / 2 + 8 + kBlock - 1) / kBlock) * kBlock);
+        // (at most 16384: the pool's scan packs a mailbox's position into 16 bits)
+        const int want = std::min({Bp_, 16384, ((persist_at_ * 3 / 2 + 8 + kBlock - 1) / kBlock) * kBlock});
         // (only widen while the 32-bit byte offsets hold)
         if (ExpBytes((size_t)(Bp_ + want)) < (size_t)0xffffffffu) twin_cap_ = want;
       }
@@ -1117,7 +1122,8 @@ class Engine final : public EngineBase {
     ALTRO_TRY(Alloc(&A_.pen, rows * bp));
     ALTRO_TRY(Alloc(&A_.cval, rows * bp));
     ALTRO_TRY(Alloc(&d_tmp_, bp));
-    if (twin_cap_ > 0) ALTRO_TRY(Alloc(&d_twin_box_, (size_t)twin_cap_ * (kTwWords + 1)));  // mailboxes, then the state words
+    // mailboxes of the workers (twin_cap_ primaries, then twin_cap_ pool workgroups), then their state words
+    if (twin_cap_ > 0) ALTRO_TRY(Alloc(&d_twin_box_, TwinBoxWords()));
     if (seg_total_ > 0) {
       // (kept out of A_: only the launches of Solve that take part in the scheme see them, SegArrays)
       ALTRO_TRY(Alloc(&seg_.end, bp));
@@ -1639,7 +1645,7 @@ class Engine final : public EngineBase {
         ALTRO_HIP_CHECK(hipMemsetAsync(A_.phase + (Bp_ - seg_total_ - twin_cap_), 0, (size_t)(seg_total_ + twin_cap_) * sizeof(int), stream_));
       if (!zero(d_counter_, counter_words))
         ALTRO_HIP_CHECK(hipMemsetAsync(d_counter_, 0, counter_words * sizeof(int), stream_));
-      if (twin_cap_ > 0) twin_box_clean_ = zero(d_twin_box_, (size_t)twin_cap_ * (kTwWords + 1) * 2);  // (else: cleared at the launch)
+      if (twin_cap_ > 0) twin_box_clean_ = zero(d_twin_box_, TwinBoxWords() * 2);  // (else: cleared at the launch)
       size_t words = 0;
       for (int j = 0; j < nz; ++j) words += z.n[j];
       const int gx = (B_ + kBlock - 1) / kBlock;
@@ -2011,10 +2017,14 @@ class Engine final : public EngineBase {
       TwinCtl tw{};
       if (twin_cap_ > 0 && !A.hist && !r.d.fast_forward_stalls) {
         if (!twin_box_clean_)  // (cleared by k_begin_solve otherwise: nothing touches the mailboxes before this launch)
-          hipMemsetAsync(d_twin_box_, 0, (size_t)twin_cap_ * (kTwWords + 1) * sizeof(unsigned long long), stream_);
-        tw = TwinCtl{d_twin_box_, d_twin_box_ + (size_t)twin_cap_ * kTwWords, ninst, twin_cap_, Bp_ - twin_cap_, kTwinLag, sw_.twin_debug ? 1 : 0};
+          hipMemsetAsync(d_twin_box_, 0, TwinBoxWords() * sizeof(unsigned long long), stream_);
+        // the pool: a workgroup per primary, or -- a small batch -- what the device has CUs left for, one shadow column each.
+        // (The variants that carry segments of the batched sweeps keep one twin per primary: their bookkeeping step is full.)
+        const int pool = std::min(twin_cap_, std::max(ninst, num_cus_ - ninst));
+        tw = TwinCtl{d_twin_box_, d_twin_box_ + (size_t)2 * twin_cap_ * kTwWords, ninst, twin_cap_, Bp_ - twin_cap_, kTwinLag, sw_.twin_debug ? 1 : 0,
+                     pool, any_split ? 1 : sw_.twin_depth, sw_.twin_misclaim};
       }
-      const dim3 g(ninst + (tw.base > 0 ? std::min(ninst, twin_cap_) : 0)), b3(kFwdWaves * kBlock), b4((kFwdWaves + 1) * kBlock);
+      const dim3 g(ninst + (tw.base > 0 ? tw.npool : 0)), b3(kFwdWaves * kBlock), b4((kFwdWaves + 1) * kBlock);
       timing_.twin_workgroups = tw.base > 0 ? (int)g.x - ninst : 0;  // twin workgroups of this launch
       // The variant of (circles, speculation, segments).  Columns of split streaks may be in the lists once a chain has
       // split: then the variants that verify / retire / cancel them in the loop's bookkeeping step (seg_on holds only
@@ -2116,49 +2126,52 @@ class Engine final : public EngineBase {
     timing_.sweeps = sweeps;
     return ALTRO_OK;
   }
+  size_t TwinBoxWords() const { return (size_t)2 * twin_cap_ * (kTwWords + 1); }
   // ALTRO_HIP_TWIN_DEBUG: the twins' mailboxes after the persistent launch, slot by slot (debug print only)
   altro_status DumpTwinMailboxes() {
-    std::vector<unsigned long long> box((size_t)twin_cap_ * kTwWords);
+    const int nbox = 2 * twin_cap_;
+    std::vector<unsigned long long> box((size_t)nbox * kTwWords);
     ALTRO_HIP_CHECK(CopySync(box.data(), d_twin_box_, box.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    int hist[4] = {0, 0, 0, 0}, why[8] = {0};
+    int hist[4] = {0, 0, 0, 0}, why[8] = {0}, by_depth[kTwinMaxDepth + 2] = {0};
     unsigned long long t0 = ~0ull;
     for (int s = 0; s < twin_cap_; ++s)
       if (box[(size_t)s * kTwWords + kTwStamp + kTsPStart]) t0 = std::min(t0, box[(size_t)s * kTwWords + kTwStamp + kTsPStart]);
+    auto us_of = [&](const unsigned long long* ts, int i) { return ts[i] ? (double)(long long)(ts[i] - t0) * 0.01 : -1.0; };
+    // one line per segment that a pool workgroup took: who it claimed from, its depth, its iterations and its timeline
     int shown = 0;
-    for (int s = 0; s < twin_cap_; ++s) {
+    double last_commit = 0, last_pend = 0, last_tstart = 0, last_leave = 0;
+    int s_commit = -1, s_pend = -1;
+    for (int s = 0; s < nbox; ++s) {
       const unsigned long long* w = &box[(size_t)s * kTwWords];
-      hist[w[kTwHand] & 3]++;
-      if ((w[kTwHand] & 3) == kTwOk && (shown++ % 8) == 0) {  // timelines of every eighth hand-over, us from the first workgroup's start
-        const unsigned long long* ts = w + kTwStamp;
-        auto us = [&](int i) { return ts[i] ? (double)(long long)(ts[i] - t0) * 0.01 : -1.0; };
-        fprintf(stderr, "  slot %3d  P: start %.0f snap %.0f (loop %llu) claim %.0f hand %.0f (loops %llu) | T: start %.0f go %.0f cloned %.0f first %.0f done %.0f (loops %llu) "
-                "verdict %.0f commit %.0f | claim start it %d\n", s, us(kTsPStart), us(kTsPSnap), ts[kTsPLoopsAtSnap], us(kTsPClaim), us(kTsPHand),
-                w[kTwHandLoops], us(kTsTStart), us(kTsTGo), us(kTsTCloned), us(kTsTFirst), us(kTsTDone), ts[kTsTLoops], us(kTsTVerdict), us(kTsTCommit),
-                (int)(w[kTwClaim] >> 32));
+      const unsigned long long* ts = w + kTwStamp;
+      auto us = [&](int i) { return us_of(ts, i); };
+      if (s >= twin_cap_ && w[kTwClaim] != 0) {
+        hist[w[kTwHand] & 3]++;
+        by_depth[std::min<unsigned long long>(w[kTwGen], kTwinMaxDepth + 1)]++;
+        const int limit = timing_.twin_claims <= 48 ? 1 : 8;  // (every segment of a small launch, every eighth otherwise)
+        if ((shown++ % limit) == 0)
+          fprintf(stderr, "  segment %4d depth %d inst %d from %d: it %d..%d hand %d | start %.0f go %.0f cloned %.0f first %.0f snap %.0f claimed %.0f "
+                  "done %.0f (loops %llu) verdict %.0f handed %.0f commit %.0f\n", s, (int)w[kTwGen], (int)w[kTwInst] - 1, (int)w[kTwPred] - 1,
+                  (int)(w[kTwClaim] >> 32), (int)w[kTwEnd], (int)(w[kTwHand] & 3), us(kTsTStart), us(kTsTGo), us(kTsTCloned), us(kTsTFirst), us(kTsPSnap),
+                  us(kTsPClaim), us(kTsTDone), ts[kTsTLoops], us(kTsTVerdict), us(kTsPHand), us(kTsTCommit));
       }
-      if (w[kTwClaim] != 0 && (w[kTwHand] & 3) == kTwRefused) {
+      if (w[kTwWhy] != 0) {
         why[w[kTwWhy] & 7]++;
         if (why[w[kTwWhy] & 7] <= 3)
-          fprintf(stderr, "  twin slot %d refused: why %d at it_inner %d (claim start %d, snapshot total %d), snapshots %llu\n", s, (int)(w[kTwWhy] & 7),
-                  (int)((w[kTwWhy] >> 8) & 0xffff), (int)((w[kTwWhy] >> 24) & 0xffff), (int)w[kTwClaimSnap], w[kTwSeq]);
+          fprintf(stderr, "  worker %d refused its successor: why %d at it_inner %d (claim start %d)\n", s, (int)(w[kTwWhy] & 7),
+                  (int)((w[kTwWhy] >> 8) & 0xffff), (int)((w[kTwWhy] >> 24) & 0xffff));
       }
+      if (us(kTsTCommit) > last_commit) { last_commit = us(kTsTCommit); s_commit = s; }
+      if (us(kTsPEnd) > last_pend) { last_pend = us(kTsPEnd); s_pend = s; }
+      last_leave = std::max(last_leave, us(kTsPHand));
+      last_tstart = std::max(last_tstart, us(kTsTStart));
     }
-    {
-      double last_commit = 0, last_pend = 0, last_tstart = 0;
-      int s_commit = -1, s_pend = -1;
-      for (int s = 0; s < twin_cap_; ++s) {
-        const unsigned long long* ts = &box[(size_t)s * kTwWords + kTwStamp];
-        auto us = [&](int i) { return ts[i] ? (double)(long long)(ts[i] - t0) * 0.01 : -1.0; };
-        if (us(kTsTCommit) > last_commit) { last_commit = us(kTsTCommit); s_commit = s; }
-        if (us(kTsPEnd) > last_pend) { last_pend = us(kTsPEnd); s_pend = s; }
-        last_tstart = std::max(last_tstart, us(kTsTStart));
-      }
-      fprintf(stderr, "twin timeline: last commit %.0f us (slot %d), last primary that finished by itself %.0f us (slot %d), last twin start %.0f us\n",
-              last_commit, s_commit, last_pend, s_pend, last_tstart);
-    }
-    fprintf(stderr, "twin mailboxes: launched %d claims %d handovers %d | hand word: open %d ok %d refused %d revoked %d | refusals of claims: "
-            "streak broke %d, passed %d, counters %d, rho %d, drho %d, break since snapshot %d\n", timing_.twin_workgroups,
-            timing_.twin_claims, timing_.twin_handovers, hist[0], hist[1], hist[2], hist[3], why[1], why[2], why[3], why[4], why[5], why[6]);
+    fprintf(stderr, "twin timeline: last commit %.0f us (mailbox %d), last primary that finished by itself %.0f us (slot %d), last hand-over %.0f us, "
+            "last pool start %.0f us\n", last_commit, s_commit, last_pend, s_pend, last_leave, last_tstart);
+    fprintf(stderr, "twin mailboxes: pool %d claims %d confirmed joints %d | segments by depth: 1: %d 2: %d 3: %d 4: %d 5: %d | hand word: open %d ok %d refused %d "
+            "revoked %d | refusals: streak broke %d, passed %d, counters %d, rho %d, drho %d, break since snapshot %d\n", (int)timing_.twin_workgroups,
+            (int)timing_.twin_claims, (int)timing_.twin_handovers, by_depth[1], by_depth[2], by_depth[3], by_depth[4], by_depth[5], hist[0], hist[1], hist[2],
+            hist[3], why[1], why[2], why[3], why[4], why[5], why[6]);
     return ALTRO_OK;
   }
   // profiler-event arithmetic of a solve (altro_options::profiler_enable), and the ALTRO_HIP_SWEEP_LOG timeline

@@ -3813,7 +3813,7 @@ enum SpecMode { kSpecOff = 0, kSpecWave = 1, kSpecFree = 3 };
 ALTRO_DEV constexpr bool spec_has_wave4(int spec) { return spec == kSpecWave || spec == kSpecFree; }
 
 // -------------------------------------------------------------------------------------------------
-// TWIN WORKGROUPS (round 5): the second half of a straggler's rejection streak, computed beside the first half.
+// TWIN WORKGROUPS: a straggler's rejection streak, computed as several segments side by side.
 //
 // What the tail of a batched solve is made of (profiles/r04_experiments.txt #5, scripts/probe_stragglers.py): ~2 % of
 // the instances reject every trial of every line search for exactly max_iterations_inner iterations.  A rejected
@@ -3822,55 +3822,96 @@ ALTRO_DEV constexpr bool spec_has_wave4(int spec) { return spec == kSpecWave || 
 // scalar rule away, PROVIDED every iteration in between is rejected as well.  The reference walks those iterations one
 // after the other on one core; here one straggler owns one CU for ~100 x 39 us while more than half of the CUs idle.
 //
-// So the launch carries, behind its `base` primary workgroups, one TWIN workgroup per slot.  A twin gets a CU when the
-// quick instances have left; it reads the snapshot its primary publishes at the end of every iteration of a streak
-// (counters, regularisation), CLAIMS the iterations from `start` on -- about half of what is left --, clones the
-// instance into a shadow column of the per-instance arrays (index col0 + slot: every array of DevArrays is allocated
-// that much wider), sets the entering state of iteration `start` there (counters advanced, regularisation stepped
-// through the increase / decrease rule, cost_prev = cost_cur) and runs the SAME code as every workgroup of this kernel
-// on that column: every iteration of the instance is still computed, with the inputs the sequential order would have
-// given it -- by two workgroups side by side instead of one.  The primary, arriving at `start`, compares what it holds
-// with what the twin assumed (bitwise: regularisation, counters, an unbroken streak since the snapshot): equal -> it hands
-// the instance over and leaves, and the twin, when its clone is finished, copies the column back over the instance's
-// own; different (an accepted step, an end of the inner solve, a Cholesky retry that moved the regularisation) -> it
-// refuses, goes on alone, and the twin drops its work.  Either way the result is the sequential one, bit for bit
-// (tests/test_fused_gpu.py::test_twin_workgroups_are_bit_identical); ALTRO_HIP_TWIN=0 launches no twins.
-//
-// Mailbox (global memory, one per slot, 64-bit words, relaxed agent-scope atomics = coherent across the XCDs' L2s; what
-// travels through ordinary memory -- the clone's source, the column copied back -- is ordered by ONE agent-scope release
-// of the primary per streak / hand-over and one acquire of the twin).  Every wait is bounded; a twin that gives up
-// revokes its claim with a compare-and-swap against the primary's hand-over, so an instance always has exactly one owner.
+// So the launch carries, behind its `base` primary workgroups, a POOL of workgroups, each with a shadow column of the
+// per-instance arrays (index col0 + t: every array of DevArrays is allocated that much wider) and a mailbox of its own.
+// A streak is a CHAIN OF SEGMENTS [s0, s1) [s1, s2) ... [sk, end), one workgroup (WORKER) per segment, under ONE rule:
+//   * a worker inside a streak -- the primary or a pool workgroup alike -- publishes where it is: once per streak the
+//     counters and the regularisation its streak began with, then one relaxed progress word per iteration; its segment's
+//     end and its successor stand in its mailbox;
+//   * an idle pool workgroup takes the published segment with the most iterations left and CLAIMS its second half
+//     [mid, seg_end): it becomes the publisher's successor and inherits the publisher's former successor; the publisher
+//     keeps [cur, mid) and may be claimed again, and so may the claimer (halves only; while both shares hold
+//     kTwinMinRemaining iterations; at most tw.depth splits along a line of claims, ALTRO_HIP_TWIN_DEPTH);
+//   * the claimer clones the publisher's column into its own, sets the entering state of iteration `mid` there (counters
+//     advanced, regularisation stepped through the increase / decrease rule, cost_prev = cost_cur) and runs the SAME code
+//     as every workgroup of this kernel on that column;
+//   * a worker arriving at its segment's end -- a JOINT -- compares what it holds with what its successor assumed (bitwise:
+//     regularisation, counters, an unbroken streak since the snapshot).  Equal: it hands over and leaves (a pool workgroup
+//     only after its own predecessor has confirmed IT, so a confirmed joint means that every joint before it holds).
+//     Different (an accepted step, an end of the inner solve, a Cholesky retry that moved the regularisation): it refuses,
+//     cancels every worker down the chain and goes on alone with the true state it holds;
+//   * the worker of the final segment runs the rest of the instance's solve and, once its predecessor has confirmed it,
+//     copies its column back over the instance's own.
+// Invariants:
+//   - every iteration is executed exactly once, on exactly the inputs the sequential order gives it: the result is the
+//     sequential one bit for bit (tests/test_fused_gpu.py::test_twin_workgroups_are_bit_identical,
+//     tests/test_tail_split_gpu.py); ALTRO_HIP_TWIN=0 launches no pool;
+//   - an instance's own column always has exactly one writer, and that writer is validated: the primary until it hands
+//     over, then the one worker whose whole line of joints is confirmed;
+//   - a claim its worker gives up on (a bounded wait that ran out) is revoked by compare-and-swap against the hand-over;
+//   - every poll is bounded and ends in the existing error paths, never in a hang;
+//   - mailbox words are relaxed agent-scope atomics (coherent across the XCDs' L2s); what travels through ordinary memory
+//     -- a clone's source, the column copied back -- is ordered by ONE agent-scope release per published streak or
+//     hand-over and one acquire per claim or verdict;
+//   - a cancelled worker has touched nothing but its own shadow column and its own mailbox.
+// What a worker pays per iteration of a streak: one relaxed store and one relaxed load whose value is used an iteration's
+// length later -- nothing is waited for (a load looked at where it is issued cost 2 us per iteration, 0.1 ms of config 2).
+// The variants with SEG = true (columns of streaks that the batched sweeps have split) run with depth 1: their
+// bookkeeping step already carries the segments' joints.
 // -------------------------------------------------------------------------------------------------
 struct TwinCtl {
-  unsigned long long* box;  // [cap][kTwWords], zeroed by the host before the launch
-  unsigned long long* state;  // [cap] one word per slot for the pool's scan: kTwsSnap | kTwsClosed | kTwsLocked
-  int base;                 // first twin block of the launch (0: no twins)
-  int cap;                  // slots that own a mailbox and a shadow column
+  unsigned long long* box;  // [2 * cap][kTwWords], zeroed by the host before the launch: primaries' (slot), then the pool's (cap + t)
+  unsigned long long* state;  // [2 * cap] one word per mailbox for the pool's scan (kTws*)
+  int base;                 // first pool block of the launch (0: no twins)
+  int cap;                  // primaries that own a mailbox; pool workgroups that own a mailbox and a shadow column
   int col0;                 // first shadow column
-  int lag;                  // iterations the primary is expected to advance while a twin clones and stages (kTwinLag)
+  int lag;                  // iterations a publisher is expected to advance while a claimer clones and stages (kTwinLag)
   int debug;                // stamp the mailbox (ALTRO_HIP_TWIN_DEBUG)
+  int npool;                // pool workgroups of this launch (<= cap)
+  int depth;                // a streak is split at most `depth` times along any line of claims: <= 2^depth workers (ALTRO_HIP_TWIN_DEPTH)
+  int misclaim;             // test only (ALTRO_HIP_TWIN_MISCLAIM=k): every k-th claim assumes a regularisation one ulp off
 };
 enum TwinStamp { kTsPStart = 0, kTsPSnap = 1, kTsPClaim = 2, kTsPHand = 3, kTsPLoopsAtSnap = 4, kTsTStart = 5, kTsTGo = 6, kTsTCloned = 7,
                  kTsTFirst = 8, kTsTDone = 9, kTsTVerdict = 10, kTsTCommit = 11, kTsTLoops = 12, kTsPEnd = 13 };
+// One mailbox per WORKER (a primary or a pool workgroup).  Words 0 - 6 are what the worker shows as the publisher of its
+// segment, words 7 - 14 describe the joint at which it ENTERS the chain (pool workgroups only: written by the worker when
+// it claims, answered by its predecessor).
 enum TwinWord {
-  kTwSeq = 0,        // version of the newest snapshot (0: none yet)
-  kTwSnap = 1,       // two snapshot buffers of 4 words: (it_inner << 32 | it_total), rho, drho, primary's loop count
-  kTwClaim = 9,      // (start_it_inner << 32 | start_it_total), written last by the twin
-  kTwClaimRho = 10,  // regularisation the twin assumes to enter iteration `start`
-  kTwClaimDrho = 11,
-  kTwClaimSnap = 12, // it_total of the snapshot the claim was derived from
-  kTwHand = 13,      // 0 open, kTwOk / kTwRefused (primary), kTwRevoked (twin): set once, by compare-and-swap
-  kTwHandLoops = 14, // the primary's loop count at the hand-over
-  kTwWhy = 15,       // diagnostics (ALTRO_HIP_TWIN_DEBUG): why a claim was refused / what the twin did last
-  kTwStamp = 16,     // diagnostics: 100 MHz wall-clock stamps of the two workgroups (TwinStamp), written when tw.debug is set
-  kTwWords = 32
+  kTwSeq = 0,        // version of the streak's snapshot (0: none on display)
+  kTwSnap = 1,       // two snapshot buffers of 3 words, written once per streak: (it_inner << 32 | it_total), rho, drho
+  kTwProg = 7,       // (it_inner << 32 | it_total) entering the publisher's next iteration: one relaxed store per iteration
+  kTwSucc = 8,       // mailbox of the successor + 1 (bits 0 - 15; 0: this is the final segment) | times this worker's line of claims
+                     // has been split << 16 (the primary starts at 0) | kTwFrozen; changed by compare-and-swap only, so a worker
+                     // reads its successor and whether it can be claimed again in one word
+  kTwEnd = 9,        // it_inner at which this segment ends (0: at the iteration caps), written by whoever holds the lock
+  kTwGen = 10,       // diagnostics: the splits of the line of claims that made this worker (its depth in the dump)
+  kTwInst = 11,      // the instance's own column + 1
+  kTwClaim = 12,     // (start_it_inner << 32 | start_it_total) of this worker's segment
+  kTwClaimRho = 13,  // regularisation the worker assumes to enter iteration `start`
+  kTwClaimDrho = 14,
+  kTwClaimSnap = 15, // it_total of the snapshot the claim was derived from
+  kTwHand = 16,      // 0 open, kTwOk / kTwRefused (predecessor), kTwRevoked (the worker): set once, by compare-and-swap
+  kTwHandLoops = 17, // iterations the workers before this one ran, at the hand-over
+  kTwWhy = 18,       // diagnostics (ALTRO_HIP_TWIN_DEBUG): why the claim of this worker's successor was refused
+  kTwPred = 19,      // diagnostics: mailbox of the publisher this worker claimed from + 1
+  kTwStamp = 20,     // diagnostics: 100 MHz wall-clock stamps of the worker (TwinStamp), written when tw.debug is set
+  kTwWords = 40
 };
 constexpr unsigned long long kTwOk = 1, kTwRefused = 2, kTwRevoked = 3;
-// state word of a slot (contiguous array: a wavefront of the pool looks at 64 slots with one coalesced load):
-//   kTwsSnap    the primary has a snapshot of a running streak on display (cleared when the streak breaks)
-//   kTwsClosed  the primary has finished, refused or handed over: nothing more to come from this slot
-//   kTwsLocked  a twin has taken the slot (compare-and-swap kTwsSnap -> kTwsSnap | kTwsLocked), or has found it not worth it
-constexpr unsigned long long kTwsSnap = 1, kTwsClosed = 2, kTwsLocked = 4;
+constexpr unsigned long long kTwSuccId = 0xffffull;  // kTwSucc: the successor's mailbox + 1
+constexpr unsigned long long kTwFrozen = 1ull << 32;  // kTwSucc: the publisher is at a joint or has left -- no further claim
+// state word of a mailbox (contiguous array: a wavefront of the pool looks at 64 of them with one coalesced load):
+//   kTwsSnap    the worker has the snapshot of a running streak on display (cleared when the streak breaks)
+//   kTwsClosed  the worker has finished, refused or handed over: nothing more to come from it
+//   kTwsLocked  a pool workgroup is claiming from this worker (compare-and-swap; released behind the claim)
+//   kTwsFull    the worker's line of claims has reached tw.depth: not claimable any more
+//   kTwsBusy    (pool workgroups) the workgroup has claimed a segment; an idle one is nobody's prospect
+constexpr unsigned long long kTwsSnap = 1, kTwsClosed = 2, kTwsLocked = 4, kTwsFull = 8, kTwsBusy = 16;
+#ifndef ALTRO_TWIN_DEPTH
+#define ALTRO_TWIN_DEPTH 3
+#endif
+constexpr int kTwinDefaultDepth = ALTRO_TWIN_DEPTH;  // workers per streak <= 2^depth (ALTRO_HIP_TWIN_DEPTH)
+constexpr int kTwinMaxDepth = 5;        // (the walk that cancels a chain is bounded by 2^kTwinMaxDepth workers)
 constexpr int kTwinMinRemaining = 12;   // iterations left in a streak below which a twin is not worth its start-up
 // iterations of the primary's share that pay for the twin's start-up (claim seen, clone, one unspeculated iteration): the twin
 // takes the iterations from snapshot + (R + lag) / 2 + 1 on.  Round 6 (mailbox stamps of config 2, ALTRO_HIP_TWIN_DEBUG): with 3
@@ -3899,6 +3940,30 @@ ALTRO_DEV bool tw_cas(unsigned long long* p, unsigned long long expect, unsigned
 }
 ALTRO_DEV unsigned long long tw_bits(double x) { return (unsigned long long)__double_as_longlong(x); }
 ALTRO_DEV double tw_dbl(unsigned long long x) { return __longlong_as_double((long long)x); }
+// iterations left in the segment of a publisher that enters iteration `prog` next: up to its successor's first one, or --
+// the final segment -- until a cap ends the streak at the latest (ilqr.hpp:600-611)
+ALTRO_DEV int tw_remaining(const DevOpts& o, unsigned long long prog, int end_inner) {
+  const int it_in = (int)(prog >> 32), it_tot = (int)(prog & 0xffffffffull);
+  if (end_inner > 0) return end_inner - it_in;
+  const int r1 = o.max_iterations_inner - it_in, r2 = o.max_iterations_total - it_tot;
+  return r1 < r2 ? r1 : r2;
+}
+// iterations the publisher keeps of the R it has left (halves, plus what pays for the claimer's start-up: kTwinLag); a
+// segment is worth splitting while both shares hold kTwinMinRemaining iterations
+ALTRO_DEV int tw_keep(int R, int lag) { return (R + lag) / 2 + 1; }
+ALTRO_DEV bool tw_claimable(int R, int lag) { return R >= 2 * kTwinMinRemaining && R - tw_keep(R, lag) >= kTwinMinRemaining; }
+// A worker that refuses its successor, gives its own claim up or finishes the instance with a successor waiting: no further
+// claim on it (kTwFrozen), and every worker down the chain is told that its work is void.  Bounded; thread 0 only.
+ALTRO_DEV void tw_cancel_chain(const TwinCtl& tw, unsigned long long* box) {
+  unsigned long long nx = __hip_atomic_fetch_or(box + kTwSucc, kTwFrozen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kTwSuccId;
+  for (int guard = 0; nx != 0 && nx <= (unsigned long long)(2 * tw.cap) && guard < (2 << kTwinMaxDepth); ++guard) {
+    const int id = (int)nx - 1;
+    unsigned long long* sb = tw.box + (size_t)id * kTwWords;
+    nx = __hip_atomic_fetch_or(sb + kTwSucc, kTwFrozen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kTwSuccId;
+    tw_cas(sb + kTwHand, 0ull, kTwRefused);
+    __hip_atomic_fetch_or(tw.state + id, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
 
 template <class T, class M, bool CIRC, int SPEC, bool SEG = false>
 __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) * kBlock) void k_sweep_fused(
@@ -3919,7 +3984,7 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   int slot = is_twin ? -1 : (int)blockIdx.x;
   int b_real = is_twin ? -1 : instance_of_slot(A, slot, 0);
   if (!is_twin && b_real < 0) return;  // uniform over the workgroup
-  if (is_twin && (tslot >= tw.cap || !persistent)) return;
+  if (is_twin && (tslot >= tw.npool || tslot >= tw.cap || !persistent)) return;
   unsigned long long* box = (!is_twin && tw.base > 0 && slot < tw.cap && persistent) ? tw.box + (size_t)slot * kTwWords : nullptr;
   int b = b_real;  // (a twin switches to its shadow column once it has claimed its share of the iterations)
   const int N = A.N;
@@ -3963,14 +4028,16 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   int spec_iters = 0;
 #endif
   // ---- twin workgroups (TwinCtl): the primary's bookkeeping, the twin's claim and clone ----
-  int tw_streak = 0;               // primary: consecutive rejected iterations during which the inner solve went on
-  int tw_break_total = -1;         // primary: it_total left by the last iteration that was NOT one of those
-  unsigned long long tw_ver = 0;   // primary, thread 0: version of the newest snapshot
-  bool tw_closed = false;          // primary, thread 0: the mailbox is out of use
-  bool tw_shown = false;           // primary, thread 0: the slot's state word says "snapshot on display"
-  unsigned long long tw_claim = 0, tw_claim_rho = 0, tw_claim_drho = 0;  // primary, thread 0: the twin's claim, once seen
-  int tw_claim_snap = 0;
-  int tw_loops0 = 0;               // twin: iterations the primary ran before the hand-over
+  int tw_streak = 0;               // consecutive rejected iterations during which the inner solve went on
+  int tw_break_total = -1;         // it_total left by the last iteration that was NOT one of those
+  unsigned long long tw_ver = 0;   // thread 0: version of the newest snapshot
+  bool tw_closed = false;          // thread 0: nothing more is published, no successor is waited for
+  bool tw_shown = false;           // thread 0: the state word says "snapshot on display"
+  unsigned long long tw_succ = 0, tw_claim = 0;  // thread 0: the mailbox's successor word and the iteration the successor starts at, once seen
+  unsigned long long tw_peek = 0;  // thread 0: the mailbox's successor word, requested at the top of the iteration
+  bool tw_full = false;            // thread 0: this worker's line of claims has reached tw.depth -- nothing more to show or to look for
+  bool tw_confirmed = false;       // pool workgroup, thread 0: the predecessor has confirmed the state this worker entered with
+  int tw_loops0 = 0;               // pool workgroup: iterations the workers before it ran before the hand-over
   auto stamp = [&](int which, long long value = -1) __attribute__((always_inline)) {
     if (box && tw.debug) tw_store(box + kTwStamp + which, (unsigned long long)(value >= 0 ? value : wall_clock64()));
   };
@@ -3994,94 +4061,124 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     }
   };
   if (is_twin) {
-    // ---- find work: a slot whose primary has published a streak and that no other twin serves ----
+    // ---- find work: the published segment with the most iterations left (late stragglers first, once CUs free up) ----
+    const int self = tw.cap + tslot;
     if (wave == 0) {
       const int cnt_slots = A.act_count ? *A.act_count : A.act_count_const;
       const int nsl = cnt_slots < tw.cap ? cnt_slots : tw.cap;
+      const int nall = nsl + tw.npool;  // the primaries' mailboxes, then the pool's
       int chosen = -1;
       for (int tries = 0; tries < kTwinIdlePolls && chosen < 0; ++tries) {
-        int waiting = 0;  // primaries that may still offer something: alive (or not yet dispatched) and unclaimed
-        for (int s0 = 0; s0 < nsl && chosen < 0; s0 += kBlock) {
-          const int sc = s0 + lane;
-          bool open = false, cand = false;
-          if (sc < nsl) {
-            const unsigned long long st = tw_load(tw.state + sc);
-            open = (st & (kTwsClosed | kTwsLocked)) == 0;
-            cand = st == kTwsSnap;
+        int waiting = 0;  // workers that may still offer something: alive (or not yet dispatched), not full, long enough
+        int key = 0;      // (iterations left << 16 | 0xffff - position in the scan) of this lane's best candidate
+        for (int v0 = 0; v0 < nall; v0 += kBlock) {
+          const int v = v0 + lane;
+          bool open = false;
+          if (v < nall) {
+            const int id = v < nsl ? v : tw.cap + (v - nsl);
+            const unsigned long long st = id == self ? kTwsClosed : tw_load(tw.state + id);
+            open = (st & (kTwsClosed | kTwsFull)) == 0 && (v < nsl || (st & kTwsBusy) != 0);
+            if (open && (st & kTwsSnap) != 0) {
+              const unsigned long long* bx = tw.box + (size_t)id * kTwWords;
+              const int R = tw_remaining(o, tw_load(bx + kTwProg), (int)tw_load(bx + kTwEnd));
+              open = tw_claimable(R, tw.lag);
+              if (open && (st & kTwsLocked) == 0) {
+                const int k2 = ((R < 0x7fff ? R : 0x7fff) << 16) | (0xffff - (v & 0xffff));
+                key = k2 > key ? k2 : key;
+              }
+            }
           }
           waiting += __popcll(__ballot(open));
-          unsigned long long m = __ballot(cand);
-          while (m != 0 && chosen < 0) {
-            const int s2 = s0 + (__ffsll((long long)m) - 1);
-            m &= m - 1;
-            unsigned long long* bx = tw.box + (size_t)s2 * kTwWords;
-            int got = 0;  // 0: lost the lock, 1: claimed, 2: locked but nothing to claim (kept locked), 3: snapshot gone (unlocked)
-            if (lane == 0 && tw_cas(tw.state + s2, kTwsSnap, kTwsSnap | kTwsLocked)) {
-              got = 3;
-              unsigned long long cnt = 0, rb = 0, db = 0;
-              bool have = false;
-              for (int r = 0; r < 8 && !have; ++r) {
-                const unsigned long long ver = tw_load(bx + kTwSeq);
-                if (ver == 0) break;  // the streak broke meanwhile
-                const unsigned long long* buf = bx + kTwSnap + 4 * (ver & 1);
-                cnt = tw_load(buf);
-                rb = tw_load(buf + 1);
-                db = tw_load(buf + 2);
-                const unsigned long long ver2 = tw_load(bx + kTwSeq);
-                have = ver2 == ver || ver2 == ver + 1;  // (buffer ver & 1 is only rewritten by version ver + 2)
-              }
-              if (have) {
-                const int it_in = (int)(cnt >> 32), it_tot = (int)(cnt & 0xffffffffull);
-                // iterations until a cap ends the streak at the latest (ilqr.hpp:600-611)
-                const int r1 = o.max_iterations_inner - it_in, r2 = o.max_iterations_total - it_tot;
-                const int R = r1 < r2 ? r1 : r2;
-                if (R < kTwinMinRemaining) {
-                  got = 2;  // not worth a twin's start-up: stays locked, nobody else tries
-                } else {
-                  const int ahead = (R + tw.lag) / 2 + 1;  // iterations the primary keeps, counted from the snapshot
-                  // the regularisation entering iteration `start`: every iteration in between runs its backward pass
-                  // (DecreaseRegularization, ilqr.hpp:440) and rejects its line search (IncreaseRegularization, :550)
-                  double rho = tw_dbl(rb), drho = tw_dbl(db);
-                  for (int jj = 0; jj < ahead; ++jj) {
-                    decrease_reg(o, &rho, &drho);
-                    increase_reg(o, &rho, &drho);
-                  }
-                  tw_store(bx + kTwClaimRho, tw_bits(rho));
-                  tw_store(bx + kTwClaimDrho, tw_bits(drho));
-                  tw_store(bx + kTwClaimSnap, (unsigned long long)(unsigned)it_tot);
-                  tw_order();
-                  tw_store(bx + kTwClaim, ((unsigned long long)(unsigned)(it_in + ahead) << 32) | (unsigned long long)(unsigned)(it_tot + ahead));
-                  ff[8] = (double)(it_in + ahead);
-                  ff[9] = (double)(it_tot + ahead);
+        }
+        for (int d = 32; d > 0; d >>= 1) {
+          const int other = __shfl_xor(key, d);
+          key = other > key ? other : key;
+        }
+        int got = 0;
+        if (key != 0 && lane == 0) {
+          const int v = 0xffff - (key & 0xffff);
+          const int id = v < nsl ? v : tw.cap + (v - nsl);
+          unsigned long long* bx = tw.box + (size_t)id * kTwWords;
+          const unsigned long long st0 = kTwsSnap | (v < nsl ? 0ull : kTwsBusy);
+          if (tw_cas(tw.state + id, st0, st0 | kTwsLocked)) {
+            unsigned long long more = 0;  // bits for the publisher's state word
+            const unsigned long long ver = tw_load(bx + kTwSeq);
+            if (ver != 0) {
+              const unsigned long long* buf = bx + kTwSnap + 3 * (ver & 1);
+              const unsigned long long c0 = tw_load(buf), rb = tw_load(buf + 1), db = tw_load(buf + 2);
+              const unsigned long long pr = tw_load(bx + kTwProg), so = tw_load(bx + kTwSucc), inst = tw_load(bx + kTwInst);
+              const int end_in = (int)tw_load(bx + kTwEnd), gen = (int)((so >> 16) & 0xffffull);
+              const bool stable = tw_load(bx + kTwSeq) == ver;  // (the streak whose snapshot this is is still on)
+              const int in0 = (int)(c0 >> 32), tot0 = (int)(c0 & 0xffffffffull), in1 = (int)(pr >> 32), tot1 = (int)(pr & 0xffffffffull);
+              const int R = tw_remaining(o, pr, end_in);
+              if (gen >= tw.depth) more = kTwsFull;
+              if (stable && more == 0 && (so & kTwFrozen) == 0 && inst != 0 && in1 >= in0 && in1 - in0 == tot1 - tot0 && tw_claimable(R, tw.lag)) {
+                const int ahead = tw_keep(R, tw.lag);  // iterations the publisher keeps, counted from where it is
+                // the regularisation entering iteration `start`: every iteration since the snapshot runs its backward pass
+                // (DecreaseRegularization, ilqr.hpp:440) and rejects its line search (IncreaseRegularization, :550)
+                double rho = tw_dbl(rb), drho = tw_dbl(db);
+                for (int jj = 0; jj < in1 - in0 + ahead; ++jj) {
+                  decrease_reg(o, &rho, &drho);
+                  increase_reg(o, &rho, &drho);
+                }
+                const int nth = sweeps_out ? atomicAdd(sweeps_out + 5, 1) + 1 : 1;  // claims of this launch, at every level
+                if (tw.misclaim > 0 && nth % tw.misclaim == 0) rho = tw_dbl(tw_bits(rho) ^ 1ull);  // (test only: the joint must refuse)
+                const bool full = gen + 1 >= tw.depth;
+                unsigned long long* mine = tw.box + (size_t)self * kTwWords;
+                tw_store(mine + kTwClaimRho, tw_bits(rho));
+                tw_store(mine + kTwClaimDrho, tw_bits(drho));
+                tw_store(mine + kTwClaimSnap, (unsigned long long)(unsigned)tot0);
+                tw_store(mine + kTwClaim, ((unsigned long long)(unsigned)(in1 + ahead) << 32) | (unsigned long long)(unsigned)(tot1 + ahead));
+                tw_store(mine + kTwInst, inst);
+                tw_store(mine + kTwGen, (unsigned long long)(unsigned)(gen + 1));
+                tw_store(mine + kTwEnd, (unsigned long long)(unsigned)end_in);  // (the publisher's former end and successor: inherited)
+                tw_store(mine + kTwSucc, (so & kTwSuccId) | ((unsigned long long)(unsigned)(gen + 1) << 16));
+                tw_store(mine + kTwPred, (unsigned long long)(unsigned)(id + 1));
+                tw_store(tw.state + self, kTwsBusy | (full ? kTwsFull : 0ull));
+                tw_store(bx + kTwEnd, (unsigned long long)(unsigned)(in1 + ahead));
+                tw_order();
+                // the claim: the publisher looks at this word once per iteration; lost against a publisher that has reached a joint
+                if (tw_cas(bx + kTwSucc, so, (unsigned long long)(unsigned)(self + 1) | ((unsigned long long)(unsigned)(gen + 1) << 16))) {
+                  ff[8] = (double)(in1 + ahead);
+                  ff[9] = (double)(tot1 + ahead);
                   ff[10] = rho;
                   ff[11] = drho;
-                  if (sweeps_out) atomicAdd(sweeps_out + 5, 1);  // claims of this launch
-                  got = 1;
+                  ff[14] = (double)((int)inst - 1);
+                  if (full) more = kTwsFull;
+                  got = id + 1;
+                } else {
+                  tw_store(tw.state + self, 0ull);
+                  if (sweeps_out) atomicSub(sweeps_out + 5, 1);
                 }
               }
-              if (got == 3) __hip_atomic_fetch_and(tw.state + s2, ~kTwsLocked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            got = __shfl(got, 0);
-            if (got == 1) chosen = s2;
+            if (more != 0) __hip_atomic_fetch_or(tw.state + id, more, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_and(tw.state + id, ~kTwsLocked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
+        got = __shfl(got, 0);
+        if (got > 0) chosen = got - 1;
         if (chosen < 0) {
-          if (waiting == 0) break;  // every primary has finished or has its twin
-          __builtin_amdgcn_s_sleep(64);
+          if (key == 0 && waiting == 0) break;  // nobody can publish a segment worth splitting any more
+          // (>= 25 us between two looks: r06_experiments.txt #4 measured what 300 fast pollers cost the workers)
+          for (int z = 0; z < (key == 0 ? 8 : 1); ++z) __builtin_amdgcn_s_sleep(127);
         }
       }
       if (lane == 0) {
         ff[15] = (double)chosen;
-        // (what the primary's workgroup stored before it published -- the trajectory of its last accepted step, the
-        //  multipliers -- may sit in another XCD's L2: its release is matched by this acquire)
+        // (what the publisher's workgroup stored before it published -- the trajectory of its last accepted step, the
+        //  multipliers, or its clone of them -- may sit in another XCD's L2: its release is matched by this acquire)
         if (chosen >= 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       }
     }
     __syncthreads();
-    slot = (int)ff[15];
-    if (slot < 0) return;
-    box = tw.box + (size_t)slot * kTwWords;
-    b_real = instance_of_slot(A, slot, 0);
+    const int src_id = (int)ff[15];
+    if (src_id < 0) return;
+    slot = self;
+    box = tw.box + (size_t)self * kTwWords;
+    b_real = (int)ff[14];
+    // (the column the publisher works on: the instance's own, or a pool workgroup's shadow column)
+    const int b_src = src_id < tw.cap ? instance_of_slot(A, src_id, 0) : tw.col0 + (src_id - tw.cap);
     if (tid == 0) {
       stamp(kTsTStart, tstart_clock);
       stamp(kTsTGo);
@@ -4092,15 +4189,15 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
       using R_ = Rec<T, M::n, M::m>;
       for (int i = tid; i < (N + 1) * R_::nP; i += kThreads) {
         const int k = i / R_::nP, e = i - k * R_::nP;
-        A.X[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::nP + e] = A.X[((size_t)(unsigned)k * Bp + (unsigned)b_real) * R_::nP + e];
+        A.X[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::nP + e] = A.X[((size_t)(unsigned)k * Bp + (unsigned)b_src) * R_::nP + e];
       }
       for (int i = tid; i < N * R_::mP; i += kThreads) {
         const int k = i / R_::mP, e = i - k * R_::mP;
-        A.U[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::mP + e] = A.U[((size_t)(unsigned)k * Bp + (unsigned)b_real) * R_::mP + e];
+        A.U[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::mP + e] = A.U[((size_t)(unsigned)k * Bp + (unsigned)b_src) * R_::mP + e];
       }
-      if (tid < R_::nP) A.x0[(size_t)bT * R_::nP + tid] = A.x0[(size_t)b_real * R_::nP + tid];
+      if (tid < R_::nP) A.x0[(size_t)bT * R_::nP + tid] = A.x0[(size_t)b_src * R_::nP + tid];
       auto column = [&](T* arr, int rows) __attribute__((always_inline)) {
-        for (int r = tid; r < rows; r += kThreads) arr[(unsigned)r * Bp + (unsigned)bT] = arr[(unsigned)r * Bp + (unsigned)b_real];
+        for (int r = tid; r < rows; r += kThreads) arr[(unsigned)r * Bp + (unsigned)bT] = arr[(unsigned)r * Bp + (unsigned)b_src];
       };
       column(A.costs, N + 1);
       column(A.lam, pd->total_rows);
@@ -4108,12 +4205,12 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
       column(A.cval, pd->total_rows);
       column(const_cast<T*>(A.ipool), pd->nslots);
       if (tid == 0) {
-        // per-instance solver state: as the primary left it ...
-        const double c0 = A.dV0[b_real], c1 = A.dV1[b_real], c2 = A.J0[b_real], c3 = A.initial_cost[b_real], c4 = A.cost_cur[b_real],
-                     c5 = A.dJ[b_real], c6 = A.grad[b_real], c7 = A.viol[b_real], c8 = A.penmax[b_real], c9 = A.alpha[b_real],
-                     c10 = A.z[b_real], c11 = A.reg_log[b_real];
-        const int i0 = A.status[b_real], i1 = A.status_al[b_real], i2 = A.it_outer[b_real], i3 = A.phase[b_real],
-                  i4 = A.need_init_cost[b_real];
+        // per-instance solver state: as the publisher left it ...
+        const double c0 = A.dV0[b_src], c1 = A.dV1[b_src], c2 = A.J0[b_src], c3 = A.initial_cost[b_src], c4 = A.cost_cur[b_src],
+                     c5 = A.dJ[b_src], c6 = A.grad[b_src], c7 = A.viol[b_src], c8 = A.penmax[b_src], c9 = A.alpha[b_src],
+                     c10 = A.z[b_src], c11 = A.reg_log[b_src];
+        const int i0 = A.status[b_src], i1 = A.status_al[b_src], i2 = A.it_outer[b_src], i3 = A.phase[b_src],
+                  i4 = A.need_init_cost[b_src];
         A.dV0[bT] = c0; A.dV1[bT] = c1; A.J0[bT] = c2; A.initial_cost[bT] = c3; A.cost_cur[bT] = c4;
         A.dJ[bT] = c5; A.grad[bT] = c6; A.viol[bT] = c7; A.penmax[bT] = c8; A.alpha[bT] = c9; A.z[bT] = c10; A.reg_log[bT] = c11;
         A.status[bT] = i0; A.status_al[bT] = i1; A.it_outer[bT] = i2; A.phase[bT] = i3; A.need_init_cost[bT] = i4;
@@ -4135,7 +4232,10 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     b = bT;
     __syncthreads();
     if (tid == 0) stamp(kTsTCloned);
-    if (tid == 0) ff[12] = tw_load(box + kTwHand) == 0 ? 1.0 : 0.0;  // (refused already -- the primary broke its streak or finished)
+    if (tid == 0) {  // (refused already -- the publisher broke its streak or finished)
+      ff[12] = tw_load(box + kTwHand) == 0 ? 1.0 : 0.0;
+      if (ff[12] == 0.0) __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __syncthreads();
     if (ff[12] == 0.0) return;
   }
@@ -4145,6 +4245,10 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   }
   for (;;) {
     const long long st_it = ALTRO_STAMP_T0();
+    // (a claim on this worker's segment: the word is requested here and looked at in the bookkeeping step behind the forward
+    //  pass, so its round trip through the memory side runs beside the iteration -- a claim is seen one iteration late at the
+    //  worst, and it names an iteration at least kTwinMinRemaining ahead)
+    if (box && tid == 0 && !tw_closed && !tw_full && (is_twin || tw_shown)) tw_peek = tw_load(box + kTwSucc);
     // ---- S: X, U, lambda, rho, parameters -> LDS (all threads).  Only once: phases 2 and 3 of the
     //      forward pass keep the LDS copies current from then on ----
     if (loops == 0) {
@@ -4321,81 +4425,87 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
       seg_leave = ff[12] != 0.0;
       if (seg_leave) break;
     }
-    // ---- twin workgroups (TwinCtl).  Primary: publish the state this iteration leaves while a streak is on, answer a
-    //      claim when the iteration it names is reached.  Twin: a look at the verdict now and then. ----
+    // ---- twin workgroups (TwinCtl).  Every worker: show where it is while a streak is on, see a claim on the rest of its
+    //      segment, answer its successor at the joint.  Pool workgroups: a look at their own verdict now and then. ----
     if (box) {
-      if (!is_twin) {
-        const bool rc = ff[0] != 0.0 && ff[3] == 0.0;  // every trial rejected, and the inner solve goes on
-        tw_streak = rc ? tw_streak + 1 : 0;
-        if (!rc) tw_break_total = (int)ff[7];
-        if (tid == 0) {
-          double act = 0.0;
-          if (!tw_closed && (tw_streak >= 2 || tw_ver != 0)) {
-            const int it_in = (int)ff[6], it_tot = (int)ff[7];  // the counters entering the next iteration
-            if (tw_claim == 0) {
-              // (a column whose streak the batched sweeps have split into segments ends at its segment's end: no twin)
-              if (rc && tw_streak >= 2 && (!SEG || !A.seg_end || A.seg_next[b] < 0)) {
-                ++tw_ver;
-                unsigned long long* buf = box + kTwSnap + 4 * (tw_ver & 1);
-                tw_store(buf, ((unsigned long long)(unsigned)it_in << 32) | (unsigned long long)(unsigned)it_tot);
-                tw_store(buf + 1, tw_bits(ff[1]));
-                tw_store(buf + 2, tw_bits(ff[2]));
-                tw_store(buf + 3, (unsigned long long)(unsigned)loops);
-                // once per streak: whatever the last accepted step and the first rejected iteration stored (trajectory,
-                // multipliers, cost_prev = cost_cur) leaves this XCD's L2 before a twin is told that it may read it
-                if (tw_streak == 2) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                tw_order();
-                tw_store(box + kTwSeq, tw_ver);
-                if (!tw_shown) {
-                  tw_order();
-                  __hip_atomic_fetch_or(tw.state + slot, kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  tw_shown = true;
-                }
-                if (tw_ver == 1) {
-                  stamp(kTsPSnap);
-                  stamp(kTsPLoopsAtSnap, loops);
-                }
-              }
-              // (a streak that broke: the snapshot on display describes a state that no longer exists -- a late twin would
-              //  claim on it and be refused; hide it until the next streak publishes)
-              if (!rc && tw_shown) {
-                __hip_atomic_fetch_and(tw.state + slot, ~kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                tw_store(box + kTwSeq, 0ull);
-                tw_shown = false;
-              }
-              tw_claim = tw_load(box + kTwClaim);
-              if (tw_claim != 0) stamp(kTsPClaim);
-              if (tw_claim != 0) {  // (its other words were stored before it; from now on nothing is published or polled)
-                tw_claim_rho = tw_load(box + kTwClaimRho);
-                tw_claim_drho = tw_load(box + kTwClaimDrho);
-                tw_claim_snap = (int)tw_load(box + kTwClaimSnap);
-              }
-            }
-            if (tw_claim != 0) {
-              const int s_in = (int)(tw_claim >> 32), s_tot = (int)(tw_claim & 0xffffffffull);
-              bool refuse = !rc || it_in > s_in;
-              int why = !rc ? 1 : (it_in > s_in ? 2 : 0);
-              if (!refuse && it_in == s_in) {
-                // the twin's assumptions about the state entering this iteration, bit for bit -- and no iteration since
-                // its snapshot that was anything but a rejected one
-                const bool same = it_tot == s_tot && tw_bits(ff[1]) == tw_claim_rho && tw_bits(ff[2]) == tw_claim_drho &&
-                                  tw_break_total < tw_claim_snap;
-                if (same) act = 2.0; else refuse = true;
-                why = it_tot != s_tot ? 3 : (tw_bits(ff[1]) != tw_claim_rho ? 4 : (tw_bits(ff[2]) != tw_claim_drho ? 5 : 6));
-              }
-              if (refuse) {
-                tw_store(box + kTwWhy, (unsigned long long)why | ((unsigned long long)(unsigned)it_in << 8) | ((unsigned long long)(unsigned)s_in << 24));
-                tw_cas(box + kTwHand, 0ull, kTwRefused);
-                __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                tw_closed = true;
-              }
+      const bool rc = ff[0] != 0.0 && ff[3] == 0.0;  // every trial rejected, and the inner solve goes on
+      tw_streak = rc ? tw_streak + 1 : 0;
+      if (!rc) tw_break_total = (int)ff[7];
+      if (tid == 0) {
+        double act = 0.0;
+        if (is_twin) {
+          if (loops == 1) stamp(kTsTFirst);
+          if (!tw_confirmed && (loops & 7) == 0 && tw_load(box + kTwHand) >= kTwRefused) act = 1.0;
+        }
+        if (act == 0.0 && !tw_closed && (is_twin || tw_streak >= 2 || tw_shown)) {
+          const int it_in = (int)ff[6], it_tot = (int)ff[7];  // the counters entering the next iteration
+          // (a column whose streak the batched sweeps have split into segments ends at its segment's end: not claimable)
+          if (rc && tw_streak >= 2 && !tw_full && (!SEG || !A.seg_end || A.seg_next[b] < 0)) {
+            const unsigned long long cnt = ((unsigned long long)(unsigned)it_in << 32) | (unsigned long long)(unsigned)it_tot;
+            tw_store(box + kTwProg, cnt);  // (all an iteration of a published streak costs: one relaxed store, nothing waited for)
+            if (!tw_shown) {
+              // once per streak: the state a claimer steps the regularisation rule from
+              ++tw_ver;
+              unsigned long long* buf = box + kTwSnap + 3 * (tw_ver & 1);
+              tw_store(buf, cnt);
+              tw_store(buf + 1, tw_bits(ff[1]));
+              tw_store(buf + 2, tw_bits(ff[2]));
+              tw_store(box + kTwInst, (unsigned long long)(unsigned)(b_real + 1));
+              // whatever the last accepted step and the first rejected iteration stored (trajectory, multipliers, cost_prev =
+              // cost_cur; a pool workgroup: its clone of them) leaves this XCD's L2 before a claimer is told that it may read it
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+              tw_order();
+              tw_store(box + kTwSeq, tw_ver);
+              tw_order();
+              __hip_atomic_fetch_or(tw.state + slot, kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              tw_shown = true;
+              stamp(kTsPSnap);
+              stamp(kTsPLoopsAtSnap, loops);
             }
           }
-          ff[13] = act;
+          // (a streak that broke: the snapshot on display describes a state that no longer exists -- a late claimer would
+          //  claim on it and be refused; hide it until the next streak publishes)
+          if (!rc && tw_shown) {
+            __hip_atomic_fetch_and(tw.state + slot, ~kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tw_store(box + kTwSeq, 0ull);
+            tw_shown = false;
+          }
+          // a claim on the second half of what is left of this segment: the newest claimer is the successor (it has
+          // inherited the former one); its words were stored before this one
+          const unsigned long long sc = tw_peek;
+          if (sc != tw_succ && (sc & kTwFrozen) == 0 && (sc & kTwSuccId) <= (unsigned long long)(2 * tw.cap)) {
+            tw_succ = sc;
+            tw_full = (int)((sc >> 16) & 0xffffull) >= tw.depth;
+            if ((sc & kTwSuccId) != 0) {
+              tw_claim = tw_load(tw.box + (size_t)((sc & kTwSuccId) - 1) * kTwWords + kTwClaim);
+              stamp(kTsPClaim);
+            }
+          }
+          if ((tw_succ & kTwSuccId) != 0) {
+            const unsigned long long* sb = tw.box + (size_t)((tw_succ & kTwSuccId) - 1) * kTwWords;
+            const int s_in = (int)(tw_claim >> 32), s_tot = (int)(tw_claim & 0xffffffffull);
+            bool refuse = !rc || it_in > s_in;
+            int why = !rc ? 1 : (it_in > s_in ? 2 : 0);
+            if (!refuse && it_in == s_in) {
+              // THE JOINT: the successor's assumptions about the state entering this iteration, bit for bit -- and no
+              // iteration since its snapshot that was anything but a rejected one
+              const unsigned long long c_rho = tw_load(sb + kTwClaimRho), c_drho = tw_load(sb + kTwClaimDrho);
+              const int c_snap = (int)tw_load(sb + kTwClaimSnap);
+              const bool same = it_tot == s_tot && tw_bits(ff[1]) == c_rho && tw_bits(ff[2]) == c_drho && tw_break_total < c_snap;
+              why = it_tot != s_tot ? 3 : (tw_bits(ff[1]) != c_rho ? 4 : (tw_bits(ff[2]) != c_drho ? 5 : 6));
+              // (no claim from here on; lost against a claimer that came too late to be served: it is refused with the rest)
+              if (same && tw_cas(box + kTwSucc, tw_succ, tw_succ | kTwFrozen)) act = 2.0; else refuse = true;
+              if (same && refuse) why = 2;
+            }
+            if (refuse) {
+              tw_store(box + kTwWhy, (unsigned long long)why | ((unsigned long long)(unsigned)it_in << 8) | ((unsigned long long)(unsigned)s_in << 24));
+              tw_cancel_chain(tw, box);  // this worker goes on alone with the state it holds
+              __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              tw_closed = true;
+            }
+          }
         }
-      } else if (tid == 0) {
-        if (loops == 1) stamp(kTsTFirst);
-        ff[13] = ((loops & 7) == 0 && tw_load(box + kTwHand) >= kTwRefused) ? 1.0 : 0.0;
+        ff[13] = act;
       }
     }
     // (waves of a workgroup share the CU's vector L1, which stores write through and keep coherent,
@@ -4405,47 +4515,81 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     if (SPEC && adopt) lds_barrier(); else __syncthreads();
     if (box) {
       const double act = ff[13];
-      if (act == 1.0) return;  // twin: the primary refused (or finished) -- nothing of the clone is visible outside its column
+      if (act == 1.0) {  // pool workgroup: refused (the refusing worker has told the chain) -- nothing of the clone is visible outside its column
+        if (tid == 0) __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+      }
       if (act == 2.0) {
-        // HAND-OVER.  Everything this workgroup has stored leaves its L2 before the twin -- which will copy its column
-        // over the instance's -- is told so: the two workgroups may sit on different XCDs, whose L2s write back on their own.
+        // HAND-OVER.  A pool workgroup answers only once its own predecessor has confirmed it: then every joint before this
+        // one holds.  Everything this workgroup has stored leaves its L2 before the successor -- whose chain will end in a
+        // copy over the instance's column -- is told so: the workgroups may sit on different XCDs, whose L2s write back on their own.
         __syncthreads();
         if (tid == 0) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-          tw_store(box + kTwHandLoops, (unsigned long long)(unsigned)loops);
-          tw_order();
-          ff[13] = tw_cas(box + kTwHand, 0ull, kTwOk) ? 3.0 : 0.0;  // (lost against a twin that gave up: go on alone)
+          unsigned long long* sb = tw.box + (size_t)((tw_succ & kTwSuccId) - 1) * kTwWords;
+          double res = 3.0;  // 3: handed over, leave; 1: this worker's own claim was refused, leave; 0: go on alone
+          if (is_twin && !tw_confirmed) {
+            unsigned long long h = 0;
+            for (int tries = 0; tries < kTwinHandPolls && (h = tw_load(box + kTwHand)) == 0; ++tries) __builtin_amdgcn_s_sleep(32);
+            if (h == 0) h = tw_cas(box + kTwHand, 0ull, kTwRevoked) ? kTwRevoked : tw_load(box + kTwHand);
+            if (h == kTwOk) {
+              tw_loops0 = (int)(unsigned)tw_load(box + kTwHandLoops);
+              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+              tw_confirmed = true;
+              if (sweeps_out) atomicAdd(sweeps_out + 4, 1);  // confirmed joints of this launch
+              stamp(kTsTVerdict);
+            } else {
+              res = 1.0;
+            }
+          }
+          if (res == 3.0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            tw_store(sb + kTwHandLoops, (unsigned long long)(unsigned)(tw_loops0 + loops));
+            tw_order();
+            res = tw_cas(sb + kTwHand, 0ull, kTwOk) ? 3.0 : 0.0;  // (lost against a successor that gave up: go on alone)
+          } else {
+            tw_cancel_chain(tw, box);
+          }
           __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           tw_closed = true;
           stamp(kTsPHand);
+          ff[13] = res;
+          ff[14] = (double)tw_loops0;
         }
         __syncthreads();
         if (ff[13] == 3.0) {
-          report(loops + skipped, loops);
-          return;  // the twin owns the instance: its copy-back is the instance's state
+          report((int)ff[14] + loops + skipped, loops);
+          return;  // the successor's chain owns the instance: its last copy-back is the instance's state
         }
+        if (ff[13] == 1.0) return;
       }
     }
   }
-  // ---- a twin commits: the primary's verdict, then the shadow column over the instance's own ----
+  // ---- the worker of the final segment commits: its predecessor's verdict (every joint before that one is confirmed
+  //      by then), then the shadow column over the instance's own ----
   if (is_twin) {
     if (tid == 0) {
       stamp(kTsTDone);
       stamp(kTsTLoops, loops);
-      unsigned long long h = 0;
-      for (int tries = 0; tries < kTwinHandPolls && (h = tw_load(box + kTwHand)) == 0; ++tries) __builtin_amdgcn_s_sleep(32);
-      if (h == 0) h = tw_cas(box + kTwHand, 0ull, kTwRevoked) ? kTwRevoked : tw_load(box + kTwHand);
-      if (h == kTwOk) {
-        ff[14] = (double)(unsigned)tw_load(box + kTwHandLoops);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        stamp(kTsTVerdict);
+      unsigned long long h = tw_confirmed ? kTwOk : 0ull;
+      if (!tw_confirmed) {
+        for (int tries = 0; tries < kTwinHandPolls && (h = tw_load(box + kTwHand)) == 0; ++tries) __builtin_amdgcn_s_sleep(32);
+        if (h == 0) h = tw_cas(box + kTwHand, 0ull, kTwRevoked) ? kTwRevoked : tw_load(box + kTwHand);
+        if (h == kTwOk) {
+          tw_loops0 = (int)(unsigned)tw_load(box + kTwHandLoops);
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          if (sweeps_out) atomicAdd(sweeps_out + 4, 1);  // confirmed joints of this launch
+          stamp(kTsTVerdict);
+        }
       }
+      // (the instance finished inside a segment that is not the final one: what comes after it assumed otherwise)
+      if (!tw_closed) tw_cancel_chain(tw, box);
+      __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ff[14] = (double)tw_loops0;
       ff[13] = h == kTwOk ? 1.0 : 0.0;
     }
     __syncthreads();
     if (ff[13] == 0.0) return;
     tw_loops0 = (int)ff[14];
-    if (sweeps_out && tid == 0) atomicAdd(sweeps_out + 4, 1);  // hand-overs of this launch
     {
       using R_ = Rec<T, M::n, M::m>;
       using RS_ = rec_scalar_t<T, M>;
@@ -4487,7 +4631,7 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     b = b_real;  // (the gains below go to the instance's own records)
     if (tid == 0) stamp(kTsTCommit);
   } else if (box && tid == 0 && !tw_closed) {
-    tw_cas(box + kTwHand, 0ull, kTwRefused);  // the instance is finished: a twin still waiting for a streak may leave
+    tw_cancel_chain(tw, box);  // the instance is finished: a successor's work is void, and the pool need not wait for a streak
     __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     stamp(kTsPEnd);
   }
