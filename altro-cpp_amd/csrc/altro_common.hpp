@@ -153,6 +153,127 @@ struct DevOpts {
   double constraint_tolerance, maximum_penalty, initial_penalty;
 };
 
+// ---- the persistent tail kernel (k_sweep_fused): its words and its LDS, shared by the kernels and the engine -------------
+#if defined(__HIPCC__)
+#define ALTRO_HD __host__ __device__ __forceinline__
+#else
+#define ALTRO_HD inline
+#endif
+constexpr int kBlock = 64;  // one wavefront per workgroup: instances never share data
+// knots per synchronisation of the persistent kernel's knot loop (the batched sweeps: 2), see producer_syncs_after.
+// Round 2 (hardware barriers only): 4 measured 5.24 -> 5.30 ms on config 2, 5.03 -> 4.74 ms on config 3, the headline kept
+// 2.  Round 3: with the forward waves of config 2 synchronised through sequence words (kSpecFree) a meeting costs the
+// consumers an LDS round trip, and 4 wins on both (tail iteration 43.8 -> 42.2 us on config 2, 57.1 -> 55.6 us on
+// config 3): 4.
+#ifndef ALTRO_SYNC_FUSED
+#define ALTRO_SYNC_FUSED 4
+#endif
+constexpr int kSyncFused = ALTRO_SYNC_FUSED;
+constexpr int kSyWords = 16;  // sequence words of the forward pass (FwdSyncWord, altro_kernels.hpp)
+
+// What a launch of the persistent kernel reports to the host: the words behind the sweep counters (`sweeps_out` in the
+// kernel; Engine::ReadBackCounters reads them back).
+enum TailReportWord {
+  kRwChainLoops = 0,   // longest chain of iterations of one instance inside this launch
+  kRwUnits = 1,        // (instance, iteration) units processed by this launch
+  kRwSweeps = 2,       // ... the longest chain counted from the first sweep of the solve
+  kRwSyncErr = 3,      // a forward wave gave up waiting for a sequence word
+  kRwHandovers = 4,    // confirmed joints between twin workgroups (depends on timing)
+  kRwClaims = 5,       // claims of pool workgroups, at every level (depends on timing)
+  kRwGroupLoops = 6,   // most iterations any ONE workgroup ran (a twin or its primary: their share)
+  kRwWords = 8
+};
+// fh (wave 0's backward pass) and fh2 (the fourth wave's speculative one): what a backward pass hands to the forward pass
+// of the same kernel.  Both blocks use the same indices; the slots from kFhRegLog on exist in fh2 only.
+enum FhSlot {
+  kFhJ0 = 0,        // running cost of the expansion step (auxiliary wave -> cost wave, behind barrier A)
+  kFhDV0 = 1,       // expected cost change, linear and quadratic term
+  kFhDV1 = 2,
+  kFhInitCost = 3,  // stats_.initial_cost (auxiliary wave -> cost wave)
+  kFhRho = 4,       // regularisation the backward pass leaves (DecreaseRegularization)
+  kFhDrho = 5,
+  kFhWords = 6,     // size of fh
+  kFhRegLog = 6,    // fh2: the regularisation the speculative pass ran with (stats_.Log("reg", rho_))
+  kFhSpecOk = 7,    // fh2: the speculative pass went through without a Cholesky failure
+  kFhSpecRho = 8,   // fh2: the regularisation the speculative pass assumed phase 3 would set (FwdSpec::inbox)
+  kFhSpecDrho = 9,
+  kFh2Words = 12    // size of fh2 (two words spare)
+};
+// ff: what phase 3 of the forward pass leaves for the kernel's bookkeeping, LDS mirrors of per-instance scalars, and the
+// words with which thread 0 (or wave 0) tells the workgroup a decision.  Slots 12 - 14 carry one name per purpose: each
+// purpose is written by one thread, read behind the next workgroup barrier and dead before the next purpose's writer runs
+// -- the claim words before the iteration loop, segment and twin words in separate barrier intervals of the loop's end, the
+// commit words behind the loop.
+enum FfSlot {
+  kFfRejected = 0,      // phase 3: the line search rejected every trial
+  kFfRho = 1,           // phase 3: the regularisation entering the next iteration
+  kFfDrho = 2,
+  kFfInnerDone = 3,     // phase 3: the inner solve ended (or the column left the solve)
+  kFfInitCost = 4,      // mirror of initial_cost (auxiliary wave, lane 0 only)
+  kFfNeedInitCost = 5,  // mirror of need_init_cost
+  kFfItInner = 6,       // phase 3: the counters entering the next iteration
+  kFfItTotal = 7,
+  kFfClaimItInner = 8,  // pool workgroup: the state its claim enters with (tw_try_claim -> tw_enter_clone)
+  kFfClaimItTotal = 9,
+  kFfClaimRho = 10,
+  kFfClaimDrho = 11,
+  kFfClaimOpen = 12,    // pool workgroup, before the loop: the claim was not refused while the clone was made
+  kFfSegLeave = 12,     // loop, segment joint: this column retires or was cancelled
+  kFfTwinAction = 13,   // loop, twin bookkeeping: 0 go on, 1 this worker's claim was refused, 2 joint reached -- hand over
+  kFfHandResult = 13,   // loop, hand-over (behind the action's barrier): 3 handed over, 1 own claim refused, 0 go on alone
+  kFfCommitOk = 13,     // behind the loop: the predecessor confirmed -- commit the shadow column
+  kFfClaimInst = 14,    // pool workgroup, before the loop: the instance of the claimed streak
+  kFfLoopsBefore = 14,  // hand-over and commit: iterations the workers before this one ran
+  kFfClaimSource = 15,  // pool workgroup: mailbox of the publisher it claimed from, -1 none
+  kFfWords = 16
+};
+
+// DISTANCE BETWEEN THE STAGED BLOCKS OF A WORKGROUP'S INSTANCES: see ALTRO_FWD_BLOCK_MOD in altro_kernels.hpp
+#ifndef ALTRO_FWD_BLOCK_MOD
+#define ALTRO_FWD_BLOCK_MOD 160
+#endif
+ALTRO_HD constexpr int fwd_block_pad_bytes(long long raw_bytes) {
+  return ALTRO_FWD_BLOCK_MOD < 0 ? 0 : (int)(((ALTRO_FWD_BLOCK_MOD - raw_bytes % 256) + 256) % 256);
+}
+template <class T>
+struct FwdLds {  // element counts of one instance's staged block (16-byte aligned sub-blocks)
+  int nX, nU, nKD, nR, nS, V;
+  ALTRO_HD int padv(int e) const { return (e + V - 1) / V * V; }
+  ALTRO_HD int rowsP() const { return padv(nR); }
+  ALTRO_HD int raw() const { return nX + nU + nKD + 2 * padv(nR) + padv(nS); }
+  ALTRO_HD int total() const { return raw() + fwd_block_pad_bytes((long long)raw() * (long long)sizeof(T)) / (int)sizeof(T); }
+};
+// LDS of k_sweep_fused: byte offset of every sub-block, in the order the kernel keeps them, and the size the engine asks
+// for.  Every count that enters is a multiple of 16 bytes (records and rows are padded to V elements, the block padding keeps
+// that, a hand-off slot is kBlock elements wide), so every sub-block up to sCost starts 16-byte aligned without rounding;
+// sCand keeps the 128-byte phase of the block before it.  tests/test_fused_lds.py checks all of this against the formula
+// Engine::PlanForwardLds used to carry.
+template <class T>
+struct FusedLds {
+  FwdLds<T> blk;  // the forward block of one instance: X | U | KD | lam | pen | ipool
+  int N, nm, npool;
+  static constexpr int kE = (int)sizeof(T), kD = (int)sizeof(double);
+  ALTRO_HD int oPool() const { return blk.total() * kE; }                    // shared parameter pool
+  ALTRO_HD int oXch() const { return oPool() + blk.padv(npool) * kE; }       // 2 kSyncFused hand-off slots [nm][kBlock]
+  ALTRO_HD int oFlags() const { return oXch() + 2 * kSyncFused * nm * kBlock * kE; }  // 2 kBlock ints: bound checks, statuses
+  ALTRO_HD int oGrad() const { return oFlags() + 2 * kBlock * (int)sizeof(int); }     // kBlock gradient slots
+  ALTRO_HD int oFh() const { return oGrad() + kBlock * kD; }                 // fh[kFhWords]
+  ALTRO_HD int oJunk() const { return oFh() + kFhWords * kD; }               // one junk slot per lane of the backward wave
+  ALTRO_HD int oActive() const { return oJunk() + kBlock * kD; }             // active flag (an int in a pair of doubles)
+  ALTRO_HD int oFf() const { return oActive() + 2 * kD; }                    // ff[kFfWords]
+  ALTRO_HD int oCand() const { return oFf() + kFfWords * kD; }               // [N + 1][kLineSearchLanes][nm] candidates
+  ALTRO_HD int oKD2() const { return oCand() + (N + 1) * kLineSearchLanes * nm * kE; }  // the speculative pass's gains + junk
+  ALTRO_HD int oFh2() const { return oKD2() + (blk.nKD + kBlock) * kE; }     // fh2[kFh2Words]
+  ALTRO_HD int oAlpha() const { return oFh2() + kFh2Words * kD; }            // [kLineSearchLanes] step lengths (8-byte slots)
+  ALTRO_HD int oSync() const { return oAlpha() + kLineSearchLanes * kD; }    // [kSyWords] ints
+  ALTRO_HD int oCost() const { return oSync() + kSyWords * (int)sizeof(int); }  // [N + 1] knot costs, padded to a pair
+  ALTRO_HD int oCvalAhead() const { return oCost() + ((N + 2) & ~1) * kE; }  // [rows] constraint values computed ahead
+  ALTRO_HD int used() const { return oCvalAhead() + blk.rowsP() * kE; }
+  // the engine has always asked for a little more than the kernel lays out (8 doubles behind the sequence words, N + 4
+  // knot costs); the LDS size decides how many workgroups share a CU, so the reserve stays
+  ALTRO_HD size_t bytes() const { return (size_t)used() + 8 * kD + (size_t)(N + 4 - ((N + 2) & ~1)) * kE; }
+};
+
 // Engines of this process that run their sweeps as chains on streams of their own, PER DEVICE (hardware queues are a
 // device's).  The count lives in libaltro_hip.so; a user-model plugin carries its own copy of this header, so the
 // library hands every plugin a pointer to ITS counter function at load time (altro_user_set_chain_hook): built-in and

@@ -1316,12 +1316,8 @@ class Engine final : public EngineBase {
     fwd_lds_bytes_ = shared_bytes + fwd_per_wave_ * per_inst;
     fwd_shared_bytes_ = shared_bytes;
     fwd_per_inst_bytes_ = per_inst;
-    fused_lds_bytes_ = (shared_bytes + (2 * kSyncFused - kFwdSlots) * (size_t)nm * kBlock * sizeof(T) + per_inst + 15) / 16 * 16 +
-                       (4 + 2 + kBlock + 2 + 16) * sizeof(double) +
-                       (size_t)(N_ + 1) * kLineSearchLanes * nm * sizeof(T) +  // + the candidates of one instance
-                       ((size_t)N_ * R::KP + kBlock) * sizeof(T) + 48 * sizeof(double) +  // + the speculative pass (gains, hand-over), step-length table, sequence words
-                       ((size_t)N_ + 4) * sizeof(T) +                                    // + the knot costs of the expansion step
-                       PadV(rows) * sizeof(T);                                           // + the constraint values of the expansions computed ahead
+    // the persistent kernel takes its pointers from the same struct (FusedLds, altro_common.hpp)
+    fused_lds_bytes_ = FusedLds<T>{FwdLds<T>{(N_ + 1) * R::nP, N_ * R::mP, N_ * R::KP, pd_.total_rows, pd_.nslots, R::V}, N_, nm, pd_.npool}.bytes();
     kdg_ = false;
     rg_ = false;
     if constexpr (kRgEligible && !kKdgEligible) PlanForwardGlbSmall(shared_bytes, per_inst);
@@ -1443,7 +1439,7 @@ class Engine final : public EngineBase {
         }
         if (loop_groups_ > 0) {
           ALTRO_TRY(Alloc(&d_loop_win_, (size_t)loop_groups_ * 4));
-          ALTRO_TRY(Alloc(&d_loop_ctl_, (size_t)kLwWords + 8));  // (+ the words the persistent tail kernel reports)
+          ALTRO_TRY(Alloc(&d_loop_ctl_, (size_t)kLwWords + kRwWords));  // (+ the words the persistent tail kernel reports)
           ALTRO_TRY(Alloc(&d_loop_tail_, (size_t)B_ + 16));
         }
       }
@@ -1840,7 +1836,7 @@ class Engine final : public EngineBase {
   altro_status LaunchSweepLoop(SolveRun& r) {
     if (!r.loop_on) return ALTRO_OK;
     if constexpr (kMfmaBackward) {
-      ALTRO_HIP_CHECK(hipMemsetAsync(d_loop_ctl_, 0, (size_t)(kLwWords + 8) * sizeof(int), stream_));
+      ALTRO_HIP_CHECK(hipMemsetAsync(d_loop_ctl_, 0, (size_t)(kLwWords + kRwWords) * sizeof(int), stream_));
       const int per_xcd = ((B_ + kLoopXcds - 1) / kLoopXcds + 15) / 16 * 16;
       const LoopCtl lc{d_loop_win_, d_loop_ctl_, d_loop_tail_, r.loop_handover, per_xcd};
       PoisonLds();
@@ -2085,9 +2081,9 @@ class Engine final : public EngineBase {
     int sweeps = 0;  // longest chain of iterations, the look-ahead sweep of a chain that ran dry included
     for (int c = 0; c < r.C; ++c) sweeps = std::max(sweeps, r.chain[c].sweeps);
     if (r.persistent_launched) {
-      int extra[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      int extra[kRwWords] = {0};  // TailReportWord
       if (r.loop_launched) {
-        int words[kLwWords + 8];
+        int words[kLwWords + kRwWords];
         ALTRO_HIP_CHECK(CopySync(words, d_loop_ctl_, sizeof(words), hipMemcpyDeviceToHost));
         std::memcpy(extra, words + kLwWords, sizeof(extra));
         timing_.loop_workgroups = words[kLwGroups];
@@ -2095,7 +2091,7 @@ class Engine final : public EngineBase {
         timing_.loop_handover = words[kLwTail];
         timing_.loop_iterations = words[kLwMaxLoops];
         sweeps = words[kLwMaxLoops];
-        extra[2] += words[kLwMaxLoops];
+        extra[kRwSweeps] += words[kLwMaxLoops];
         if (sw_.loop_log) {
           const double per = words[kLwGroups] > 0 ? 0.01 / words[kLwGroups] : 0.0;  // 100 MHz ticks -> us per workgroup
           fprintf(stderr, "LOOPLOG %d workgroups (%d per CU), %d units, longest %d iterations, handed over %d | us per workgroup: slots %.1f E %.1f B %.1f F %.1f\n",
@@ -2105,23 +2101,23 @@ class Engine final : public EngineBase {
       } else {
         ALTRO_HIP_CHECK(CopySync(extra, d_counter_ + r.max_sweeps + 2, sizeof(extra), hipMemcpyDeviceToHost));
       }
-      timing_.twin_handovers = extra[4];
-      timing_.twin_claims = extra[5];
-      timing_.fused_workgroup_iterations = extra[6];
+      timing_.twin_handovers = extra[kRwHandovers];
+      timing_.twin_claims = extra[kRwClaims];
+      timing_.fused_workgroup_iterations = extra[kRwGroupLoops];
       if (r.seg_on && sw_.twin_debug) {
         int cur[kMaxChains] = {0};
         ALTRO_HIP_CHECK(CopySync(cur, d_seg_cursor_, sizeof(cur), hipMemcpyDeviceToHost));
         fprintf(stderr, "segments: shadow columns used per chain %d %d %d %d (of %d each), persistent launch over <= %d slots, longest own chain %d, longest workgroup %d\n",
-                cur[0], cur[1], cur[2], cur[3], r.seg_capc, (int)timing_.twin_workgroups, extra[0], extra[6]);
+                cur[0], cur[1], cur[2], cur[3], r.seg_capc, (int)timing_.twin_workgroups, extra[kRwChainLoops], extra[kRwGroupLoops]);
       }
       if (twin_cap_ > 0 && sw_.twin_debug) ALTRO_TRY(DumpTwinMailboxes());
-      if (extra[3] != 0) {
+      if (extra[kRwSyncErr] != 0) {
         err_ = "k_sweep_fused: a forward wave gave up waiting for its sequence word (software synchronisation)";
         return ALTRO_HIP_ERROR;
       }
-      timing_.fused_sweeps = extra[0];
-      timing_.fused_instance_iterations = extra[1];
-      sweeps = std::max(sweeps, extra[2]);
+      timing_.fused_sweeps = extra[kRwChainLoops];
+      timing_.fused_instance_iterations = extra[kRwUnits];
+      sweeps = std::max(sweeps, extra[kRwSweeps]);
     }
     timing_.sweeps = sweeps;
     return ALTRO_OK;

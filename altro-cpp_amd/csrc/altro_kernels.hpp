@@ -33,17 +33,8 @@
 
 namespace altro_hip {
 
-constexpr int kBlock = 64;  // one wavefront per workgroup: instances never share data
+// (kBlock, kSyncFused and the layout of the persistent kernel's LDS: altro_common.hpp, shared with the engine)
 constexpr int kFwdWaves = 3;  // k_forward2 / k_sweep_fused: rollout wave, cost wave, auxiliary wave
-// knots per synchronisation of the persistent kernel's knot loop (the batched sweeps: 2), see producer_syncs_after.
-// Round 2 (hardware barriers only): 4 measured 5.24 -> 5.30 ms on config 2, 5.03 -> 4.74 ms on config 3, the headline kept
-// 2.  Round 3: with the forward waves of config 2 synchronised through sequence words (kSpecFree) a meeting costs the
-// consumers an LDS round trip, and 4 wins on both (tail iteration 43.8 -> 42.2 us on config 2, 57.1 -> 55.6 us on
-// config 3): 4.
-#ifndef ALTRO_SYNC_FUSED
-#define ALTRO_SYNC_FUSED 4
-#endif
-constexpr int kSyncFused = ALTRO_SYNC_FUSED;
 constexpr int kEAheadToErrWord = -7;      // kSyErr - kSyEAhead0 (FwdSyncWord, asserted there)
 constexpr int kFwdSpinLimit = 1 << 22;   // polls of an LDS sequence word (~0.1 us each) before a wave gives up
 // Debugging aid (ALTRO_HIP_DEBUG_POISON): fills the LDS of the CU it lands on with a pattern, so that a kernel that reads
@@ -664,15 +655,16 @@ constexpr int kBwdChunk = 126;  // knots of gains buffered in LDS between two bu
 // slot_base + blk of the launch).  sKD: LDS buffer of kBwdChunk * 4 * RR::KP + 64 doubles (RR: the stored record).
 // FUSED (k_sweep_fused): one instance per wavefront (block 0), the gains go straight into the forward
 // pass's LDS block sKDf[k * KP + e] (+ a junk slot at sKDf[fused_junk + lane]) and are also written to
-// A.KD at the end; the running cost J0 is summed by the other wave; dV0 / dV1 are handed over in fh[1..2].
+// A.KD at the end; the running cost J0 is summed by the other wave; dV0 / dV1 are handed over in fh[kFhDV0], fh[kFhDV1].
 // T is the STORAGE type of the engine (records, gains, costs); the recursion itself always runs in fp64 on
 // the fp64 matrix cores -- an fp32 engine reads float tiles, converts exactly, and rounds the gains once.
 // SPEC (the fourth wave of k_sweep_fused): the backward pass of the NEXT iteration, run beside the forward pass of
 // this one on the assumption that the line search rejects every trial -- then the trajectory and the multipliers do
 // not change, the expansions of the next iteration are the ones in memory, and the only input that differs is the
 // regularisation (spec_rho, spec_drho = what phase 3 will set).  Nothing is written to global memory: the gains go to
-// a second LDS block (sKDf), the hand-over values to fh[1], [2], [4], [5], the regularisation that was used to fh[6]
-// and fh[7] = 1 if the pass went through without a Cholesky failure (a failure simply invalidates the speculation).
+// a second LDS block (sKDf), the hand-over values to fh[kFhDV0], [kFhDV1], [kFhRho], [kFhDrho], the regularisation that was
+// used to fh[kFhRegLog] and fh[kFhSpecOk] = 1 if the pass went through without a Cholesky failure (a failure simply
+// invalidates the speculation).
 // lds_unset (FUSED, the first iteration of a launch): sKDf does not hold the instance's gains yet -- the kernel stages none,
 // every pass that reaches knot 0 writes them all.  A pass that GIVES UP leaves the knots from its lowest failing knot down
 // untouched (ilqr.hpp:409-427), so it fetches those from A.KD; in later iterations sKDf holds the previous pass's gains.
@@ -976,17 +968,17 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
       A.dV1[b] = 0.5 * dV1;
     }
     if (FUSED) {
-      fh[1] = dV0;
-      fh[2] = 0.5 * dV1;
+      fh[kFhDV0] = dV0;
+      fh[kFhDV1] = 0.5 * dV1;
     }
   }
   if (c != 0) return;
   if (SPEC) {
-    fh[6] = rho;  // stats_.Log("reg", rho_) of the speculated iteration
+    fh[kFhRegLog] = rho;  // stats_.Log("reg", rho_) of the speculated iteration
     decrease_reg(o, &rho, &drho);
-    fh[4] = rho;
-    fh[5] = drho;
-    fh[7] = spec_bad ? 0.0 : 1.0;
+    fh[kFhRho] = rho;
+    fh[kFhDrho] = drho;
+    fh[kFhSpecOk] = spec_bad ? 0.0 : 1.0;
     return;
   }
   if (!FUSED) {
@@ -1003,8 +995,8 @@ ALTRO_DEV void backward_mfma_body(const DevArrays<T>& A, const DevOpts& o, int a
   A.drho[b] = drho;
   A.status[b] = status;
   if (FUSED) {  // the forward pass of the same kernel must not depend on L1 seeing these stores
-    fh[4] = rho;
-    fh[5] = drho;
+    fh[kFhRho] = rho;
+    fh[kFhDrho] = drho;
   }
 }
 
@@ -1788,6 +1780,125 @@ ALTRO_DEV bool conv_stats_and_done_pre(const DevArrays<T>& A, const DevOpts& o, 
   return done;
 }
 
+// ---- one column of the per-instance arrays copied onto another (segments of rejection streaks, twin workgroups) ----
+// The parts of a column, and who copies which:
+//
+//                                    Traj  X0  Rows  Costs  Params  Exp  Gains  State
+//   segment clone (forward_phase3)    x    x    x             x                          kColSegClone
+//   twin clone    (tw_enter_clone)    x    x    x      x      x                   x      kColTwinClone
+//   twin commit   (tw_commit)         x         x      x             x            x      kColTwinCommit
+//   k_seg_fixup                       x         x      x             x     x      x      kColSegFixup
+//
+// A CLONE starts a shadow column that has held nothing of the instance, so it needs the initial state and the per-instance
+// parameters; nothing reads the records it lacks before an expansion step and a backward pass have rewritten them.  The
+// segment clone's solver state is DERIVED, not copied (forward_phase3 writes it out); the twin clone copies it and then
+// overrides what the rejected iterations up to its first one will have changed (tw_enter_clone).  A COMMIT goes over the
+// instance's own column, which has x0 and the parameters; it carries the expansion records for the getters.  The twin's gains
+// are in its LDS and go to the instance's records from there (end of k_sweep_fused); k_seg_fixup has only the column's.
+enum ColumnPart : unsigned {
+  kColTraj = 1,     // X, U
+  kColX0 = 2,       // x0
+  kColRows = 4,     // lam, pen, cval
+  kColCosts = 8,    // costs
+  kColParams = 16,  // ipool
+  kColExp = 32,     // expansion records, in the stored type
+  kColGains = 64,   // gain records, in the stored type
+  kColState = 128,  // every per-instance solver-state scalar (copy_column_state)
+  kColSegClone = kColTraj | kColX0 | kColRows | kColParams,
+  kColTwinClone = kColSegClone | kColCosts | kColState,
+  kColTwinCommit = kColTraj | kColRows | kColCosts | kColExp | kColState,
+  kColSegFixup = kColTwinCommit | kColGains
+};
+// THE list of per-instance solver-state scalars (DevArrays): one thread, loads before stores
+template <class T>
+ALTRO_DEV void copy_column_state(const DevArrays<T>& A, unsigned src, unsigned dst) {
+  const double c0 = A.rho_reg[src], c1 = A.drho[src], c2 = A.dV0[src], c3 = A.dV1[src], c4 = A.J0[src], c5 = A.initial_cost[src],
+               c6 = A.cost_cur[src], c7 = A.cost_prev[src], c8 = A.dJ[src], c9 = A.grad[src], c10 = A.viol[src], c11 = A.penmax[src],
+               c12 = A.alpha[src], c13 = A.z[src], c14 = A.reg_log[src];
+  const int i0 = A.status[src], i1 = A.status_al[src], i2 = A.it_inner[src], i3 = A.it_outer[src], i4 = A.it_total[src],
+            i5 = A.phase[src], i6 = A.need_init_cost[src];
+  A.rho_reg[dst] = c0; A.drho[dst] = c1; A.dV0[dst] = c2; A.dV1[dst] = c3; A.J0[dst] = c4;
+  A.initial_cost[dst] = c5; A.cost_cur[dst] = c6; A.cost_prev[dst] = c7; A.dJ[dst] = c8; A.grad[dst] = c9;
+  A.viol[dst] = c10; A.penmax[dst] = c11; A.alpha[dst] = c12; A.z[dst] = c13; A.reg_log[dst] = c14;
+  A.status[dst] = i0; A.status_al[dst] = i1; A.it_inner[dst] = i2; A.it_outer[dst] = i3; A.it_total[dst] = i4;
+  A.phase[dst] = i5; A.need_init_cost[dst] = i6;
+}
+// one array of per-knot records [k][Bp][EP]
+template <class E_>
+ALTRO_DEV void copy_column_records(E_* arr, int knots, int EP, unsigned Bp, unsigned src, unsigned dst, int tid, int nthreads) {
+  for (int i = tid; i < knots * EP; i += nthreads) {
+    const int k = i / EP, e = i - k * EP;
+    arr[((size_t)(unsigned)k * Bp + dst) * EP + e] = arr[((size_t)(unsigned)k * Bp + src) * EP + e];
+  }
+}
+// `parts` (ColumnPart) of column src onto column dst, by threads tid = 0 .. nthreads - 1 (a workgroup, or the line-search lanes
+// of one instance); the state scalars by thread 0.  No barrier: the caller orders the copy against its readers.
+template <class T, class M>
+ALTRO_DEV void copy_column(const DevArrays<T>& A, const ProblemDesc* pd, unsigned src, unsigned dst, unsigned parts, int tid,
+                           int nthreads) {
+  using R = Rec<T, M::n, M::m>;
+  using RS = rec_scalar_t<T, M>;
+  using RR = Rec<RS, M::n, M::m>;
+  const unsigned Bp = A.Bp;
+  const int N = A.N;
+  if (parts & kColTraj) {
+    copy_column_records(A.X, N + 1, R::nP, Bp, src, dst, tid, nthreads);
+    copy_column_records(A.U, N, R::mP, Bp, src, dst, tid, nthreads);
+  }
+  if ((parts & kColX0) && tid < R::nP) A.x0[(size_t)dst * R::nP + tid] = A.x0[(size_t)src * R::nP + tid];
+  if (parts & kColExp) copy_column_records((RS*)A.EXP, N + 1, RR::EP, Bp, src, dst, tid, nthreads);
+  if (parts & kColGains) copy_column_records((RS*)A.KD, N, RR::KP, Bp, src, dst, tid, nthreads);
+  if (parts & kColCosts)
+    for (int r = tid; r <= N; r += nthreads) A.costs[(unsigned)r * Bp + dst] = A.costs[(unsigned)r * Bp + src];
+  if (parts & kColRows)
+    for (int r = tid; r < pd->total_rows; r += nthreads) {
+      A.lam[(unsigned)r * Bp + dst] = A.lam[(unsigned)r * Bp + src];
+      A.pen[(unsigned)r * Bp + dst] = A.pen[(unsigned)r * Bp + src];
+      A.cval[(unsigned)r * Bp + dst] = A.cval[(unsigned)r * Bp + src];
+    }
+  if (parts & kColParams) {
+    T* const ip = const_cast<T*>(A.ipool);
+    for (int r = tid; r < pd->nslots; r += nthreads) ip[(unsigned)r * Bp + dst] = ip[(unsigned)r * Bp + src];
+  }
+  if ((parts & kColState) && tid == 0) copy_column_state(A, src, dst);
+}
+
+// The JOINT of two segments of a rejection streak (DevArrays::seg_*), one thread: column b, which was cancelled or has a
+// successor nxt, has finished an iteration that leaves the counters it_next / tot_next and the regularisation rho_next /
+// drho_next; rc = every trial was rejected and the inner solve goes on.  A cancelled column leaves: a predecessor did not
+// arrive where it assumed it would, its work is void.  At its segment's end the column verifies, bit for bit, what its
+// successor assumed when it started, and retires; anything else -- an accepted step, an end of the inner solve, a
+// regularisation off the rule -- cancels the successors, and the column goes on alone.  Returns true if the column leaves.
+// (forward_phase3 calls it for the batched kernels, k_sweep_fused in its own bookkeeping step: compiled into the phase 3
+//  of the persistent kernel it cost that kernel's register allocation 560 B of scratch per lane.)
+template <class T>
+ALTRO_DEV bool seg_joint(const DevArrays<T>& A, int b, int flag, int nxt, bool rc, int it_next, int tot_next, double rho_next,
+                         double drho_next) {
+  if (flag & kSegCancelled) return true;
+  bool leave = false, cancel = !rc;
+  if (rc && it_next == A.seg_end[b]) {
+    const bool same = A.seg_tot0[nxt] == tot_next && __double_as_longlong(A.seg_rho0[nxt]) == __double_as_longlong(rho_next) &&
+                      __double_as_longlong(A.seg_drho0[nxt]) == __double_as_longlong(drho_next) &&
+                      (__hip_atomic_load(A.seg_flag + nxt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kSegCancelled) == 0;
+    if (same) {
+      A.seg_flag[b] = flag | kSegRetired;  // (the next column owns the instance from here: k_seg_fixup follows the chain)
+      leave = true;
+    } else {
+      cancel = true;
+    }
+  }
+  if (cancel) {
+    int sgd = nxt;
+    for (int guard = 0; sgd >= 0 && guard < 256; ++guard) {
+      atomicOr(A.seg_flag + sgd, kSegCancelled);
+      sgd = A.seg_next[sgd];
+    }
+    A.seg_next[b] = -1;
+    A.seg_end[b] = kSegNoEnd;
+  }
+  return leave;
+}
+
 // Phase 3 of the forward pass: per-instance state machine (shared by both forward kernels).
 // Lane 0 of the instance takes the decisions; the row sweeps of the AL transition (dual and penalty
 // updates) are spread over its 20 lanes.  sKD / sU: LDS copies of the gains / controls (or nullptr).
@@ -1855,9 +1966,9 @@ ALTRO_DEV void forward_phase3(const DevArrays<T>& A, const ProblemDesc* pd, cons
       rho_next = rho;
       drho_next = drho;
       if (ff) {  // what the stall detector of the persistent kernel compares between iterations
-        ff[0] = accepted ? 0.0 : 1.0;
-        ff[1] = rho;
-        ff[2] = drho;
+        ff[kFfRejected] = accepted ? 0.0 : 1.0;
+        ff[kFfRho] = rho;
+        ff[kFfDrho] = drho;
       }
     }
     if (accepted) {
@@ -1873,8 +1984,8 @@ ALTRO_DEV void forward_phase3(const DevArrays<T>& A, const ProblemDesc* pd, cons
       const double gsum = accepted ? g_sel : gsum_rej;
       inner_done = conv_stats_and_done_pre(A, o, b, gsum, viol, pre, cost_cur, last_status) ? 1 : 0;
       if (ff) {  // (persistent kernel: the counters this iteration leaves -- what a twin workgroup's hand-over compares)
-        ff[6] = (double)(pre.it_inner + 1);
-        ff[7] = (double)(pre.it_total + 1);
+        ff[kFfItInner] = (double)(pre.it_inner + 1);
+        ff[kFfItTotal] = (double)(pre.it_total + 1);
       }
     }
   }
@@ -1890,31 +2001,8 @@ ALTRO_DEV void forward_phase3(const DevArrays<T>& A, const ProblemDesc* pd, cons
       const int it_next = pre.it_inner + 1, tot_next = pre.it_total + 1;
       const int flag = A.seg_flag[b];
       const int nxt = A.seg_next[b];
-      if (flag & kSegCancelled) {
-        drop = 1;  // a predecessor did not arrive where this column assumed it would: its work is void
-      } else if (nxt >= 0) {
-        bool cancel = !rc;
-        if (rc && it_next == A.seg_end[b]) {
-          // the end of this column's segment: does it hold, bit for bit, what the next column assumed when it started?
-          const bool same = A.seg_tot0[nxt] == tot_next && __double_as_longlong(A.seg_rho0[nxt]) == __double_as_longlong(rho_next) &&
-                            __double_as_longlong(A.seg_drho0[nxt]) == __double_as_longlong(drho_next) &&
-                            (__hip_atomic_load(A.seg_flag + nxt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kSegCancelled) == 0;
-          if (same) {
-            A.seg_flag[b] = flag | kSegRetired;  // (the next column owns the instance from here: k_seg_fixup follows the chain)
-            drop = 1;
-          } else {
-            cancel = true;
-          }
-        }
-        if (cancel) {  // an accepted step, an end of the inner solve, a regularisation off the rule: the successors are void
-          int sgd = nxt;
-          for (int guard = 0; sgd >= 0 && guard < 256; ++guard) {
-            atomicOr(A.seg_flag + sgd, kSegCancelled);
-            sgd = A.seg_next[sgd];
-          }
-          A.seg_next[b] = -1;
-          A.seg_end[b] = kSegNoEnd;
-        }
+      if ((flag & kSegCancelled) || nxt >= 0) {
+        drop = seg_joint(A, b, flag, nxt, rc, it_next, tot_next, rho_next, drho_next) ? 1 : 0;
       } else if (SPLIT && rc && streak >= 2 && !active_out && A.next_count && A.seg_parts > 1) {
         // ---- split: what is left of this inner solve (ilqr.hpp:600-611 caps it) in seg_parts segments ----
         const int r1 = o.max_iterations_inner - it_next, r2 = o.max_iterations_total - tot_next;
@@ -1977,30 +2065,11 @@ ALTRO_DEV void forward_phase3(const DevArrays<T>& A, const ProblemDesc* pd, cons
     if (SPLIT && nclones > 0) {
       // the clones' share of the instance: trajectory, multipliers, penalties, parameters -- nothing a rejected iteration
       // changes (the stored constraint values, knot costs, records and gains are recomputed before they are read)
-      using R_ = Rec<T, M::n, M::m>;
-      for (int j = 0; j < nclones; ++j) {
-        const unsigned col = (unsigned)(first + j);
-        for (int i = t; i < (N + 1) * R_::nP; i += LS) {
-          const int k = i / R_::nP, e = i - k * R_::nP;
-          A.X[((size_t)(unsigned)k * Bp + col) * R_::nP + e] = A.X[((size_t)(unsigned)k * Bp + (unsigned)b) * R_::nP + e];
-        }
-        for (int i = t; i < N * R_::mP; i += LS) {
-          const int k = i / R_::mP, e = i - k * R_::mP;
-          A.U[((size_t)(unsigned)k * Bp + col) * R_::mP + e] = A.U[((size_t)(unsigned)k * Bp + (unsigned)b) * R_::mP + e];
-        }
-        if (t < R_::nP) A.x0[(size_t)col * R_::nP + t] = A.x0[(size_t)(unsigned)b * R_::nP + t];
-        for (int r = t; r < pd->total_rows; r += LS) {
-          A.lam[(unsigned)r * Bp + col] = A.lam[(unsigned)r * Bp + (unsigned)b];
-          A.pen[(unsigned)r * Bp + col] = A.pen[(unsigned)r * Bp + (unsigned)b];
-          A.cval[(unsigned)r * Bp + col] = A.cval[(unsigned)r * Bp + (unsigned)b];
-        }
-        T* const ip = const_cast<T*>(A.ipool);
-        for (int r = t; r < pd->nslots; r += LS) ip[(unsigned)r * Bp + col] = ip[(unsigned)r * Bp + (unsigned)b];
-      }
+      for (int j = 0; j < nclones; ++j) copy_column<T, M>(A, pd, (unsigned)b, (unsigned)(first + j), kColSegClone, t, LS);
     }
     if (drop) {  // retired or cancelled: this column leaves the solve here
       if (t == 0) {
-        if (ff) ff[3] = 1.0;
+        if (ff) ff[kFfInnerDone] = 1.0;
         if (active_out) *active_out = 0;
         A.phase[b] = 0;
       }
@@ -2071,8 +2140,8 @@ ALTRO_DEV void forward_phase3(const DevArrays<T>& A, const ProblemDesc* pd, cons
         if (t == 0) {
           begin_inner_solve(A, o, b);
           if (ff) {
-            ff[5] = 1.0;  // (persistent kernel: LDS mirror of need_init_cost)
-            ff[6] = 0.0;  // ... and of it_inner
+            ff[kFfNeedInitCost] = 1.0;  // (persistent kernel: LDS mirror of need_init_cost)
+            ff[kFfItInner] = 0.0;  // ... and of it_inner
           }
         }
       }
@@ -2082,7 +2151,7 @@ ALTRO_DEV void forward_phase3(const DevArrays<T>& A, const ProblemDesc* pd, cons
     }
   }
   if (t != 0) return;
-  if (ff) ff[3] = inner_done ? 1.0 : 0.0;
+  if (ff) ff[kFfInnerDone] = inner_done ? 1.0 : 0.0;
   if (active_out) *active_out = active ? 1 : 0;  // persistent sweep kernel: keep iterating?
   if (!active) {
     A.phase[b] = 0;
@@ -2265,20 +2334,7 @@ ALTRO_DEV void rollout_run(const Ctx& C, const ProblemDesc* pd, const DevArrays<
 // What it buys is LDS issue slots, not time -- a lone wave reads at the same pace with and without the counted conflicts, and
 // the A/B on the real kernel is neutral (6.09 - 6.19 against 6.15 - 6.20 ms per step; 96 B, equally conflict-free in the
 // probe, is 5 % SLOWER: profiles/r06_experiments.txt #5).
-#ifndef ALTRO_FWD_BLOCK_MOD
-#define ALTRO_FWD_BLOCK_MOD 160
-#endif
-__host__ __device__ constexpr int fwd_block_pad_bytes(long long raw_bytes) {
-  return ALTRO_FWD_BLOCK_MOD < 0 ? 0 : (int)(((ALTRO_FWD_BLOCK_MOD - raw_bytes % 256) + 256) % 256);
-}
-template <class T>
-struct FwdLds {  // element counts of one instance's staged block (16-byte aligned sub-blocks)
-  int nX, nU, nKD, nR, nS, V;
-  ALTRO_DEV int padv(int e) const { return (e + V - 1) / V * V; }
-  ALTRO_DEV int rowsP() const { return padv(nR); }
-  ALTRO_DEV int raw() const { return nX + nU + nKD + 2 * padv(nR) + padv(nS); }
-  ALTRO_DEV int total() const { return raw() + fwd_block_pad_bytes((long long)raw() * (long long)sizeof(T)) / (int)sizeof(T); }
-};
+// (fwd_block_pad_bytes, FwdLds and the persistent kernel's FusedLds: altro_common.hpp)
 
 // Single-wave forward pass that reads everything from global memory: the fallback when the staged block of
 // one instance exceeds the LDS, or line_search_max_iterations > 20 (rounds of 20 trials).
@@ -2645,8 +2701,8 @@ ALTRO_DEV int fwd_slot(int k, int G = 2) { return k & (2 * G - 1); }
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kFwdSeqStride = 1 << 12;   // > stretches of one forward pass (N / G + 2)
 enum FwdSyncWord { kSyPub = 0, kSyErr = 1, kSyCons0 = 2, kSyCons1 = 3, kSyA = 4, kSyS = 5, kSyV0 = 6, kSyV1 = 7,
-                   kSyEAhead0 = 8,  // + wave index 0..2: iteration whose expansions-ahead that wave has finished (all modes)
-                   kSyWords = 16 };
+                   kSyEAhead0 = 8 };  // + wave index 0..2: iteration whose expansions-ahead that wave has finished (all modes)
+                                      // (kSyWords = 16 of them: altro_common.hpp)
 static_assert(kSyErr - kSyEAhead0 == kEAheadToErrWord, "forward_phase3 raises the error word relative to the E-ahead words");
 template <bool SOFT>
 struct FwdSync {
@@ -3522,18 +3578,19 @@ ALTRO_DEV void forward2_body(const DevArrays<T>& A, const ProblemDesc* __restric
                                     gsx, grad_in_loop, sy, FUSED ? sCost : nullptr, &J0_run);
     if (FUSED && lane == 0) {
       // J0 of the expansion step and, on the first iteration of an inner solve, stats_.initial_cost (ilqr.hpp:298);
-      // ff[4] / ff[5]: LDS mirrors of initial_cost / need_init_cost (phase 3 sets ff[5] when a new inner solve begins)
+      // ff[kFfInitCost] / ff[kFfNeedInitCost]: LDS mirrors of initial_cost / need_init_cost (phase 3 sets the latter when a new
+      // inner solve begins)
       A.J0[b] = J0_run;
-      double ic = ff[4];
-      if (ff[5] != 0.0) {
+      double ic = ff[kFfInitCost];
+      if (ff[kFfNeedInitCost] != 0.0) {
         ic = J0_run;
         A.initial_cost[b] = J0_run;
         A.need_init_cost[b] = 0;
       }
-      fhw[0] = J0_run;
-      fhw[3] = ic;
-      ff[4] = ic;
-      ff[5] = 0.0;
+      fhw[kFhJ0] = J0_run;
+      fhw[kFhInitCost] = ic;
+      ff[kFfInitCost] = ic;
+      ff[kFfNeedInitCost] = 0.0;
     }
     ALTRO_STAMP_ADD(7, st_w2);
     sy.signal_a();  // barrier A
@@ -3564,12 +3621,12 @@ ALTRO_DEV void forward2_body(const DevArrays<T>& A, const ProblemDesc* __restric
     if (wave == 3) {
       // ============ fourth wave: the backward pass of the NEXT iteration, assuming this line search fails ============
       // (ilqr.hpp:550: a rejected step raises the regularisation; nothing else changes)
-      double rho_in = fh[4], drho_in = fh[5];
+      double rho_in = fh[kFhRho], drho_in = fh[kFhDrho];
       increase_reg(o, &rho_in, &drho_in);
       if (lane == 0) {
         spec->inbox[0] = rho_in;
         spec->inbox[1] = drho_in;
-        spec->fh2[7] = 0.0;
+        spec->fh2[kFhSpecOk] = 0.0;
       }
       int nbar = 0;
       const long long st_w3 = ALTRO_STAMP_T0();
@@ -3591,11 +3648,11 @@ ALTRO_DEV void forward2_body(const DevArrays<T>& A, const ProblemDesc* __restric
   CtxL<T> C(A, b, sPool, sIp, sLam, sPen);
   const long long st_w1 = ALTRO_STAMP_T0();
   double J0 = FUSED ? 0.0 : A.J0[b];  // (FUSED: summed by the auxiliary wave during the knot loop, read behind barrier A)
-  const double dV0 = FUSED ? fh[1] : A.dV0[b], dV1 = FUSED ? fh[2] : A.dV1[b];
+  const double dV0 = FUSED ? fh[kFhDV0] : A.dV0[b], dV1 = FUSED ? fh[kFhDV1] : A.dV1[b];
   InstPre pre = load_inst_pre(A, b);  // consumed by the state machine at the very end
   if (FUSED) {
-    pre.rho_reg = fh[4];
-    pre.drho = fh[5];
+    pre.rho_reg = fh[kFhRho];
+    pre.drho = fh[kFhDrho];
   }
   double J = 0.0;
   for (int r = 0; r < pd->nruns; ++r) {
@@ -3629,8 +3686,8 @@ ALTRO_DEV void forward2_body(const DevArrays<T>& A, const ProblemDesc* __restric
   }
   sy.await_a();  // barrier A: the auxiliary wave's verdicts (FUSED: and the running cost)
   if (FUSED) {
-    J0 = fh[0];
-    pre.initial_cost = fh[3];
+    J0 = fh[kFhJ0];
+    pre.initial_cost = fh[kFhInitCost];
   }
   ALTRO_STAMP_ADD(3, st_w1);
   const long long st_w1b = ALTRO_STAMP_T0();
@@ -3965,6 +4022,583 @@ ALTRO_DEV void tw_cancel_chain(const TwinCtl& tw, unsigned long long* box) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The steps of k_sweep_fused.  The kernel further down is a list of them; each is force-inlined into it, so what they
+// share -- fences, tw_order(), compare-and-swaps, barriers, bounded polls -- runs in the order the kernel calls them.
+// ---------------------------------------------------------------------------------------------------------------------
+template <class T>
+struct TailCtx {  // what every step sees: the launch's arguments, the workgroup's ff words, the thread
+  const DevArrays<T>& A;
+  const ProblemDesc* pd;
+  const DevOpts& o;
+  const TwinCtl& tw;
+  int* sweeps_out;  // the launch's report words (TailReportWord), or nullptr
+  double* ff;       // FfSlot
+  int tid;
+};
+// A worker of the twin protocol (TwinCtl): a primary workgroup with a mailbox, or a pool workgroup.  streak / break_total
+// are kept by every thread; the words from ver on are thread 0's.
+struct TwinWorker {
+  unsigned long long* box = nullptr;  // its mailbox (nullptr: the launch has no twins, or the slot lies beyond tw.cap)
+  int slot = -1;                      // index of its mailbox: the launch slot of a primary, tw.cap + t of pool workgroup t
+  bool is_twin = false;               // a pool workgroup
+  int streak = 0;                     // consecutive rejected iterations during which the inner solve went on
+  int break_total = -1;               // it_total left by the last iteration that was NOT one of those
+  unsigned long long ver = 0;         // version of the newest snapshot
+  bool closed = false;                // nothing more is published, no successor is waited for
+  bool shown = false;                 // the state word says "snapshot on display"
+  unsigned long long succ = 0, claim = 0;  // the mailbox's successor word and the iteration the successor starts at, once seen
+  unsigned long long peek = 0;        // the mailbox's successor word, requested at the top of the iteration
+  bool full = false;                  // this worker's line of claims has reached tw.depth -- nothing more to show or to look for
+  bool confirmed = false;             // pool workgroup: the predecessor has confirmed the state this worker entered with
+  int loops0 = 0;                     // pool workgroup: iterations the workers before it ran before the hand-over
+  ALTRO_DEV void stamp(const TwinCtl& tw, int which, long long value = -1) const {
+    if (box && tw.debug) tw_store(box + kTwStamp + which, (unsigned long long)(value >= 0 ? value : wall_clock64()));
+  }
+  ALTRO_DEV void close(const TwinCtl& tw) const {
+    __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+// report of a workgroup to the host (longest chain of iterations, units processed): both ways out of the kernel
+template <class T, bool SEG, bool SOFT>
+ALTRO_DEV void fused_report(const TailCtx<T>& C, int b_real, const int* sync_words, int chain_loops, int units, int skipped) {
+  const DevArrays<T>& A = C.A;
+  int* const sweeps_out = C.sweeps_out;
+  if (sweeps_out && C.tid == 0) {
+    atomicMax(sweeps_out + kRwChainLoops, chain_loops);
+    atomicAdd(sweeps_out + kRwUnits, units);
+    atomicMax(sweeps_out + kRwGroupLoops, units + skipped);
+    // (a column of a split streak that the sweeps handed over sits behind the batch; the tail launch carries
+    //  the first shadow column in seg_lo and the columns per chain in seg_hi, which give the chain that owns it)
+    int chain = 0;
+    if (A.chain_size) {
+      chain = (SEG && A.seg_end && b_real >= A.B && A.seg_hi > 0 && b_real >= A.seg_lo) ? (b_real - A.seg_lo) / A.seg_hi : b_real / A.chain_size;
+      chain = chain < kMaxSweepChains - 1 ? chain : kMaxSweepChains - 1;
+    }
+    atomicMax(sweeps_out + kRwSweeps, A.chain_base[chain] + chain_loops);
+    if (SOFT && sync_words[kSyErr] != 0) atomicMax(sweeps_out + kRwSyncErr, 1);
+  }
+}
+
+// ---- pool workgroups: find work.  Wave 0 scans the mailboxes for the published segment with the most iterations left
+//      (late stragglers first, once CUs free up) and lane 0 tries to claim its second half. ----
+// One look at every mailbox -- the primaries', then the pool's.  Returns the wave's best candidate as (iterations left << 16 |
+// 0xffff - position in the scan), 0 for none; *waiting_out: workers that may still offer something -- alive (or not yet
+// dispatched), not full, long enough.
+ALTRO_DEV int tw_scan(const TwinCtl& tw, const DevOpts& o, int nsl, int nall, int self, int lane, int* waiting_out) {
+  int waiting = 0, key = 0;
+  for (int v0 = 0; v0 < nall; v0 += kBlock) {
+    const int v = v0 + lane;
+    bool open = false;
+    if (v < nall) {
+      const int id = v < nsl ? v : tw.cap + (v - nsl);
+      const unsigned long long st = id == self ? kTwsClosed : tw_load(tw.state + id);
+      open = (st & (kTwsClosed | kTwsFull)) == 0 && (v < nsl || (st & kTwsBusy) != 0);
+      if (open && (st & kTwsSnap) != 0) {
+        const unsigned long long* bx = tw.box + (size_t)id * kTwWords;
+        const int R = tw_remaining(o, tw_load(bx + kTwProg), (int)tw_load(bx + kTwEnd));
+        open = tw_claimable(R, tw.lag);
+        if (open && (st & kTwsLocked) == 0) {
+          const int k2 = ((R < 0x7fff ? R : 0x7fff) << 16) | (0xffff - (v & 0xffff));
+          key = k2 > key ? k2 : key;
+        }
+      }
+    }
+    waiting += __popcll(__ballot(open));
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    const int other = __shfl_xor(key, d);
+    key = other > key ? other : key;
+  }
+  *waiting_out = waiting;
+  return key;
+}
+// Lane 0: claim from the worker at position v of the scan the iterations behind the share it keeps.  Locks the publisher's
+// state word, reads its snapshot, steps the regularisation rule to the claimed iteration, fills this workgroup's mailbox
+// and swaps itself in as the publisher's successor.  Returns the publisher's mailbox + 1, or 0; the state the claim enters
+// with goes to ff[kFfClaim*].
+template <class T>
+ALTRO_DEV int tw_try_claim(const TailCtx<T>& C, int v, int nsl, int self) {
+  const TwinCtl& tw = C.tw;
+  const DevOpts& o = C.o;
+  int* const sweeps_out = C.sweeps_out;
+  double* const ff = C.ff;
+  int got = 0;
+  const int id = v < nsl ? v : tw.cap + (v - nsl);
+  unsigned long long* bx = tw.box + (size_t)id * kTwWords;
+  const unsigned long long st0 = kTwsSnap | (v < nsl ? 0ull : kTwsBusy);
+  if (!tw_cas(tw.state + id, st0, st0 | kTwsLocked)) return 0;
+  unsigned long long more = 0;  // bits for the publisher's state word
+  const unsigned long long ver = tw_load(bx + kTwSeq);
+  if (ver != 0) {
+    const unsigned long long* buf = bx + kTwSnap + 3 * (ver & 1);
+    const unsigned long long c0 = tw_load(buf), rb = tw_load(buf + 1), db = tw_load(buf + 2);
+    const unsigned long long pr = tw_load(bx + kTwProg), so = tw_load(bx + kTwSucc), inst = tw_load(bx + kTwInst);
+    const int end_in = (int)tw_load(bx + kTwEnd), gen = (int)((so >> 16) & 0xffffull);
+    const bool stable = tw_load(bx + kTwSeq) == ver;  // (the streak whose snapshot this is is still on)
+    const int in0 = (int)(c0 >> 32), tot0 = (int)(c0 & 0xffffffffull), in1 = (int)(pr >> 32), tot1 = (int)(pr & 0xffffffffull);
+    const int R = tw_remaining(o, pr, end_in);
+    if (gen >= tw.depth) more = kTwsFull;
+    if (stable && more == 0 && (so & kTwFrozen) == 0 && inst != 0 && in1 >= in0 && in1 - in0 == tot1 - tot0 && tw_claimable(R, tw.lag)) {
+      const int ahead = tw_keep(R, tw.lag);  // iterations the publisher keeps, counted from where it is
+      // the regularisation entering iteration `start`: every iteration since the snapshot runs its backward pass
+      // (DecreaseRegularization, ilqr.hpp:440) and rejects its line search (IncreaseRegularization, :550)
+      double rho = tw_dbl(rb), drho = tw_dbl(db);
+      for (int jj = 0; jj < in1 - in0 + ahead; ++jj) {
+        decrease_reg(o, &rho, &drho);
+        increase_reg(o, &rho, &drho);
+      }
+      const int nth = sweeps_out ? atomicAdd(sweeps_out + kRwClaims, 1) + 1 : 1;
+      if (tw.misclaim > 0 && nth % tw.misclaim == 0) rho = tw_dbl(tw_bits(rho) ^ 1ull);  // (test only: the joint must refuse)
+      const bool full = gen + 1 >= tw.depth;
+      unsigned long long* mine = tw.box + (size_t)self * kTwWords;
+      tw_store(mine + kTwClaimRho, tw_bits(rho));
+      tw_store(mine + kTwClaimDrho, tw_bits(drho));
+      tw_store(mine + kTwClaimSnap, (unsigned long long)(unsigned)tot0);
+      tw_store(mine + kTwClaim, ((unsigned long long)(unsigned)(in1 + ahead) << 32) | (unsigned long long)(unsigned)(tot1 + ahead));
+      tw_store(mine + kTwInst, inst);
+      tw_store(mine + kTwGen, (unsigned long long)(unsigned)(gen + 1));
+      tw_store(mine + kTwEnd, (unsigned long long)(unsigned)end_in);  // (the publisher's former end and successor: inherited)
+      tw_store(mine + kTwSucc, (so & kTwSuccId) | ((unsigned long long)(unsigned)(gen + 1) << 16));
+      tw_store(mine + kTwPred, (unsigned long long)(unsigned)(id + 1));
+      tw_store(tw.state + self, kTwsBusy | (full ? kTwsFull : 0ull));
+      tw_store(bx + kTwEnd, (unsigned long long)(unsigned)(in1 + ahead));
+      tw_order();
+      // the claim: the publisher looks at this word once per iteration; lost against a publisher that has reached a joint
+      if (tw_cas(bx + kTwSucc, so, (unsigned long long)(unsigned)(self + 1) | ((unsigned long long)(unsigned)(gen + 1) << 16))) {
+        ff[kFfClaimItInner] = (double)(in1 + ahead);
+        ff[kFfClaimItTotal] = (double)(tot1 + ahead);
+        ff[kFfClaimRho] = rho;
+        ff[kFfClaimDrho] = drho;
+        ff[kFfClaimInst] = (double)((int)inst - 1);
+        if (full) more = kTwsFull;
+        got = id + 1;
+      } else {
+        tw_store(tw.state + self, 0ull);
+        if (sweeps_out) atomicSub(sweeps_out + kRwClaims, 1);
+      }
+    }
+  }
+  if (more != 0) __hip_atomic_fetch_or(tw.state + id, more, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_and(tw.state + id, ~kTwsLocked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return got;
+}
+// Wave 0 of a pool workgroup: scan and try until a claim holds, nobody can publish any more, or kTwinIdlePolls looks have
+// passed.  Leaves the publisher's mailbox (-1: none) in ff[kFfClaimSource] for the workgroup, behind the caller's barrier.
+template <class T>
+ALTRO_DEV void tw_find_work(const TailCtx<T>& C, int self, int lane) {
+  const TwinCtl& tw = C.tw;
+  const int cnt_slots = C.A.act_count ? *C.A.act_count : C.A.act_count_const;
+  const int nsl = cnt_slots < tw.cap ? cnt_slots : tw.cap;
+  const int nall = nsl + tw.npool;  // the primaries' mailboxes, then the pool's
+  int chosen = -1;
+  for (int tries = 0; tries < kTwinIdlePolls && chosen < 0; ++tries) {
+    int waiting = 0;
+    const int key = tw_scan(tw, C.o, nsl, nall, self, lane, &waiting);
+    int got = 0;
+    if (key != 0 && lane == 0) got = tw_try_claim(C, 0xffff - (key & 0xffff), nsl, self);
+    got = __shfl(got, 0);
+    if (got > 0) chosen = got - 1;
+    if (chosen < 0) {
+      if (key == 0 && waiting == 0) break;  // nobody can publish a segment worth splitting any more
+      // (>= 25 us between two looks: r06_experiments.txt #4 measured what 300 fast pollers cost the workers)
+      for (int z = 0; z < (key == 0 ? 8 : 1); ++z) __builtin_amdgcn_s_sleep(127);
+    }
+  }
+  if (lane == 0) {
+    C.ff[kFfClaimSource] = (double)chosen;
+    // (what the publisher's workgroup stored before it published -- the trajectory of its last accepted step, the
+    //  multipliers, or its clone of them -- may sit in another XCD's L2: its release is matched by this acquire)
+    if (chosen >= 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  }
+}
+// ---- pool workgroup with a claim: clone the instance into the shadow column and enter the state the claim names ----
+// All threads, behind the barrier that publishes tw_find_work's words.  Returns false if the workgroup has nothing to do: no
+// claim, or refused already -- the publisher broke its streak or finished while the clone was made.
+template <class T, class M, bool SEG>
+ALTRO_DEV bool tw_enter_clone(const TailCtx<T>& C, TwinWorker& w, int tslot, long long tstart_clock, int nthreads, int* b,
+                              int* b_real) {
+  const DevArrays<T>& A = C.A;
+  const TwinCtl& tw = C.tw;
+  double* const ff = C.ff;
+  const int tid = C.tid;
+  const int src_id = (int)ff[kFfClaimSource];
+  if (src_id < 0) return false;
+  w.slot = tw.cap + tslot;
+  w.box = tw.box + (size_t)w.slot * kTwWords;
+  *b_real = (int)ff[kFfClaimInst];
+  // (the column the publisher works on: the instance's own, or a pool workgroup's shadow column)
+  const int b_src = src_id < tw.cap ? instance_of_slot(A, src_id, 0) : tw.col0 + (src_id - tw.cap);
+  if (tid == 0) {
+    w.stamp(tw, kTsTStart, tstart_clock);
+    w.stamp(tw, kTsTGo);
+  }
+  const int bT = tw.col0 + tslot;
+  // per-instance solver state: as the publisher left it ...
+  copy_column<T, M>(A, C.pd, (unsigned)b_src, (unsigned)bT, kColTwinClone, tid, nthreads);
+  if (tid == 0) {
+    // ... but for what the rejected iterations up to `start` will have changed: counters, regularisation, and the
+    // previous cost, which every iteration of a streak sets to the (unchanged) current one (solver_stats.cpp:54-66)
+    if (SEG && A.seg_end) {
+      A.seg_end[bT] = kSegNoEnd;
+      A.seg_next[bT] = -1;
+      A.seg_flag[bT] = 0;
+      A.seg_streak[bT] = 2;
+    }
+    A.cost_prev[bT] = A.cost_cur[bT];  // (this thread's own store, above)
+    A.it_inner[bT] = (int)ff[kFfClaimItInner];
+    A.it_total[bT] = (int)ff[kFfClaimItTotal];
+    A.rho_reg[bT] = ff[kFfClaimRho];
+    A.drho[bT] = ff[kFfClaimDrho];
+  }
+  *b = bT;
+  __syncthreads();
+  if (tid == 0) w.stamp(tw, kTsTCloned);
+  if (tid == 0) {  // (refused already -- the publisher broke its streak or finished)
+    ff[kFfClaimOpen] = tw_load(w.box + kTwHand) == 0 ? 1.0 : 0.0;
+    if (ff[kFfClaimOpen] == 0.0) w.close(tw);
+  }
+  __syncthreads();
+  return ff[kFfClaimOpen] != 0.0;
+}
+
+// ---- B was run ahead (fourth wave) during the previous forward pass: take its results ----
+template <class T>
+ALTRO_DEV void fused_adopt_spec(const DevArrays<T>& A, int b, T* sKDf, const T* sKD2, int nKD, double* fh, const double* fh2,
+                                int tid, int nthreads) {
+  for (int i = tid; i < nKD; i += nthreads) sKDf[i] = sKD2[i];
+  if (tid == 0) {
+    double h[6];
+    h[0] = fh2[kFhDV0]; h[1] = fh2[kFhDV1]; h[2] = fh2[kFhRho]; h[3] = fh2[kFhDrho]; h[4] = fh2[kFhRegLog];  // (the fourth wave's hand-over values)
+    fh[kFhDV0] = h[0];
+    fh[kFhDV1] = h[1];
+    fh[kFhRho] = h[2];
+    fh[kFhDrho] = h[3];
+    A.dV0[b] = h[0];
+    A.dV1[b] = h[1];
+    A.reg_log[b] = h[4];  // stats_.Log("reg", rho_)
+    A.rho_reg[b] = h[2];
+    A.drho[b] = h[3];
+  }
+}
+
+// ---- E AHEAD.  Phase 3 runs on the cost wave alone; the other waves left the forward pass behind barrier V and
+//      would only wait for it.  If the line search rejected every trial, the trajectory and -- unless phase 3 ends
+//      the inner solve -- the multipliers are what they were, so the next iteration's expansions can be computed
+//      NOW, from the same LDS block, by the waves that are free: the same work the next iteration would do at its
+//      top (nothing is skipped), 6 000 cycles earlier.  If phase 3 does end the inner solve (dual / penalty update)
+//      or the instance, the result is discarded and E runs again as usual. ----
+//      Two things keep the state exactly the reference's: the constraint values c_ that an expansion step stores
+//      (ilqr.hpp:675 -> al_cost.hpp:264-274) go to an LDS scratch (sCvalAhead) and are committed by the kernel only when
+//      the expansions are the next iteration's -- phase 3's dual update reads the c_ the line search left (quirk Q6) --,
+//      and the cost wave holds its dual / penalty sweeps until these waves are through (forward_phase3), so that the
+//      records left in memory when the instance finishes are this iteration's own.
+//      Waves 0, 2 (, 3) of the workgroup; `loops` is already this iteration's number + 1.
+template <class T, class M, bool WAVE4>
+ALTRO_DEV void fused_expand_ahead(const DevArrays<T>& A, const ProblemDesc* pd, const FwdLds<T>& L, T* sm, T* sPool, T* sCost,
+                                  T* sCvalAhead, int* sync_words, int b, int wave, int lane, int loops) {
+  constexpr int kAhead = WAVE4 ? 3 : 2;     // waves 0, 2 (, 3)
+  const int wi = wave == 0 ? 0 : wave - 1;  // 0, 1 (, 2)
+  const CtxL<T> CA(A, b, sPool, sm + L.nX + L.nU + L.nKD + 2 * L.rowsP(), sm + L.nX + L.nU + L.nKD,
+                   sm + L.nX + L.nU + L.nKD + L.rowsP(), sCvalAhead);
+  expansion_from_lds<T, M>(A, pd, CA, sm, sm + L.nX, sCost, b, wi * kBlock + lane, kAhead * kBlock);
+  if (lane == 0) FwdSync<true>::post(sync_words + kSyEAhead0 + wi, loops);
+}
+
+// ---- OPT-IN (DevOpts::fast_forward_stalls), off by default.  A rejected line search leaves the trajectory, the
+//      multipliers and -- once the regularisation has settled into its increase/decrease cycle -- the whole state of the
+//      instance unchanged, so the next iteration recomputes exactly the same rejection: the reference (and the default
+//      path here) repeats it until max_iterations_inner.  Two consecutive rejections with bit-identical regularisation
+//      state prove the fixed point; the identical iterations in between are then only counted (and logged), and the last
+//      one is executed normally so that every status decision is taken by the usual code.  Returns the iterations that
+//      thread 0 skipped (0 in every other thread: the caller keeps them apart from `loops`, which must stay wave-uniform). ----
+struct StallWatch {
+  bool prev_rej = false;
+  double prev_rho = -1.0, prev_drho = -1.0;
+};
+template <class T>
+ALTRO_DEV int fused_fast_forward(const TailCtx<T>& C, StallWatch& s, int b) {
+  const DevArrays<T>& A = C.A;
+  const DevOpts& o = C.o;
+  const double* ff = C.ff;
+  const bool rej = ff[kFfRejected] != 0.0 && ff[kFfInnerDone] == 0.0;
+  const bool stalled = rej && s.prev_rej && ff[kFfRho] == s.prev_rho && ff[kFfDrho] == s.prev_drho;
+  s.prev_rej = rej;
+  s.prev_rho = ff[kFfRho];
+  s.prev_drho = ff[kFfDrho];
+  int skipped = 0;
+  if (stalled && C.tid == 0) {
+    const int it_in = A.it_inner[b], it_tot = A.it_total[b];
+    int k = o.max_iterations_inner - 1 - it_in;
+    const int k2 = o.max_iterations_total - 1 - it_tot;
+    k = k < k2 ? k : k2;
+    if (k > 0) {
+      A.it_inner[b] = it_in + k;
+      A.it_total[b] = it_tot + k;
+      for (int j = 0; j < k; ++j) hist_push(A, b);
+      skipped = k;
+    }
+    // the cost wave of the next iteration reads these counters from global memory (load_inst_pre): another wave, and
+    // the barrier below may be LDS-only -- drain this wave's stores first (with the expansions computed ahead there
+    // is no expansion phase in between any more to hide the race)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  return skipped;
+}
+
+// ---- segments of rejection streaks (DevArrays::seg_*) that the batched sweeps handed over: a column with a successor
+//      verifies the successor's assumptions at its segment's end and retires, or cancels the chain; a cancelled column
+//      leaves (seg_joint).  Thread 0; the verdict goes to ff[kFfSegLeave] for the workgroup.  The iteration that just ended
+//      is complete either way; a column that leaves does so through the loop's normal exit. ----
+template <class T>
+ALTRO_DEV void fused_seg_joint(const TailCtx<T>& C, int b) {
+  const DevArrays<T>& A = C.A;
+  double* const ff = C.ff;
+  const int flag = A.seg_flag[b];
+  const int nxt = A.seg_next[b];
+  const bool rc = ff[kFfRejected] != 0.0 && ff[kFfInnerDone] == 0.0;  // every trial rejected, and the inner solve goes on
+  double leave = 0.0;
+  if ((flag & kSegCancelled) || nxt >= 0)
+    leave = seg_joint(A, b, flag, nxt, rc, (int)ff[kFfItInner], (int)ff[kFfItTotal], ff[kFfRho], ff[kFfDrho]) ? 1.0 : 0.0;
+  if (leave != 0.0) A.phase[b] = 0;
+  ff[kFfSegLeave] = leave;
+}
+
+// ---- twin workgroups (TwinCtl), thread 0, behind every iteration.  Every worker: show where it is while a streak is on
+//      (tw_publish), see a claim on the rest of its segment (tw_see_claim), answer its successor at the joint (tw_joint).
+//      Pool workgroups: a look at their own verdict now and then. ----
+// rc = every trial rejected and the inner solve goes on; it_in / it_tot: the counters entering the next iteration
+template <class T, bool SEG>
+ALTRO_DEV void tw_publish(const TailCtx<T>& C, TwinWorker& w, bool rc, int it_in, int it_tot, int loops, int b, int b_real) {
+  const TwinCtl& tw = C.tw;
+  const double* ff = C.ff;
+  // (a column whose streak the batched sweeps have split into segments ends at its segment's end: not claimable)
+  if (rc && w.streak >= 2 && !w.full && (!SEG || !C.A.seg_end || C.A.seg_next[b] < 0)) {
+    const unsigned long long cnt = ((unsigned long long)(unsigned)it_in << 32) | (unsigned long long)(unsigned)it_tot;
+    tw_store(w.box + kTwProg, cnt);  // (all an iteration of a published streak costs: one relaxed store, nothing waited for)
+    if (!w.shown) {
+      // once per streak: the state a claimer steps the regularisation rule from
+      ++w.ver;
+      unsigned long long* buf = w.box + kTwSnap + 3 * (w.ver & 1);
+      tw_store(buf, cnt);
+      tw_store(buf + 1, tw_bits(ff[kFfRho]));
+      tw_store(buf + 2, tw_bits(ff[kFfDrho]));
+      tw_store(w.box + kTwInst, (unsigned long long)(unsigned)(b_real + 1));
+      // whatever the last accepted step and the first rejected iteration stored (trajectory, multipliers, cost_prev =
+      // cost_cur; a pool workgroup: its clone of them) leaves this XCD's L2 before a claimer is told that it may read it
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      tw_order();
+      tw_store(w.box + kTwSeq, w.ver);
+      tw_order();
+      __hip_atomic_fetch_or(tw.state + w.slot, kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      w.shown = true;
+      w.stamp(tw, kTsPSnap);
+      w.stamp(tw, kTsPLoopsAtSnap, loops);
+    }
+  }
+  // (a streak that broke: the snapshot on display describes a state that no longer exists -- a late claimer would
+  //  claim on it and be refused; hide it until the next streak publishes)
+  if (!rc && w.shown) {
+    __hip_atomic_fetch_and(tw.state + w.slot, ~kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tw_store(w.box + kTwSeq, 0ull);
+    w.shown = false;
+  }
+}
+// a claim on the second half of what is left of this segment: the newest claimer is the successor (it has inherited the
+// former one); its words were stored before this one
+ALTRO_DEV void tw_see_claim(const TwinCtl& tw, TwinWorker& w) {
+  const unsigned long long sc = w.peek;
+  if (sc != w.succ && (sc & kTwFrozen) == 0 && (sc & kTwSuccId) <= (unsigned long long)(2 * tw.cap)) {
+    w.succ = sc;
+    w.full = (int)((sc >> 16) & 0xffffull) >= tw.depth;
+    if ((sc & kTwSuccId) != 0) {
+      w.claim = tw_load(tw.box + (size_t)((sc & kTwSuccId) - 1) * kTwWords + kTwClaim);
+      w.stamp(tw, kTsPClaim);
+    }
+  }
+}
+// This worker has a successor.  Before the successor's first iteration it goes on; past it, or with a streak that broke, it
+// refuses: the chain is cancelled and this worker goes on alone with the state it holds.  Returns true at the joint, if
+// the successor's assumptions hold (then no further claim is taken: kTwFrozen).
+template <class T>
+ALTRO_DEV bool tw_joint(const TailCtx<T>& C, TwinWorker& w, bool rc, int it_in, int it_tot) {
+  const TwinCtl& tw = C.tw;
+  const double* ff = C.ff;
+  const unsigned long long* sb = tw.box + (size_t)((w.succ & kTwSuccId) - 1) * kTwWords;
+  const int s_in = (int)(w.claim >> 32), s_tot = (int)(w.claim & 0xffffffffull);
+  bool refuse = !rc || it_in > s_in, hand = false;
+  int why = !rc ? 1 : (it_in > s_in ? 2 : 0);
+  if (!refuse && it_in == s_in) {
+    // THE JOINT: the successor's assumptions about the state entering this iteration, bit for bit -- and no
+    // iteration since its snapshot that was anything but a rejected one
+    const unsigned long long c_rho = tw_load(sb + kTwClaimRho), c_drho = tw_load(sb + kTwClaimDrho);
+    const int c_snap = (int)tw_load(sb + kTwClaimSnap);
+    const bool same = it_tot == s_tot && tw_bits(ff[kFfRho]) == c_rho && tw_bits(ff[kFfDrho]) == c_drho && w.break_total < c_snap;
+    why = it_tot != s_tot ? 3 : (tw_bits(ff[kFfRho]) != c_rho ? 4 : (tw_bits(ff[kFfDrho]) != c_drho ? 5 : 6));
+    // (no claim from here on; lost against a claimer that came too late to be served: it is refused with the rest)
+    if (same && tw_cas(w.box + kTwSucc, w.succ, w.succ | kTwFrozen)) hand = true; else refuse = true;
+    if (same && refuse) why = 2;
+  }
+  if (refuse) {
+    tw_store(w.box + kTwWhy, (unsigned long long)why | ((unsigned long long)(unsigned)it_in << 8) | ((unsigned long long)(unsigned)s_in << 24));
+    tw_cancel_chain(tw, w.box);  // this worker goes on alone with the state it holds
+    w.close(tw);
+    w.closed = true;
+  }
+  return hand;
+}
+// all threads of a worker with a mailbox; thread 0 leaves its decision in ff[kFfTwinAction]
+template <class T, bool SEG>
+ALTRO_DEV void tw_bookkeeping(const TailCtx<T>& C, TwinWorker& w, int loops, int b, int b_real) {
+  const TwinCtl& tw = C.tw;
+  double* const ff = C.ff;
+  const bool rc = ff[kFfRejected] != 0.0 && ff[kFfInnerDone] == 0.0;  // every trial rejected, and the inner solve goes on
+  w.streak = rc ? w.streak + 1 : 0;
+  if (!rc) w.break_total = (int)ff[kFfItTotal];
+  if (C.tid == 0) {
+    double act = 0.0;
+    if (w.is_twin) {
+      if (loops == 1) w.stamp(tw, kTsTFirst);
+      if (!w.confirmed && (loops & 7) == 0 && tw_load(w.box + kTwHand) >= kTwRefused) act = 1.0;
+    }
+    if (act == 0.0 && !w.closed && (w.is_twin || w.streak >= 2 || w.shown)) {
+      const int it_in = (int)ff[kFfItInner], it_tot = (int)ff[kFfItTotal];  // the counters entering the next iteration
+      tw_publish<T, SEG>(C, w, rc, it_in, it_tot, loops, b, b_real);
+      tw_see_claim(tw, w);
+      if ((w.succ & kTwSuccId) != 0 && tw_joint(C, w, rc, it_in, it_tot)) act = 2.0;
+    }
+    ff[kFfTwinAction] = act;
+  }
+}
+// Thread 0 of a pool workgroup waits for its predecessor's verdict on the state it entered with -- the predecessor answers
+// at the joint, so the bound only guards against one that never runs; a worker that gives up revokes its claim.  Returns
+// the verdict; on kTwOk the worker is confirmed, knows the iterations run before it, and sees what its predecessors stored.
+template <class T>
+ALTRO_DEV unsigned long long tw_await_verdict(const TailCtx<T>& C, TwinWorker& w) {
+  unsigned long long h = 0;
+  for (int tries = 0; tries < kTwinHandPolls && (h = tw_load(w.box + kTwHand)) == 0; ++tries) __builtin_amdgcn_s_sleep(32);
+  if (h == 0) h = tw_cas(w.box + kTwHand, 0ull, kTwRevoked) ? kTwRevoked : tw_load(w.box + kTwHand);
+  if (h == kTwOk) {
+    w.loops0 = (int)(unsigned)tw_load(w.box + kTwHandLoops);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    w.confirmed = true;
+    if (C.sweeps_out) atomicAdd(C.sweeps_out + kRwHandovers, 1);  // confirmed joints of this launch
+    w.stamp(C.tw, kTsTVerdict);
+  }
+  return h;
+}
+// HAND-OVER (all threads; ff[kFfTwinAction] was 2).  A pool workgroup answers only once its own predecessor has confirmed
+// it: then every joint before this one holds.  Everything this workgroup has stored leaves its L2 before the successor --
+// whose chain will end in a copy over the instance's column -- is told so: the workgroups may sit on different XCDs, whose
+// L2s write back on their own.  Returns ff[kFfHandResult]: 3 handed over, leave (ff[kFfLoopsBefore]: the iterations run
+// before this worker); 1 this worker's own claim was refused, leave; 0 go on alone.
+template <class T>
+ALTRO_DEV double tw_hand_over(const TailCtx<T>& C, TwinWorker& w, int loops) {
+  const TwinCtl& tw = C.tw;
+  __syncthreads();
+  if (C.tid == 0) {
+    unsigned long long* sb = tw.box + (size_t)((w.succ & kTwSuccId) - 1) * kTwWords;
+    double res = 3.0;
+    if (w.is_twin && !w.confirmed && tw_await_verdict(C, w) != kTwOk) res = 1.0;
+    if (res == 3.0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      tw_store(sb + kTwHandLoops, (unsigned long long)(unsigned)(w.loops0 + loops));
+      tw_order();
+      res = tw_cas(sb + kTwHand, 0ull, kTwOk) ? 3.0 : 0.0;  // (lost against a successor that gave up: go on alone)
+    } else {
+      tw_cancel_chain(tw, w.box);
+    }
+    w.close(tw);
+    w.closed = true;
+    w.stamp(tw, kTsPHand);
+    C.ff[kFfHandResult] = res;
+    C.ff[kFfLoopsBefore] = (double)w.loops0;
+  }
+  __syncthreads();
+  return C.ff[kFfHandResult];
+}
+// ---- the worker of the final segment commits (all threads of a pool workgroup, behind the loop): its predecessor's
+//      verdict (every joint before that one is confirmed by then), then the shadow column b over the instance's own.
+//      Returns false if the verdict is not kTwOk: nothing of the clone is visible outside its column. ----
+template <class T, class M>
+ALTRO_DEV bool tw_commit(const TailCtx<T>& C, TwinWorker& w, int loops, int b, int b_real, int nthreads) {
+  const TwinCtl& tw = C.tw;
+  double* const ff = C.ff;
+  if (C.tid == 0) {
+    w.stamp(tw, kTsTDone);
+    w.stamp(tw, kTsTLoops, loops);
+    const unsigned long long h = w.confirmed ? kTwOk : tw_await_verdict(C, w);
+    // (the instance finished inside a segment that is not the final one: what comes after it assumed otherwise)
+    if (!w.closed) tw_cancel_chain(tw, w.box);
+    w.close(tw);
+    ff[kFfLoopsBefore] = (double)w.loops0;
+    ff[kFfCommitOk] = h == kTwOk ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  if (ff[kFfCommitOk] == 0.0) return false;
+  w.loops0 = (int)ff[kFfLoopsBefore];
+  copy_column<T, M>(C.A, C.pd, (unsigned)b, (unsigned)b_real, kColTwinCommit, C.tid, nthreads);
+  if (C.tid == 0) w.stamp(tw, kTsTCommit);
+  return true;
+}
+#ifdef ALTRO_STAMPS
+// thread 0 of a straggler (a few dozen lines per launch): where the cycles of an adopted iteration went
+ALTRO_DEV void fused_stamp_summary(int b, int loops, int spec_iters) {
+  const double c = 1.0 / spec_iters;
+  const double ca = 1.0 / loops;  // the per-wave stamps run in every iteration
+  printf("STAMPS (instance %d): %d iterations, %d adopted (speculated); per adopted iteration, shader-clock cycles:\n"
+         "  E %.0f | take-over %.0f | forward pass (wave 0) %.0f | barrier behind F (wave 0 waits) %.0f | whole iteration %.0f\n"
+         "  rollout wave: knot loop %.0f, wait A+S %.0f, phase 2 %.0f\n"
+         "  cost wave: knot loop + wait A %.0f, selection %.0f, phase 2 + wait V %.0f, phase 3 %.0f\n"
+         "  auxiliary wave: knot loop %.0f | fourth wave: speculative backward pass %.0f (only passes of armed iterations)\n"
+         "  take-over: copy + hand-over (wave 0) %.0f, running cost (wave 1) %.0f | E alone, waves 0..3: %.0f %.0f %.0f %.0f | E ahead (wave 0) %.0f\n",
+         b, loops, spec_iters, c * g_stamp_acc[9], c * g_stamp_acc[10], c * g_stamp_acc[11], c * g_stamp_acc[12], c * g_stamp_acc[14],
+         ca * g_stamp_acc[0], ca * g_stamp_acc[1], ca * g_stamp_acc[2], ca * g_stamp_acc[3], ca * g_stamp_acc[4], ca * g_stamp_acc[5],
+         ca * g_stamp_acc[6], ca * g_stamp_acc[7], c * g_stamp_acc[8], c * g_stamp_acc[16], c * g_stamp_acc[15],
+         c * g_stamp_acc[17], c * g_stamp_acc[18], c * g_stamp_acc[19], c * g_stamp_acc[20], c * g_stamp_acc[21]);
+}
+#endif
+
+// The kernel's pointers into its LDS, taken from FusedLds: the forward block of one instance, then {pool, hand-off slots,
+// flags, gradient slots} exactly as k_forward2 lays them out (forward2_body finds those itself), then the fused extras.
+template <class T>
+struct FusedSmem {
+  T* sm;            // the staged block: X | U | KD | lam | pen | ipool
+  T* sKDf;          // its gain block: wave 0's backward pass writes it, the forward pass reads it
+  T* sPool;         // shared parameters
+  T* xch;           // hand-off slots; its first words carry the line search's selection
+  double* fh;       // FhSlot
+  int fused_junk;   // one junk slot per lane of the backward wave, in units of T behind sKDf
+  int* active_flag;
+  double* ff;       // FfSlot
+  T* sCand;         // [N + 1][kLineSearchLanes][n + m] line-search candidates
+  T* sKD2;          // the speculative backward pass: second gain block + junk slots ...
+  double* fh2;      // ... its hand-over values and the regularisation it assumed (FhSlot)
+  T* alpha_tab;     // [kLineSearchLanes] step lengths of the line-search lanes (ilqr.hpp:544)
+  int* sync_words;  // [kSyWords] FwdSync<true> (kSpecFree), E ahead
+  T* sCost;         // [N + 1] knot costs of the expansion step
+  T* sCvalAhead;    // [total_rows] constraint values of the expansions computed ahead
+  ALTRO_DEV FusedSmem(unsigned char* raw, const FwdLds<T>& L, const FusedLds<T>& F)
+      : sm(reinterpret_cast<T*>(raw)), sKDf(sm + L.nX + L.nU), sPool(reinterpret_cast<T*>(raw + F.oPool())),
+        xch(reinterpret_cast<T*>(raw + F.oXch())), fh(reinterpret_cast<double*>(raw + F.oFh())),
+        fused_junk((int)(reinterpret_cast<T*>(raw + F.oJunk()) - sKDf)), active_flag(reinterpret_cast<int*>(raw + F.oActive())),
+        ff(reinterpret_cast<double*>(raw + F.oFf())), sCand(reinterpret_cast<T*>(raw + F.oCand())),
+        sKD2(reinterpret_cast<T*>(raw + F.oKD2())), fh2(reinterpret_cast<double*>(raw + F.oFh2())),
+        alpha_tab(reinterpret_cast<T*>(raw + F.oAlpha())), sync_words(reinterpret_cast<int*>(raw + F.oSync())),
+        sCost(reinterpret_cast<T*>(raw + F.oCost())), sCvalAhead(reinterpret_cast<T*>(raw + F.oCvalAhead())) {}
+};
+// the sequence words start at zero (visible behind the staging barrier of the first iteration); the step-length table
+template <class T>
+ALTRO_DEV void fused_init_lds(const FusedSmem<T>& S, const DevOpts& o, int tid) {
+  if (tid < kSyWords) S.sync_words[tid] = 0;
+  if (tid < kLineSearchLanes) {
+    T alpha = T(1);
+    for (int i = 0; i < tid; ++i) alpha /= T(o.line_search_decrease_factor);
+    S.alpha_tab[tid] = alpha;
+  }
+}
+
 template <class T, class M, bool CIRC, int SPEC, bool SEG = false>
 __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) * kBlock) void k_sweep_fused(
     DevArrays<T> A, const ProblemDesc* __restrict__ pdg, const ProblemDesc pd_arg, DevOpts o, int mode, int persistent,
@@ -3979,47 +4613,24 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   if (blockIdx.x == 0 && tid == 0) publish_count(A);
   // (twin workgroups, see TwinCtl: blocks [base, ...) of the launch are a POOL -- each serves whichever slot of the launch
   //  publishes a streak first -- and block base + t owns shadow column col0 + t)
-  const bool is_twin = tw.base > 0 && (int)blockIdx.x >= tw.base;
-  const int tslot = is_twin ? (int)blockIdx.x - tw.base : -1;
-  int slot = is_twin ? -1 : (int)blockIdx.x;
-  int b_real = is_twin ? -1 : instance_of_slot(A, slot, 0);
-  if (!is_twin && b_real < 0) return;  // uniform over the workgroup
-  if (is_twin && (tslot >= tw.npool || tslot >= tw.cap || !persistent)) return;
-  unsigned long long* box = (!is_twin && tw.base > 0 && slot < tw.cap && persistent) ? tw.box + (size_t)slot * kTwWords : nullptr;
+  TwinWorker w;
+  w.is_twin = tw.base > 0 && (int)blockIdx.x >= tw.base;
+  const int tslot = w.is_twin ? (int)blockIdx.x - tw.base : -1;
+  w.slot = w.is_twin ? -1 : (int)blockIdx.x;
+  int b_real = w.is_twin ? -1 : instance_of_slot(A, w.slot, 0);
+  if (!w.is_twin && b_real < 0) return;  // uniform over the workgroup
+  if (w.is_twin && (tslot >= tw.npool || tslot >= tw.cap || !persistent)) return;
+  if (!w.is_twin && tw.base > 0 && w.slot < tw.cap && persistent) w.box = tw.box + (size_t)w.slot * kTwWords;
   int b = b_real;  // (a twin switches to its shadow column once it has claimed its share of the iterations)
   const int N = A.N;
   const unsigned Bp = A.Bp;
-  // LDS: the forward block of one instance, then {pool, hand-off slots, flags} exactly as k_forward2
-  // lays them out, then the fused extras: fh[4] and a junk slot per lane for the backward wave
   const FwdLds<T> L{(N + 1) * R::nP, N * R::mP, N * R::KP, pd->total_rows, pd->nslots, R::V};
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  T* sKDf = sm + L.nX + L.nU;
-  T* sPool = sm + L.total();
-  T* xch = sPool + L.padv(pd->npool);
-  int* flags = reinterpret_cast<int*>(xch + 2 * kSyncFused * nm * kBlock);
-  double* fh = reinterpret_cast<double*>(flags + 2 * kBlock) + kBlock;  // behind the gradient slots
-  const int fused_junk = (int)(reinterpret_cast<T*>(fh + 6) - sKDf);  // one junk slot per lane, in units of T
-
-  int* active_flag = reinterpret_cast<int*>(fh + 6 + kBlock);
-  double* ff = fh + 6 + kBlock + 2;                          // {rejected, rho, drho, inner_done} of the last iteration
-  T* sCand = reinterpret_cast<T*>(fh + 6 + kBlock + 2 + 16);  // [N+1][20][n+m] line-search candidates (128-byte phase kept)
-  // the speculative backward pass: second gain block + junk slots, hand-over values, assumed regularisation
-  T* sKD2 = sCand + (size_t)(N + 1) * kLineSearchLanes * nm;
-  double* fh2 = reinterpret_cast<double*>(sKD2 + N * R::KP + kBlock);
-  FwdSpec<T> spec{sKD2, N * R::KP, fh2, fh2 + 8, false};
-  T* const alpha_tab = reinterpret_cast<T*>(fh2 + 12);      // [20] step lengths of the line-search lanes (ilqr.hpp:544)
-  int* const sync_words = reinterpret_cast<int*>(fh2 + 12 + kLineSearchLanes);  // [kSyWords] FwdSync<true> (kSpecFree), E ahead
-  if (tid < kSyWords) sync_words[tid] = 0;  // (visible behind the staging barrier of the first iteration)
-  T* const sCost = reinterpret_cast<T*>(fh2 + 12 + kLineSearchLanes + kSyWords / 2);  // [N + 1] knot costs of the expansion step
-  T* const sCvalAhead = sCost + ((N + 2) & ~1);  // [total_rows] constraint values of the expansions computed ahead
-  if (tid < kLineSearchLanes) {
-    T alpha = T(1);
-    for (int i = 0; i < tid; ++i) alpha /= T(o.line_search_decrease_factor);
-    alpha_tab[tid] = alpha;
-  }
+  const FusedSmem<T> S(smem_raw, L, FusedLds<T>{L, N, nm, pd->npool});
+  FwdSpec<T> spec{S.sKD2, L.nKD, S.fh2, S.fh2 + kFhSpecRho, false};
+  fused_init_lds(S, o, tid);
+  const TailCtx<T> C{A, pd, o, tw, sweeps_out, S.ff, tid};
   bool adopt = false;
-  bool prev_rej = false;
-  double prev_rho = -1.0, prev_drho = -1.0;
+  StallWatch stall;
   int skipped = 0;
   int loops = 0;
   bool e_done = false;  // this iteration's expansions were computed beside phase 3 of the previous one
@@ -4027,242 +4638,35 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   if (tid < 32) g_stamp_acc[tid] = 0;
   int spec_iters = 0;
 #endif
-  // ---- twin workgroups (TwinCtl): the primary's bookkeeping, the twin's claim and clone ----
-  int tw_streak = 0;               // consecutive rejected iterations during which the inner solve went on
-  int tw_break_total = -1;         // it_total left by the last iteration that was NOT one of those
-  unsigned long long tw_ver = 0;   // thread 0: version of the newest snapshot
-  bool tw_closed = false;          // thread 0: nothing more is published, no successor is waited for
-  bool tw_shown = false;           // thread 0: the state word says "snapshot on display"
-  unsigned long long tw_succ = 0, tw_claim = 0;  // thread 0: the mailbox's successor word and the iteration the successor starts at, once seen
-  unsigned long long tw_peek = 0;  // thread 0: the mailbox's successor word, requested at the top of the iteration
-  bool tw_full = false;            // thread 0: this worker's line of claims has reached tw.depth -- nothing more to show or to look for
-  bool tw_confirmed = false;       // pool workgroup, thread 0: the predecessor has confirmed the state this worker entered with
-  int tw_loops0 = 0;               // pool workgroup: iterations the workers before it ran before the hand-over
-  auto stamp = [&](int which, long long value = -1) __attribute__((always_inline)) {
-    if (box && tw.debug) tw_store(box + kTwStamp + which, (unsigned long long)(value >= 0 ? value : wall_clock64()));
-  };
   const long long tstart_clock = tw.debug ? wall_clock64() : 0;
-  if (tid == 0 && !is_twin) stamp(kTsPStart);
-  // report of this workgroup to the host (longest chain of iterations, units processed): both ways out of the kernel
-  auto report = [&](int chain_loops, int units) __attribute__((always_inline)) {
-    if (sweeps_out && tid == 0) {
-      atomicMax(sweeps_out, chain_loops);      // longest chain of iterations of one instance inside this launch
-      atomicAdd(sweeps_out + 1, units);        // (instance, iteration) units processed by this launch
-      atomicMax(sweeps_out + 6, units + skipped);  // most iterations any ONE workgroup ran (a twin or its primary: their share)
-      // (a column of a split streak that the sweeps handed over sits behind the batch; the tail launch carries
-      //  the first shadow column in seg_lo and the columns per chain in seg_hi, which give the chain that owns it)
-      int chain = 0;
-      if (A.chain_size) {
-        chain = (SEG && A.seg_end && b_real >= A.B && A.seg_hi > 0 && b_real >= A.seg_lo) ? (b_real - A.seg_lo) / A.seg_hi : b_real / A.chain_size;
-        chain = chain < kMaxSweepChains - 1 ? chain : kMaxSweepChains - 1;
-      }
-      atomicMax(sweeps_out + 2, A.chain_base[chain] + chain_loops);  // ... counted from the first sweep of the solve
-      if (kSoft && sync_words[kSyErr] != 0) atomicMax(sweeps_out + 3, 1);  // a wave gave up waiting for a sequence word
-    }
-  };
-  if (is_twin) {
-    // ---- find work: the published segment with the most iterations left (late stragglers first, once CUs free up) ----
-    const int self = tw.cap + tslot;
-    if (wave == 0) {
-      const int cnt_slots = A.act_count ? *A.act_count : A.act_count_const;
-      const int nsl = cnt_slots < tw.cap ? cnt_slots : tw.cap;
-      const int nall = nsl + tw.npool;  // the primaries' mailboxes, then the pool's
-      int chosen = -1;
-      for (int tries = 0; tries < kTwinIdlePolls && chosen < 0; ++tries) {
-        int waiting = 0;  // workers that may still offer something: alive (or not yet dispatched), not full, long enough
-        int key = 0;      // (iterations left << 16 | 0xffff - position in the scan) of this lane's best candidate
-        for (int v0 = 0; v0 < nall; v0 += kBlock) {
-          const int v = v0 + lane;
-          bool open = false;
-          if (v < nall) {
-            const int id = v < nsl ? v : tw.cap + (v - nsl);
-            const unsigned long long st = id == self ? kTwsClosed : tw_load(tw.state + id);
-            open = (st & (kTwsClosed | kTwsFull)) == 0 && (v < nsl || (st & kTwsBusy) != 0);
-            if (open && (st & kTwsSnap) != 0) {
-              const unsigned long long* bx = tw.box + (size_t)id * kTwWords;
-              const int R = tw_remaining(o, tw_load(bx + kTwProg), (int)tw_load(bx + kTwEnd));
-              open = tw_claimable(R, tw.lag);
-              if (open && (st & kTwsLocked) == 0) {
-                const int k2 = ((R < 0x7fff ? R : 0x7fff) << 16) | (0xffff - (v & 0xffff));
-                key = k2 > key ? k2 : key;
-              }
-            }
-          }
-          waiting += __popcll(__ballot(open));
-        }
-        for (int d = 32; d > 0; d >>= 1) {
-          const int other = __shfl_xor(key, d);
-          key = other > key ? other : key;
-        }
-        int got = 0;
-        if (key != 0 && lane == 0) {
-          const int v = 0xffff - (key & 0xffff);
-          const int id = v < nsl ? v : tw.cap + (v - nsl);
-          unsigned long long* bx = tw.box + (size_t)id * kTwWords;
-          const unsigned long long st0 = kTwsSnap | (v < nsl ? 0ull : kTwsBusy);
-          if (tw_cas(tw.state + id, st0, st0 | kTwsLocked)) {
-            unsigned long long more = 0;  // bits for the publisher's state word
-            const unsigned long long ver = tw_load(bx + kTwSeq);
-            if (ver != 0) {
-              const unsigned long long* buf = bx + kTwSnap + 3 * (ver & 1);
-              const unsigned long long c0 = tw_load(buf), rb = tw_load(buf + 1), db = tw_load(buf + 2);
-              const unsigned long long pr = tw_load(bx + kTwProg), so = tw_load(bx + kTwSucc), inst = tw_load(bx + kTwInst);
-              const int end_in = (int)tw_load(bx + kTwEnd), gen = (int)((so >> 16) & 0xffffull);
-              const bool stable = tw_load(bx + kTwSeq) == ver;  // (the streak whose snapshot this is is still on)
-              const int in0 = (int)(c0 >> 32), tot0 = (int)(c0 & 0xffffffffull), in1 = (int)(pr >> 32), tot1 = (int)(pr & 0xffffffffull);
-              const int R = tw_remaining(o, pr, end_in);
-              if (gen >= tw.depth) more = kTwsFull;
-              if (stable && more == 0 && (so & kTwFrozen) == 0 && inst != 0 && in1 >= in0 && in1 - in0 == tot1 - tot0 && tw_claimable(R, tw.lag)) {
-                const int ahead = tw_keep(R, tw.lag);  // iterations the publisher keeps, counted from where it is
-                // the regularisation entering iteration `start`: every iteration since the snapshot runs its backward pass
-                // (DecreaseRegularization, ilqr.hpp:440) and rejects its line search (IncreaseRegularization, :550)
-                double rho = tw_dbl(rb), drho = tw_dbl(db);
-                for (int jj = 0; jj < in1 - in0 + ahead; ++jj) {
-                  decrease_reg(o, &rho, &drho);
-                  increase_reg(o, &rho, &drho);
-                }
-                const int nth = sweeps_out ? atomicAdd(sweeps_out + 5, 1) + 1 : 1;  // claims of this launch, at every level
-                if (tw.misclaim > 0 && nth % tw.misclaim == 0) rho = tw_dbl(tw_bits(rho) ^ 1ull);  // (test only: the joint must refuse)
-                const bool full = gen + 1 >= tw.depth;
-                unsigned long long* mine = tw.box + (size_t)self * kTwWords;
-                tw_store(mine + kTwClaimRho, tw_bits(rho));
-                tw_store(mine + kTwClaimDrho, tw_bits(drho));
-                tw_store(mine + kTwClaimSnap, (unsigned long long)(unsigned)tot0);
-                tw_store(mine + kTwClaim, ((unsigned long long)(unsigned)(in1 + ahead) << 32) | (unsigned long long)(unsigned)(tot1 + ahead));
-                tw_store(mine + kTwInst, inst);
-                tw_store(mine + kTwGen, (unsigned long long)(unsigned)(gen + 1));
-                tw_store(mine + kTwEnd, (unsigned long long)(unsigned)end_in);  // (the publisher's former end and successor: inherited)
-                tw_store(mine + kTwSucc, (so & kTwSuccId) | ((unsigned long long)(unsigned)(gen + 1) << 16));
-                tw_store(mine + kTwPred, (unsigned long long)(unsigned)(id + 1));
-                tw_store(tw.state + self, kTwsBusy | (full ? kTwsFull : 0ull));
-                tw_store(bx + kTwEnd, (unsigned long long)(unsigned)(in1 + ahead));
-                tw_order();
-                // the claim: the publisher looks at this word once per iteration; lost against a publisher that has reached a joint
-                if (tw_cas(bx + kTwSucc, so, (unsigned long long)(unsigned)(self + 1) | ((unsigned long long)(unsigned)(gen + 1) << 16))) {
-                  ff[8] = (double)(in1 + ahead);
-                  ff[9] = (double)(tot1 + ahead);
-                  ff[10] = rho;
-                  ff[11] = drho;
-                  ff[14] = (double)((int)inst - 1);
-                  if (full) more = kTwsFull;
-                  got = id + 1;
-                } else {
-                  tw_store(tw.state + self, 0ull);
-                  if (sweeps_out) atomicSub(sweeps_out + 5, 1);
-                }
-              }
-            }
-            if (more != 0) __hip_atomic_fetch_or(tw.state + id, more, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_and(tw.state + id, ~kTwsLocked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        got = __shfl(got, 0);
-        if (got > 0) chosen = got - 1;
-        if (chosen < 0) {
-          if (key == 0 && waiting == 0) break;  // nobody can publish a segment worth splitting any more
-          // (>= 25 us between two looks: r06_experiments.txt #4 measured what 300 fast pollers cost the workers)
-          for (int z = 0; z < (key == 0 ? 8 : 1); ++z) __builtin_amdgcn_s_sleep(127);
-        }
-      }
-      if (lane == 0) {
-        ff[15] = (double)chosen;
-        // (what the publisher's workgroup stored before it published -- the trajectory of its last accepted step, the
-        //  multipliers, or its clone of them -- may sit in another XCD's L2: its release is matched by this acquire)
-        if (chosen >= 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-    }
+  if (tid == 0 && !w.is_twin) w.stamp(tw, kTsPStart);
+  if (w.is_twin) {
+    if (wave == 0) tw_find_work(C, tw.cap + tslot, lane);
     __syncthreads();
-    const int src_id = (int)ff[15];
-    if (src_id < 0) return;
-    slot = self;
-    box = tw.box + (size_t)self * kTwWords;
-    b_real = (int)ff[14];
-    // (the column the publisher works on: the instance's own, or a pool workgroup's shadow column)
-    const int b_src = src_id < tw.cap ? instance_of_slot(A, src_id, 0) : tw.col0 + (src_id - tw.cap);
-    if (tid == 0) {
-      stamp(kTsTStart, tstart_clock);
-      stamp(kTsTGo);
-    }
-    // ---- clone the instance into the shadow column ----
-    const int bT = tw.col0 + tslot;
-    {
-      using R_ = Rec<T, M::n, M::m>;
-      for (int i = tid; i < (N + 1) * R_::nP; i += kThreads) {
-        const int k = i / R_::nP, e = i - k * R_::nP;
-        A.X[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::nP + e] = A.X[((size_t)(unsigned)k * Bp + (unsigned)b_src) * R_::nP + e];
-      }
-      for (int i = tid; i < N * R_::mP; i += kThreads) {
-        const int k = i / R_::mP, e = i - k * R_::mP;
-        A.U[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::mP + e] = A.U[((size_t)(unsigned)k * Bp + (unsigned)b_src) * R_::mP + e];
-      }
-      if (tid < R_::nP) A.x0[(size_t)bT * R_::nP + tid] = A.x0[(size_t)b_src * R_::nP + tid];
-      auto column = [&](T* arr, int rows) __attribute__((always_inline)) {
-        for (int r = tid; r < rows; r += kThreads) arr[(unsigned)r * Bp + (unsigned)bT] = arr[(unsigned)r * Bp + (unsigned)b_src];
-      };
-      column(A.costs, N + 1);
-      column(A.lam, pd->total_rows);
-      column(A.pen, pd->total_rows);
-      column(A.cval, pd->total_rows);
-      column(const_cast<T*>(A.ipool), pd->nslots);
-      if (tid == 0) {
-        // per-instance solver state: as the publisher left it ...
-        const double c0 = A.dV0[b_src], c1 = A.dV1[b_src], c2 = A.J0[b_src], c3 = A.initial_cost[b_src], c4 = A.cost_cur[b_src],
-                     c5 = A.dJ[b_src], c6 = A.grad[b_src], c7 = A.viol[b_src], c8 = A.penmax[b_src], c9 = A.alpha[b_src],
-                     c10 = A.z[b_src], c11 = A.reg_log[b_src];
-        const int i0 = A.status[b_src], i1 = A.status_al[b_src], i2 = A.it_outer[b_src], i3 = A.phase[b_src],
-                  i4 = A.need_init_cost[b_src];
-        A.dV0[bT] = c0; A.dV1[bT] = c1; A.J0[bT] = c2; A.initial_cost[bT] = c3; A.cost_cur[bT] = c4;
-        A.dJ[bT] = c5; A.grad[bT] = c6; A.viol[bT] = c7; A.penmax[bT] = c8; A.alpha[bT] = c9; A.z[bT] = c10; A.reg_log[bT] = c11;
-        A.status[bT] = i0; A.status_al[bT] = i1; A.it_outer[bT] = i2; A.phase[bT] = i3; A.need_init_cost[bT] = i4;
-        // ... but for what the rejected iterations up to `start` will have changed: counters, regularisation, and the
-        // previous cost, which every iteration of a streak sets to the (unchanged) current one (solver_stats.cpp:54-66)
-        if (SEG && A.seg_end) {
-          A.seg_end[bT] = kSegNoEnd;
-          A.seg_next[bT] = -1;
-          A.seg_flag[bT] = 0;
-          A.seg_streak[bT] = 2;
-        }
-        A.cost_prev[bT] = c4;
-        A.it_inner[bT] = (int)ff[8];
-        A.it_total[bT] = (int)ff[9];
-        A.rho_reg[bT] = ff[10];
-        A.drho[bT] = ff[11];
-      }
-    }
-    b = bT;
-    __syncthreads();
-    if (tid == 0) stamp(kTsTCloned);
-    if (tid == 0) {  // (refused already -- the publisher broke its streak or finished)
-      ff[12] = tw_load(box + kTwHand) == 0 ? 1.0 : 0.0;
-      if (ff[12] == 0.0) __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (ff[12] == 0.0) return;
+    if (!tw_enter_clone<T, M, SEG>(C, w, tslot, tstart_clock, kThreads, &b, &b_real)) return;
   }
   if (wave == 2 && lane == 0) {  // LDS mirrors of initial_cost / need_init_cost (read by this same lane: forward2_body)
-    ff[4] = A.initial_cost[b];
-    ff[5] = A.need_init_cost[b] ? 1.0 : 0.0;
+    S.ff[kFfInitCost] = A.initial_cost[b];
+    S.ff[kFfNeedInitCost] = A.need_init_cost[b] ? 1.0 : 0.0;
   }
   for (;;) {
     const long long st_it = ALTRO_STAMP_T0();
     // (a claim on this worker's segment: the word is requested here and looked at in the bookkeeping step behind the forward
     //  pass, so its round trip through the memory side runs beside the iteration -- a claim is seen one iteration late at the
     //  worst, and it names an iteration at least kTwinMinRemaining ahead)
-    if (box && tid == 0 && !tw_closed && !tw_full && (is_twin || tw_shown)) tw_peek = tw_load(box + kTwSucc);
+    if (w.box && tid == 0 && !w.closed && !w.full && (w.is_twin || w.shown)) w.peek = tw_load(w.box + kTwSucc);
     // ---- S: X, U, lambda, rho, parameters -> LDS (all threads).  Only once: phases 2 and 3 of the
     //      forward pass keep the LDS copies current from then on ----
     if (loops == 0) {
-      forward2_stage<T, M>(A, pd, L, smem_raw, sPool, 1, 0, tid, kThreads, kKdNone, true, -1, b);
+      forward2_stage<T, M>(A, pd, L, smem_raw, S.sPool, 1, 0, tid, kThreads, kKdNone, true, -1, b);
       __syncthreads();
     }
-    // (the two per-instance scalars the running-cost wave needs after E: requested now, their memory latency -- two
-    //  dependent round trips -- runs beside the expansions instead of behind them)
     // ---- E: expansions from the LDS block (unless they were computed AHEAD, beside phase 3 of the previous iteration:
-    //      see the end of the loop) ----
-    const CtxL<T> CE(A, b, sPool, sm + L.nX + L.nU + L.nKD + 2 * L.rowsP(), sm + L.nX + L.nU + L.nKD,
-                     sm + L.nX + L.nU + L.nKD + L.rowsP());
+    //      see below) ----
+    const CtxL<T> CE(A, b, S.sPool, S.sm + L.nX + L.nU + L.nKD + 2 * L.rowsP(), S.sm + L.nX + L.nU + L.nKD,
+                     S.sm + L.nX + L.nU + L.nKD + L.rowsP());
     if (!e_done) {
-      expansion_from_lds<T, M>(A, pd, CE, sm, sm + L.nX, sCost, b, tid, kThreads);
+      expansion_from_lds<T, M>(A, pd, CE, S.sm, S.sm + L.nX, S.sCost, b, tid, kThreads);
       if (adopt) ALTRO_STAMP_ADD(17 + wave, st_it);  // (17..20: each wave's own share of E)
       // drains the stores: the records are in L2 for the backward wave, the costs in LDS.  (A speculated iteration runs
       // no backward pass of its own, and the records it just rewrote are bit for bit the ones the fourth wave will read:
@@ -4274,29 +4678,15 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
 
     // speculate only in a streak of rejections (ff: phase 3 of the previous iteration, rewritten by this one's): a
     // converging instance accepts its steps, and a recursion beside its forward pass would only slow that down
-    const bool armed = SPEC != kSpecOff && loops > 0 && ff[0] != 0.0;
+    const bool armed = SPEC != kSpecOff && loops > 0 && S.ff[kFfRejected] != 0.0;
     if (SPEC && adopt) {
       const long long st_cp = ALTRO_STAMP_T0();
-      // ---- B was run ahead (fourth wave) during the previous forward pass: take its results ----
-      for (int i = tid; i < N * R::KP; i += kThreads) sKDf[i] = sKD2[i];
-      if (tid == 0) {
-        double h[6];
-        h[0] = fh2[1]; h[1] = fh2[2]; h[2] = fh2[4]; h[3] = fh2[5]; h[4] = fh2[6];  // (the fourth wave's hand-over values)
-        fh[1] = h[0];
-        fh[2] = h[1];
-        fh[4] = h[2];
-        fh[5] = h[3];
-        A.dV0[b] = h[0];
-        A.dV1[b] = h[1];
-        A.reg_log[b] = h[4];  // stats_.Log("reg", rho_)
-        A.rho_reg[b] = h[2];
-        A.drho[b] = h[3];
-      }
+      fused_adopt_spec(A, b, S.sKDf, S.sKD2, L.nKD, S.fh, S.fh2, tid, kThreads);
       if (wave == 0) ALTRO_STAMP_ADD(16, st_cp);
     } else if (wave == 0) {
       // ---- B ----
-      backward_mfma_body<T, M, false, true>(A, o, 0, lane, blockIdx.x, nullptr, sKDf, fused_junk, fh, 0.0, 0.0, nullptr, b, loops == 0);
-      // (its own LDS writes of fh[4], fh[5]: program order)
+      backward_mfma_body<T, M, false, true>(A, o, 0, lane, blockIdx.x, nullptr, S.sKDf, S.fused_junk, S.fh, 0.0, 0.0, nullptr, b, loops == 0);
+      // (its own LDS writes of fh[kFhRho], fh[kFhDrho]: program order)
     }
     // (the running cost J0 of the expansion step is summed by the auxiliary wave during the forward pass: aux_wave_run)
     if (SPEC && adopt) lds_barrier(); else __syncthreads();
@@ -4305,31 +4695,17 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     const bool st_adopted = adopt;
     // ---- F ----
     spec.armed = armed;
-    forward2_body<T, M, true, kSrcLds, CIRC, kSoft, false>(A, pdg, pd, o, mode, 0, 1, smem_raw, fh, active_flag, sCand, ff,
-                                                    kWave4 ? &spec : nullptr, alpha_tab,
-                                                    FwdSync<kSoft>{sync_words, loops * kFwdSeqStride}, sCost, fh,
-                                                    sync_words + kSyEAhead0, persistent ? (kWave4 ? 3 : 2) : 0, loops + 1, b);
+    forward2_body<T, M, true, kSrcLds, CIRC, kSoft, false>(A, pdg, pd, o, mode, 0, 1, smem_raw, S.fh, S.active_flag, S.sCand, S.ff,
+                                                    kWave4 ? &spec : nullptr, S.alpha_tab,
+                                                    FwdSync<kSoft>{S.sync_words, loops * kFwdSeqStride}, S.sCost, S.fh,
+                                                    S.sync_words + kSyEAhead0, persistent ? (kWave4 ? 3 : 2) : 0, loops + 1, b);
     ++loops;
     if (wave == 0 && st_adopted) ALTRO_STAMP_ADD(11, st_f);
     const long long st_x = ALTRO_STAMP_T0();
-    // ---- E AHEAD.  Phase 3 runs on the cost wave alone; the other waves left the forward pass behind barrier V and
-    //      would only wait for it.  If the line search rejected every trial, the trajectory and -- unless phase 3 ends
-    //      the inner solve -- the multipliers are what they were, so the next iteration's expansions can be computed
-    //      NOW, from the same LDS block, by the waves that are free: the same work the next iteration would do at its
-    //      top (nothing is skipped), 6 000 cycles earlier.  If phase 3 does end the inner solve (dual / penalty update)
-    //      or the instance, the result is discarded and E runs again as usual. ----
-    //      Two things keep the state exactly the reference's: the constraint values c_ that an expansion step stores
-    //      (ilqr.hpp:675 -> al_cost.hpp:264-274) go to an LDS scratch and are committed only when the expansions are the
-    //      next iteration's -- phase 3's dual update reads the c_ the line search left (quirk Q6) --, and the cost wave
-    //      holds its dual / penalty sweeps until these waves are through (forward_phase3), so that the records left in
-    //      memory when the instance finishes are this iteration's own.
-    if (persistent && wave != 1 && reinterpret_cast<const int*>(xch)[1] == 0) {
-      constexpr int kAhead = kWave4 ? 3 : 2;                     // waves 0, 2 (, 3)
-      const int wi = wave == 0 ? 0 : wave - 1;                   // 0, 1 (, 2)
-      const CtxL<T> CA(A, b, sPool, sm + L.nX + L.nU + L.nKD + 2 * L.rowsP(), sm + L.nX + L.nU + L.nKD,
-                       sm + L.nX + L.nU + L.nKD + L.rowsP(), sCvalAhead);
-      expansion_from_lds<T, M>(A, pd, CA, sm, sm + L.nX, sCost, b, wi * kBlock + lane, kAhead * kBlock);
-      if (lane == 0) FwdSync<true>::post(sync_words + kSyEAhead0 + wi, loops);  // (loops: already this iteration's number + 1)
+    // ---- E AHEAD: where the selection says that every trial was rejected, the waves that phase 3 leaves free compute the
+    //      next iteration's expansions now ----
+    if (persistent && wave != 1 && reinterpret_cast<const int*>(S.xch)[1] == 0) {
+      fused_expand_ahead<T, M, kWave4>(A, pd, L, S.sm, S.sPool, S.sCost, S.sCvalAhead, S.sync_words, b, wave, lane, loops);
       if (wave == 0 && st_adopted) ALTRO_STAMP_ADD(21, st_x);
     }
     // (phase 2's stores were drained by barrier V; what is in flight now are the scalars of phase 3, which only a
@@ -4342,334 +4718,72 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
       if (wave == 0) ALTRO_STAMP_ADD(14, st_it);
     }
 #endif
-    if (!persistent || *active_flag == 0) break;
+    if (!persistent || *S.active_flag == 0) break;
     // (the expansions ahead are the next iteration's iff the step was rejected and the inner solve goes on: then their
     //  constraint values become c_, as the expansion step at the top of the loop would have stored them)
-    e_done = ff[0] != 0.0 && ff[3] == 0.0;
+    e_done = S.ff[kFfRejected] != 0.0 && S.ff[kFfInnerDone] == 0.0;
     if (e_done)
-      for (int r = tid; r < pd->total_rows; r += kThreads) A.cval[(unsigned)r * Bp + (unsigned)b] = sCvalAhead[r];
+      for (int r = tid; r < pd->total_rows; r += kThreads) A.cval[(unsigned)r * Bp + (unsigned)b] = S.sCvalAhead[r];
     // the speculation holds if the line search rejected every trial, the inner solve goes on (no dual / penalty
-    // update: ff[3]) and phase 3 set exactly the regularisation the speculative pass assumed
-    if (kWave4) adopt = armed && fh2[7] != 0.0 && ff[0] != 0.0 && ff[3] == 0.0 && ff[1] == fh2[8] && ff[2] == fh2[9];
-    if (o.fast_forward_stalls) {
-      // OPT-IN, off by default.  A rejected line search leaves the trajectory, the multipliers and -- once
-      // the regularisation has settled into its increase/decrease cycle -- the whole state of the instance
-      // unchanged, so the next iteration recomputes exactly the same rejection: the reference (and the default
-      // path here) repeats it until max_iterations_inner.  Two consecutive rejections with bit-identical
-      // regularisation state prove the fixed point; the identical iterations in between are then only
-      // counted (and logged), and the last one is executed normally so that every status decision is taken
-      // by the usual code.
-      const bool rej = ff[0] != 0.0 && ff[3] == 0.0;
-      const bool stalled = rej && prev_rej && ff[1] == prev_rho && ff[2] == prev_drho;
-      prev_rej = rej;
-      prev_rho = ff[1];
-      prev_drho = ff[2];
-      if (stalled && tid == 0) {
-        const int it_in = A.it_inner[b], it_tot = A.it_total[b];
-        int k = o.max_iterations_inner - 1 - it_in;
-        const int k2 = o.max_iterations_total - 1 - it_tot;
-        k = k < k2 ? k : k2;
-        if (k > 0) {
-          A.it_inner[b] = it_in + k;
-          A.it_total[b] = it_tot + k;
-          for (int j = 0; j < k; ++j) hist_push(A, b);
-          skipped += k;  // (kept apart from `loops`, which must stay wave-uniform)
-        }
-        // the cost wave of the next iteration reads these counters from global memory (load_inst_pre): another wave, and
-        // the barrier below may be LDS-only -- drain this wave's stores first (with the expansions computed ahead there
-        // is no expansion phase in between any more to hide the race)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    }
-    // ---- segments of rejection streaks (DevArrays::seg_*) that the batched sweeps handed over: a column with a successor
-    //      verifies the successor's assumptions at its segment's end and retires, or cancels the chain; a cancelled column
-    //      leaves.  (The batched kernels do this inside forward_phase3; here it sits beside the twins' bookkeeping: compiled
-    //      into phase 3 it cost this kernel's register allocation 560 B of scratch per lane.)  The iteration that just ended
-    //      is complete either way; a column that leaves does so through the loop's normal exit. ----
-    bool seg_leave = false;
+    // update) and phase 3 set exactly the regularisation the speculative pass assumed
+    if (kWave4)
+      adopt = armed && S.fh2[kFhSpecOk] != 0.0 && S.ff[kFfRejected] != 0.0 && S.ff[kFfInnerDone] == 0.0 && S.ff[kFfRho] == S.fh2[kFhSpecRho] &&
+              S.ff[kFfDrho] == S.fh2[kFhSpecDrho];
+    if (o.fast_forward_stalls) skipped += fused_fast_forward(C, stall, b);
     if (SEG && A.seg_end) {
-      if (tid == 0) {
-        double leave = 0.0;
-        const int flag = A.seg_flag[b];
-        const int nxt = A.seg_next[b];
-        const bool rc = ff[0] != 0.0 && ff[3] == 0.0;  // every trial rejected, and the inner solve goes on
-        if (flag & kSegCancelled) {
-          leave = 1.0;  // a predecessor did not arrive where this column assumed it would: its work is void
-        } else if (nxt >= 0) {
-          bool cancel = !rc;
-          if (rc && (int)ff[6] == A.seg_end[b]) {
-            const bool same = A.seg_tot0[nxt] == (int)ff[7] && tw_bits(A.seg_rho0[nxt]) == tw_bits(ff[1]) &&
-                              tw_bits(A.seg_drho0[nxt]) == tw_bits(ff[2]) &&
-                              (__hip_atomic_load(A.seg_flag + nxt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kSegCancelled) == 0;
-            if (same) {
-              A.seg_flag[b] = flag | kSegRetired;  // (the next column owns the instance from here: k_seg_fixup follows the chain)
-              leave = 1.0;
-            } else {
-              cancel = true;
-            }
-          }
-          if (cancel) {
-            int sgd = nxt;
-            for (int guard = 0; sgd >= 0 && guard < 256; ++guard) {
-              atomicOr(A.seg_flag + sgd, kSegCancelled);
-              sgd = A.seg_next[sgd];
-            }
-            A.seg_next[b] = -1;
-            A.seg_end[b] = kSegNoEnd;
-          }
-        }
-        if (leave != 0.0) A.phase[b] = 0;
-        ff[12] = leave;
-      }
+      if (tid == 0) fused_seg_joint(C, b);
       if (SPEC && adopt) lds_barrier(); else __syncthreads();
-      seg_leave = ff[12] != 0.0;
-      if (seg_leave) break;
+      if (S.ff[kFfSegLeave] != 0.0) break;
     }
-    // ---- twin workgroups (TwinCtl).  Every worker: show where it is while a streak is on, see a claim on the rest of its
-    //      segment, answer its successor at the joint.  Pool workgroups: a look at their own verdict now and then. ----
-    if (box) {
-      const bool rc = ff[0] != 0.0 && ff[3] == 0.0;  // every trial rejected, and the inner solve goes on
-      tw_streak = rc ? tw_streak + 1 : 0;
-      if (!rc) tw_break_total = (int)ff[7];
-      if (tid == 0) {
-        double act = 0.0;
-        if (is_twin) {
-          if (loops == 1) stamp(kTsTFirst);
-          if (!tw_confirmed && (loops & 7) == 0 && tw_load(box + kTwHand) >= kTwRefused) act = 1.0;
-        }
-        if (act == 0.0 && !tw_closed && (is_twin || tw_streak >= 2 || tw_shown)) {
-          const int it_in = (int)ff[6], it_tot = (int)ff[7];  // the counters entering the next iteration
-          // (a column whose streak the batched sweeps have split into segments ends at its segment's end: not claimable)
-          if (rc && tw_streak >= 2 && !tw_full && (!SEG || !A.seg_end || A.seg_next[b] < 0)) {
-            const unsigned long long cnt = ((unsigned long long)(unsigned)it_in << 32) | (unsigned long long)(unsigned)it_tot;
-            tw_store(box + kTwProg, cnt);  // (all an iteration of a published streak costs: one relaxed store, nothing waited for)
-            if (!tw_shown) {
-              // once per streak: the state a claimer steps the regularisation rule from
-              ++tw_ver;
-              unsigned long long* buf = box + kTwSnap + 3 * (tw_ver & 1);
-              tw_store(buf, cnt);
-              tw_store(buf + 1, tw_bits(ff[1]));
-              tw_store(buf + 2, tw_bits(ff[2]));
-              tw_store(box + kTwInst, (unsigned long long)(unsigned)(b_real + 1));
-              // whatever the last accepted step and the first rejected iteration stored (trajectory, multipliers, cost_prev =
-              // cost_cur; a pool workgroup: its clone of them) leaves this XCD's L2 before a claimer is told that it may read it
-              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-              tw_order();
-              tw_store(box + kTwSeq, tw_ver);
-              tw_order();
-              __hip_atomic_fetch_or(tw.state + slot, kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              tw_shown = true;
-              stamp(kTsPSnap);
-              stamp(kTsPLoopsAtSnap, loops);
-            }
-          }
-          // (a streak that broke: the snapshot on display describes a state that no longer exists -- a late claimer would
-          //  claim on it and be refused; hide it until the next streak publishes)
-          if (!rc && tw_shown) {
-            __hip_atomic_fetch_and(tw.state + slot, ~kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tw_store(box + kTwSeq, 0ull);
-            tw_shown = false;
-          }
-          // a claim on the second half of what is left of this segment: the newest claimer is the successor (it has
-          // inherited the former one); its words were stored before this one
-          const unsigned long long sc = tw_peek;
-          if (sc != tw_succ && (sc & kTwFrozen) == 0 && (sc & kTwSuccId) <= (unsigned long long)(2 * tw.cap)) {
-            tw_succ = sc;
-            tw_full = (int)((sc >> 16) & 0xffffull) >= tw.depth;
-            if ((sc & kTwSuccId) != 0) {
-              tw_claim = tw_load(tw.box + (size_t)((sc & kTwSuccId) - 1) * kTwWords + kTwClaim);
-              stamp(kTsPClaim);
-            }
-          }
-          if ((tw_succ & kTwSuccId) != 0) {
-            const unsigned long long* sb = tw.box + (size_t)((tw_succ & kTwSuccId) - 1) * kTwWords;
-            const int s_in = (int)(tw_claim >> 32), s_tot = (int)(tw_claim & 0xffffffffull);
-            bool refuse = !rc || it_in > s_in;
-            int why = !rc ? 1 : (it_in > s_in ? 2 : 0);
-            if (!refuse && it_in == s_in) {
-              // THE JOINT: the successor's assumptions about the state entering this iteration, bit for bit -- and no
-              // iteration since its snapshot that was anything but a rejected one
-              const unsigned long long c_rho = tw_load(sb + kTwClaimRho), c_drho = tw_load(sb + kTwClaimDrho);
-              const int c_snap = (int)tw_load(sb + kTwClaimSnap);
-              const bool same = it_tot == s_tot && tw_bits(ff[1]) == c_rho && tw_bits(ff[2]) == c_drho && tw_break_total < c_snap;
-              why = it_tot != s_tot ? 3 : (tw_bits(ff[1]) != c_rho ? 4 : (tw_bits(ff[2]) != c_drho ? 5 : 6));
-              // (no claim from here on; lost against a claimer that came too late to be served: it is refused with the rest)
-              if (same && tw_cas(box + kTwSucc, tw_succ, tw_succ | kTwFrozen)) act = 2.0; else refuse = true;
-              if (same && refuse) why = 2;
-            }
-            if (refuse) {
-              tw_store(box + kTwWhy, (unsigned long long)why | ((unsigned long long)(unsigned)it_in << 8) | ((unsigned long long)(unsigned)s_in << 24));
-              tw_cancel_chain(tw, box);  // this worker goes on alone with the state it holds
-              __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              tw_closed = true;
-            }
-          }
-        }
-        ff[13] = act;
-      }
-    }
+    if (w.box) tw_bookkeeping<T, SEG>(C, w, loops, b, b_real);
     // (waves of a workgroup share the CU's vector L1, which stores write through and keep coherent,
     // so what this iteration wrote -- trajectory, multipliers, records -- is what the next one reads)
     // everyone has read the flag before phase 3 of the next iteration rewrites it; without a speculated backward pass
     // the next iteration reads this one's scalars from global memory: drain the stores
     if (SPEC && adopt) lds_barrier(); else __syncthreads();
-    if (box) {
-      const double act = ff[13];
+    if (w.box) {
+      const double act = S.ff[kFfTwinAction];
       if (act == 1.0) {  // pool workgroup: refused (the refusing worker has told the chain) -- nothing of the clone is visible outside its column
-        if (tid == 0) __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) w.close(tw);
         return;
       }
       if (act == 2.0) {
-        // HAND-OVER.  A pool workgroup answers only once its own predecessor has confirmed it: then every joint before this
-        // one holds.  Everything this workgroup has stored leaves its L2 before the successor -- whose chain will end in a
-        // copy over the instance's column -- is told so: the workgroups may sit on different XCDs, whose L2s write back on their own.
-        __syncthreads();
-        if (tid == 0) {
-          unsigned long long* sb = tw.box + (size_t)((tw_succ & kTwSuccId) - 1) * kTwWords;
-          double res = 3.0;  // 3: handed over, leave; 1: this worker's own claim was refused, leave; 0: go on alone
-          if (is_twin && !tw_confirmed) {
-            unsigned long long h = 0;
-            for (int tries = 0; tries < kTwinHandPolls && (h = tw_load(box + kTwHand)) == 0; ++tries) __builtin_amdgcn_s_sleep(32);
-            if (h == 0) h = tw_cas(box + kTwHand, 0ull, kTwRevoked) ? kTwRevoked : tw_load(box + kTwHand);
-            if (h == kTwOk) {
-              tw_loops0 = (int)(unsigned)tw_load(box + kTwHandLoops);
-              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-              tw_confirmed = true;
-              if (sweeps_out) atomicAdd(sweeps_out + 4, 1);  // confirmed joints of this launch
-              stamp(kTsTVerdict);
-            } else {
-              res = 1.0;
-            }
-          }
-          if (res == 3.0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            tw_store(sb + kTwHandLoops, (unsigned long long)(unsigned)(tw_loops0 + loops));
-            tw_order();
-            res = tw_cas(sb + kTwHand, 0ull, kTwOk) ? 3.0 : 0.0;  // (lost against a successor that gave up: go on alone)
-          } else {
-            tw_cancel_chain(tw, box);
-          }
-          __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          tw_closed = true;
-          stamp(kTsPHand);
-          ff[13] = res;
-          ff[14] = (double)tw_loops0;
-        }
-        __syncthreads();
-        if (ff[13] == 3.0) {
-          report((int)ff[14] + loops + skipped, loops);
+        const double res = tw_hand_over(C, w, loops);
+        if (res == 3.0) {
+          fused_report<T, SEG, kSoft>(C, b_real, S.sync_words, (int)S.ff[kFfLoopsBefore] + loops + skipped, loops, skipped);
           return;  // the successor's chain owns the instance: its last copy-back is the instance's state
         }
-        if (ff[13] == 1.0) return;
+        if (res == 1.0) return;
       }
     }
   }
-  // ---- the worker of the final segment commits: its predecessor's verdict (every joint before that one is confirmed
-  //      by then), then the shadow column over the instance's own ----
-  if (is_twin) {
-    if (tid == 0) {
-      stamp(kTsTDone);
-      stamp(kTsTLoops, loops);
-      unsigned long long h = tw_confirmed ? kTwOk : 0ull;
-      if (!tw_confirmed) {
-        for (int tries = 0; tries < kTwinHandPolls && (h = tw_load(box + kTwHand)) == 0; ++tries) __builtin_amdgcn_s_sleep(32);
-        if (h == 0) h = tw_cas(box + kTwHand, 0ull, kTwRevoked) ? kTwRevoked : tw_load(box + kTwHand);
-        if (h == kTwOk) {
-          tw_loops0 = (int)(unsigned)tw_load(box + kTwHandLoops);
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          if (sweeps_out) atomicAdd(sweeps_out + 4, 1);  // confirmed joints of this launch
-          stamp(kTsTVerdict);
-        }
-      }
-      // (the instance finished inside a segment that is not the final one: what comes after it assumed otherwise)
-      if (!tw_closed) tw_cancel_chain(tw, box);
-      __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ff[14] = (double)tw_loops0;
-      ff[13] = h == kTwOk ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    if (ff[13] == 0.0) return;
-    tw_loops0 = (int)ff[14];
-    {
-      using R_ = Rec<T, M::n, M::m>;
-      using RS_ = rec_scalar_t<T, M>;
-      using RR_ = Rec<RS_, M::n, M::m>;
-      const int bT = b;
-      for (int i = tid; i < (N + 1) * R_::nP; i += kThreads) {
-        const int k = i / R_::nP, e = i - k * R_::nP;
-        A.X[((size_t)(unsigned)k * Bp + (unsigned)b_real) * R_::nP + e] = A.X[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::nP + e];
-      }
-      for (int i = tid; i < N * R_::mP; i += kThreads) {
-        const int k = i / R_::mP, e = i - k * R_::mP;
-        A.U[((size_t)(unsigned)k * Bp + (unsigned)b_real) * R_::mP + e] = A.U[((size_t)(unsigned)k * Bp + (unsigned)bT) * R_::mP + e];
-      }
-      RS_* const E = (RS_*)A.EXP;
-      for (int i = tid; i < (N + 1) * RR_::EP; i += kThreads) {
-        const int k = i / RR_::EP, e = i - k * RR_::EP;
-        E[((size_t)(unsigned)k * Bp + (unsigned)b_real) * RR_::EP + e] = E[((size_t)(unsigned)k * Bp + (unsigned)bT) * RR_::EP + e];
-      }
-      auto column = [&](T* arr, int rows) __attribute__((always_inline)) {
-        for (int r = tid; r < rows; r += kThreads) arr[(unsigned)r * Bp + (unsigned)b_real] = arr[(unsigned)r * Bp + (unsigned)bT];
-      };
-      column(A.costs, N + 1);
-      column(A.lam, pd->total_rows);
-      column(A.pen, pd->total_rows);
-      column(A.cval, pd->total_rows);
-      if (tid == 0) {
-        const double c0 = A.rho_reg[bT], c1 = A.drho[bT], c2 = A.dV0[bT], c3 = A.dV1[bT], c4 = A.J0[bT], c5 = A.initial_cost[bT],
-                     c6 = A.cost_cur[bT], c7 = A.cost_prev[bT], c8 = A.dJ[bT], c9 = A.grad[bT], c10 = A.viol[bT], c11 = A.penmax[bT],
-                     c12 = A.alpha[bT], c13 = A.z[bT], c14 = A.reg_log[bT];
-        const int i0 = A.status[bT], i1 = A.status_al[bT], i2 = A.it_inner[bT], i3 = A.it_outer[bT], i4 = A.it_total[bT],
-                  i5 = A.phase[bT], i6 = A.need_init_cost[bT];
-        A.rho_reg[b_real] = c0; A.drho[b_real] = c1; A.dV0[b_real] = c2; A.dV1[b_real] = c3; A.J0[b_real] = c4;
-        A.initial_cost[b_real] = c5; A.cost_cur[b_real] = c6; A.cost_prev[b_real] = c7; A.dJ[b_real] = c8; A.grad[b_real] = c9;
-        A.viol[b_real] = c10; A.penmax[b_real] = c11; A.alpha[b_real] = c12; A.z[b_real] = c13; A.reg_log[b_real] = c14;
-        A.status[b_real] = i0; A.status_al[b_real] = i1; A.it_inner[b_real] = i2; A.it_outer[b_real] = i3; A.it_total[b_real] = i4;
-        A.phase[b_real] = i5; A.need_init_cost[b_real] = i6;
-      }
-    }
+  if (w.is_twin) {
+    if (!tw_commit<T, M>(C, w, loops, b, b_real, kThreads)) return;
     b = b_real;  // (the gains below go to the instance's own records)
-    if (tid == 0) stamp(kTsTCommit);
-  } else if (box && tid == 0 && !tw_closed) {
-    tw_cancel_chain(tw, box);  // the instance is finished: a successor's work is void, and the pool need not wait for a streak
-    __hip_atomic_fetch_or(tw.state + slot, kTwsClosed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    stamp(kTsPEnd);
+  } else if (w.box && tid == 0 && !w.closed) {
+    tw_cancel_chain(tw, w.box);  // the instance is finished: a successor's work is void, and the pool need not wait for a streak
+    w.close(tw);
+    w.stamp(tw, kTsPEnd);
   }
 #ifdef ALTRO_STAMPS
   __syncthreads();
-  if (tid == 0 && spec_iters > 60 && loops > 100) {  // (the stragglers: a few dozen lines)
-    const double c = 1.0 / spec_iters;
-    const double ca = 1.0 / loops;  // the per-wave stamps run in every iteration
-    printf("STAMPS (instance %d): %d iterations, %d adopted (speculated); per adopted iteration, shader-clock cycles:\n"
-           "  E %.0f | take-over %.0f | forward pass (wave 0) %.0f | barrier behind F (wave 0 waits) %.0f | whole iteration %.0f\n"
-           "  rollout wave: knot loop %.0f, wait A+S %.0f, phase 2 %.0f\n"
-           "  cost wave: knot loop + wait A %.0f, selection %.0f, phase 2 + wait V %.0f, phase 3 %.0f\n"
-           "  auxiliary wave: knot loop %.0f | fourth wave: speculative backward pass %.0f (only passes of armed iterations)\n"
-           "  take-over: copy + hand-over (wave 0) %.0f, running cost (wave 1) %.0f | E alone, waves 0..3: %.0f %.0f %.0f %.0f | E ahead (wave 0) %.0f\n",
-           b, loops, spec_iters, c * g_stamp_acc[9], c * g_stamp_acc[10], c * g_stamp_acc[11], c * g_stamp_acc[12], c * g_stamp_acc[14],
-           ca * g_stamp_acc[0], ca * g_stamp_acc[1], ca * g_stamp_acc[2], ca * g_stamp_acc[3], ca * g_stamp_acc[4], ca * g_stamp_acc[5],
-           ca * g_stamp_acc[6], ca * g_stamp_acc[7], c * g_stamp_acc[8], c * g_stamp_acc[16], c * g_stamp_acc[15],
-           c * g_stamp_acc[17], c * g_stamp_acc[18], c * g_stamp_acc[19], c * g_stamp_acc[20], c * g_stamp_acc[21]);
-  }
+  if (tid == 0 && spec_iters > 60 && loops > 100) fused_stamp_summary(b, loops, spec_iters);
 #endif
   // the gains for the getters (nothing inside the sweep reads them from global memory)
   for (int i = tid; i < N * R::KP; i += kThreads) {
     const int k = i / R::KP, e = i - k * R::KP;
     using RS = rec_scalar_t<T, M>;
-    if (e < (Rec<RS, M::n, M::m>::KP)) RECP((RS*)A.KD, k, (Rec<RS, M::n, M::m>::KP))[e] = (RS)sKDf[i];
+    if (e < (Rec<RS, M::n, M::m>::KP)) RECP((RS*)A.KD, k, (Rec<RS, M::n, M::m>::KP))[e] = (RS)S.sKDf[i];
   }
-  report(tw_loops0 + loops + skipped, loops);
+  fused_report<T, SEG, kSoft>(C, b_real, S.sync_words, w.loops0 + loops + skipped, loops, skipped);
 }
 
 
 // The last valid column of every chain of segments (DevArrays::seg_*) over the instance's own: one workgroup per instance,
 // follows seg_next while the column it stands on has retired (= its successor started from exactly the state it arrived
-// with), then copies that column's trajectory, multipliers, constraint values, records and solver state.
+// with), then copies that column's trajectory, multipliers, constraint values, records and solver state (kColSegFixup).
 template <class T, class M>
 __global__ __launch_bounds__(kBlock) void k_seg_fixup(DevArrays<T> A, const ProblemDesc* __restrict__ pd) {
-  using R = Rec<T, M::n, M::m>;
-  using RS = rec_scalar_t<T, M>;
-  using RR = Rec<RS, M::n, M::m>;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= A.B) return;
   int cur = b;
@@ -4679,41 +4793,7 @@ __global__ __launch_bounds__(kBlock) void k_seg_fixup(DevArrays<T> A, const Prob
     cur = nx;
   }
   if (cur == b) return;
-  const unsigned Bp = A.Bp, src = (unsigned)cur, dst = (unsigned)b;
-  const int N = A.N;
-  for (int i = tid; i < (N + 1) * R::nP; i += kBlock) {
-    const int k = i / R::nP, e = i - k * R::nP;
-    A.X[((size_t)(unsigned)k * Bp + dst) * R::nP + e] = A.X[((size_t)(unsigned)k * Bp + src) * R::nP + e];
-  }
-  for (int i = tid; i < N * R::mP; i += kBlock) {
-    const int k = i / R::mP, e = i - k * R::mP;
-    A.U[((size_t)(unsigned)k * Bp + dst) * R::mP + e] = A.U[((size_t)(unsigned)k * Bp + src) * R::mP + e];
-  }
-  RS* const E = (RS*)A.EXP;
-  for (int i = tid; i < (N + 1) * RR::EP; i += kBlock) {
-    const int k = i / RR::EP, e = i - k * RR::EP;
-    E[((size_t)(unsigned)k * Bp + dst) * RR::EP + e] = E[((size_t)(unsigned)k * Bp + src) * RR::EP + e];
-  }
-  RS* const G = (RS*)A.KD;
-  for (int i = tid; i < N * RR::KP; i += kBlock) {
-    const int k = i / RR::KP, e = i - k * RR::KP;
-    G[((size_t)(unsigned)k * Bp + dst) * RR::KP + e] = G[((size_t)(unsigned)k * Bp + src) * RR::KP + e];
-  }
-  for (int r = tid; r <= N; r += kBlock) A.costs[(unsigned)r * Bp + dst] = A.costs[(unsigned)r * Bp + src];
-  for (int r = tid; r < pd->total_rows; r += kBlock) {
-    A.lam[(unsigned)r * Bp + dst] = A.lam[(unsigned)r * Bp + src];
-    A.pen[(unsigned)r * Bp + dst] = A.pen[(unsigned)r * Bp + src];
-    A.cval[(unsigned)r * Bp + dst] = A.cval[(unsigned)r * Bp + src];
-  }
-  if (tid == 0) {
-    A.rho_reg[dst] = A.rho_reg[src]; A.drho[dst] = A.drho[src]; A.dV0[dst] = A.dV0[src]; A.dV1[dst] = A.dV1[src]; A.J0[dst] = A.J0[src];
-    A.initial_cost[dst] = A.initial_cost[src]; A.cost_cur[dst] = A.cost_cur[src]; A.cost_prev[dst] = A.cost_prev[src];
-    A.dJ[dst] = A.dJ[src]; A.grad[dst] = A.grad[src]; A.viol[dst] = A.viol[src]; A.penmax[dst] = A.penmax[src];
-    A.alpha[dst] = A.alpha[src]; A.z[dst] = A.z[src]; A.reg_log[dst] = A.reg_log[src];
-    A.status[dst] = A.status[src]; A.status_al[dst] = A.status_al[src]; A.it_inner[dst] = A.it_inner[src];
-    A.it_outer[dst] = A.it_outer[src]; A.it_total[dst] = A.it_total[src]; A.phase[dst] = A.phase[src];
-    A.need_init_cost[dst] = A.need_init_cost[src];
-  }
+  copy_column<T, M>(A, pd, (unsigned)cur, (unsigned)b, kColSegFixup, tid, kBlock);
 }
 
 // -------------------------------------------------------------------------------------------------

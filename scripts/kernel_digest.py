@@ -16,21 +16,25 @@ import sys
 READELF = "/opt/rocm/llvm/bin/llvm-readelf"
 
 
-def digest(path):
+def symbols(path):
+    """(name, size, bytes) of every FUNC / OBJECT entry of the code object's symbol tables"""
     data = open(path, "rb").read()
     out = subprocess.check_output([READELF, "-sW", "-S", path], text=True)
     sections = {}  # index -> (address, file offset, type)
     for m in re.finditer(r"^\s*\[\s*(\d+)\]\s+(\S*)\s+(\S+)\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", out, re.M):
         sections[int(m.group(1))] = (int(m.group(4), 16), int(m.group(5), 16), m.group(3))
-    lines = []
+    syms = []
     for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+(FUNC|OBJECT)\s+\S+\s+\S+\s+(\d+)\s+(\S+)", out, re.M):
         value, size, ndx, name = int(m.group(1), 16), int(m.group(2)), int(m.group(4)), m.group(5)
         if name.startswith("__hip_cuid_"):
             continue
         addr, off, kind = sections[ndx]
-        body = b"" if kind == "NOBITS" else data[off + value - addr:off + value - addr + size]
-        lines.append("%s %d %s" % (name, size, hashlib.sha256(body).hexdigest()))
-    return sorted(lines)
+        syms.append((name, size, b"" if kind == "NOBITS" else data[off + value - addr:off + value - addr + size]))
+    return syms
+
+
+def digest(path):
+    return sorted("%s %d %s" % (name, size, hashlib.sha256(body).hexdigest()) for name, size, body in symbols(path))
 
 
 if __name__ == "__main__":
