@@ -70,6 +70,16 @@ STATS_DTYPE = np.dtype([(name, np.int32 if t is C.c_int else np.float64) for nam
 assert STATS_DTYPE.itemsize == C.sizeof(Stats)
 
 
+class TrackStats(C.Structure):
+    """altro_track_stats (include/altro_mpc.h): one per (instance, sample) of mpc_track."""
+    _fields_ = [("status", C.c_int), ("steps_done", C.c_int), ("cost", C.c_double), ("violation", C.c_double),
+                ("max_dx", C.c_double), ("max_du", C.c_double)]
+
+
+TRACK_STATS_DTYPE = np.dtype([(name, np.int32 if t is C.c_int else np.float64) for name, t in TrackStats._fields_])
+assert TRACK_STATS_DTYPE.itemsize == C.sizeof(TrackStats) == 40
+
+
 class Timing(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("init_ms", C.c_double), ("expansions_ms", C.c_double),
                 ("backward_pass_ms", C.c_double), ("forward_pass_ms", C.c_double), ("fused_ms", C.c_double),
@@ -514,6 +524,56 @@ class BatchSolver:
         self._call("mpc_run", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(X), _dp(U),
                    it.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int)))
         return dict(X_cl=X, U_cl=U, iterations=it, status=st)
+
+    def _track_bounds(self, u_lo, u_hi):
+        u_lo, u_hi = _f64(u_lo), _f64(u_hi)
+        for name, a in (("u_lo", u_lo), ("u_hi", u_hi)):
+            if a is not None and a.shape != (self.m,):
+                raise ValueError(f"{name} must have shape ({self.m},)")
+        return u_lo, u_hi
+
+    def mpc_track(self, steps, samples=1, dx0=None, w=None, u_lo=None, u_hi=None, log=True):
+        """Simulate every (instance, sample) for ``steps`` knots under the plan's feedback policy u = Ubar + K (x - Xbar) on
+        the device (altro_mpc_track): x_0 = x0 + ``dx0`` ([B][S][n]), x+ = f(x, u) + ``w`` ([B][S][steps][n]), controls
+        clipped to ``u_lo`` / ``u_hi`` ([m], both or neither).  Changes nothing on the handle.  Returns
+        dict(stats [B][S] of TRACK_STATS_DTYPE, and with ``log`` X_cl [B][S][steps+1][n], U_cl [B][S][steps][m])."""
+        S, K = max(int(samples), 0), max(int(steps), 0)
+        dx0, w = _f64(dx0), _f64(w)
+        u_lo, u_hi = self._track_bounds(u_lo, u_hi)
+        if dx0 is not None and dx0.shape != (self.batch, S, self.n):
+            raise ValueError(f"dx0 must have shape ({self.batch}, {S}, {self.n})")
+        if w is not None and w.shape != (self.batch, S, K, self.n):
+            raise ValueError(f"w must have shape ({self.batch}, {S}, {K}, {self.n})")
+        stats = np.zeros((self.batch, S), dtype=TRACK_STATS_DTYPE)
+        X = np.zeros((self.batch, S, K + 1, self.n)) if log else None
+        U = np.zeros((self.batch, S, K, self.m)) if log else None
+        self._call("mpc_track", C.c_int(steps), C.c_int(samples), _dp(dx0), _dp(w), _dp(u_lo), _dp(u_hi), _dp(X), _dp(U),
+                   stats.ctypes.data_as(C.POINTER(TrackStats)))
+        return dict(stats=stats, X_cl=X, U_cl=U) if log else dict(stats=stats)
+
+    def mpc_track_device(self, steps, samples=1, dx0_ptr=0, w_ptr=0, u_lo_ptr=0, u_hi_ptr=0, x_ptr=0, u_ptr=0, stats_ptr=0):
+        """mpc_track with every array in memory of this handle's device (any pointer may be 0)."""
+        self._call("mpc_track_device", C.c_int(steps), C.c_int(samples), *(C.c_void_p(p or None) for p in
+                   (dx0_ptr, w_ptr, u_lo_ptr, u_hi_ptr, x_ptr, u_ptr, stats_ptr)))
+
+    def mpc_run_tracked(self, cycles, shift, w=None, u_lo=None, u_hi=None):
+        """``cycles`` x (solve; mpc_track(shift, 1, w=w[c]); mpc_advance(shift, x0=the tracked state)) with the log kept on
+        the device; w [cycles][B][shift][n].  Returns dict(X_cl [B][cycles*shift+1][n], U_cl [B][cycles*shift][m] -- the
+        TRACKED states and controls --, iterations [B][cycles], status [B][cycles], track [B][cycles] of TRACK_STATS_DTYPE)."""
+        w = _f64(w)
+        u_lo, u_hi = self._track_bounds(u_lo, u_hi)
+        if w is not None and w.shape != (cycles, self.batch, shift, self.n):
+            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {shift}, {self.n})")
+        L = max(cycles, 0) * max(shift, 0)
+        X = np.zeros((self.batch, L + 1, self.n))
+        U = np.zeros((self.batch, L, self.m))
+        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        track = np.zeros((self.batch, max(cycles, 0)), dtype=TRACK_STATS_DTYPE)
+        self._call("mpc_run_tracked", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(u_lo), _dp(u_hi), _dp(X), _dp(U),
+                   it.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int)),
+                   track.ctypes.data_as(C.POINTER(TrackStats)))
+        return dict(X_cl=X, U_cl=U, iterations=it, status=st, track=track)
 
     def get_initial_state(self):
         """What the next solve starts from, [B][n]."""

@@ -17,6 +17,7 @@
 #include <cerrno>
 #include <cmath>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,7 +39,7 @@ using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 8  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 9  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -46,6 +47,7 @@ struct altro_solver_s {
   std::unique_ptr<EngineBase> engine;
   bool uploaded = false;
   bool ilqr_mode = false;
+  bool has_gains = false;  // a backward pass (a solve, altro_backward_pass) has left gains on the device: altro_mpc_track
   std::string err;
   // Asynchronous solve (altro_solve_al_async): ONE worker thread per handle, created on first use and
   // parked on a condition variable between solves.  While a solve is pending the handle only answers
@@ -315,6 +317,12 @@ altro_status Forward(altro_handle h, F f) {
   if (st != ALTRO_OK) return st;
   st = f(*h->engine);
   if (st != ALTRO_OK) h->err = h->engine->LastError();
+  return st;
+}
+
+// behind a call that ran a backward pass: from now on the device holds gains (altro_mpc_track asks)
+altro_status GainsAfter(altro_handle h, altro_status st) {
+  if (h && st == ALTRO_OK) h->has_gains = true;
   return st;
 }
 
@@ -731,11 +739,11 @@ altro_status altro_set_penalty_scaling(altro_handle h, double phi) {
 
 altro_status altro_solve_al(altro_handle h) {
   if (h) h->ilqr_mode = false;
-  return Forward(h, [&](EngineBase& e) { return e.SolveAL(h->opts); });
+  return GainsAfter(h, Forward(h, [&](EngineBase& e) { return e.SolveAL(h->opts); }));
 }
 altro_status altro_solve_ilqr(altro_handle h) {
   if (h) h->ilqr_mode = true;
-  return Forward(h, [&](EngineBase& e) { return e.SolveILQR(h->opts); });
+  return GainsAfter(h, Forward(h, [&](EngineBase& e) { return e.SolveILQR(h->opts); }));
 }
 altro_status altro_solve_al_async(altro_handle h) {
   if (!h) return ALTRO_INVALID_ARG;
@@ -791,14 +799,16 @@ altro_status altro_wait(altro_handle h) {
   }
   h->async_pending = false;
   if (h->async_status != ALTRO_OK) h->err = h->async_err;
-  return h->async_status;
+  return GainsAfter(h, h->async_status);
 }
 altro_status altro_al_init(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.AlInit(h->opts); }); }
 altro_status altro_solve_setup(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.SolveSetup(h->opts); }); }
 altro_status altro_rollout(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.Rollout(h->opts); }); }
 altro_status altro_cost(altro_handle h, double* J) { return Forward(h, [&](EngineBase& e) { return e.Cost(h->opts, J); }); }
 altro_status altro_update_expansions(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.UpdateExpansions(h->opts); }); }
-altro_status altro_backward_pass(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.BackwardPass(h->opts); }); }
+altro_status altro_backward_pass(altro_handle h) {
+  return GainsAfter(h, Forward(h, [&](EngineBase& e) { return e.BackwardPass(h->opts); }));
+}
 altro_status altro_forward_pass(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.ForwardPass(h->opts); }); }
 altro_status altro_update_convergence_statistics(altro_handle h) {
   return Forward(h, [&](EngineBase& e) { return e.UpdateConvergenceStatistics(h->opts); });
@@ -970,6 +980,57 @@ altro_status MpcAdvanceImpl(altro_handle h, int shift, const double* x0, const d
   return st;
 }
 
+static_assert(sizeof(altro_track_stats) == sizeof(TrackStats) && sizeof(altro_track_stats) == 40 &&
+                  offsetof(altro_track_stats, steps_done) == offsetof(TrackStats, steps_done) &&
+                  offsetof(altro_track_stats, cost) == offsetof(TrackStats, cost) &&
+                  offsetof(altro_track_stats, violation) == offsetof(TrackStats, violation) &&
+                  offsetof(altro_track_stats, max_dx) == offsetof(TrackStats, max_dx) &&
+                  offsetof(altro_track_stats, max_du) == offsetof(TrackStats, max_du),
+              "altro_track_stats (include/altro_mpc.h) and TrackStats (altro_common.hpp) are one layout");
+// the options a tracking call takes from the handle
+TrackArgs TrackOpts(altro_handle h) {
+  TrackArgs g{};
+  g.check_bounds = h->opts.check_forwardpass_bounds;
+  g.state_max = h->opts.state_max;
+  g.control_max = h->opts.control_max;
+  return g;
+}
+// both tracking entry points: everything that can be refused without a device first
+altro_status MpcTrackImpl(altro_handle h, int steps, int samples, const double* dx0, const double* w, const double* u_lo,
+                          const double* u_hi, double* X_cl, double* U_cl, altro_track_stats* stats, int on_device, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const int N = h->spec.desc.N;
+  if (steps < 1 || steps > N) {
+    h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
+    return ALTRO_INVALID_ARG;
+  }
+  if (samples < 1) {
+    h->err = std::string(who) + ": at least one sample per instance, got " + std::to_string(samples);
+    return ALTRO_INVALID_ARG;
+  }
+  if ((u_lo == nullptr) != (u_hi == nullptr)) {
+    h->err = std::string(who) + ": u_lo and u_hi come together (both or neither)";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!h->has_gains) {
+    h->err = std::string(who) + ": no backward pass has produced gains on this handle yet (altro_solve_al, altro_solve_ilqr, "
+             "altro_backward_pass)";
+    return ALTRO_NOT_READY;
+  }
+  TrackArgs g = TrackOpts(h);
+  g.steps = steps;
+  g.S = samples;
+  g.dx0 = dx0;
+  g.w = w;
+  g.u_lo = u_lo;
+  g.u_hi = u_hi;
+  g.X_cl = X_cl;
+  g.U_cl = U_cl;
+  g.stats = reinterpret_cast<TrackStats*>(stats);
+  return Forward(h, [&](EngineBase& e) { return e.MpcTrack(g, on_device); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1031,6 +1092,55 @@ altro_status altro_mpc_run(altro_handle h, int cycles, int shift, const double* 
   if (h->uploaded) {
     const std::string err = h->err;
     const altro_status es = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);  // (also after a failure: it frees the log)
+    if (st == ALTRO_OK && es != ALTRO_OK) {
+      h->err = h->engine->LastError();
+      st = es;
+    } else {
+      h->err = err;
+    }
+  }
+  return st;
+}
+altro_status altro_mpc_track(altro_handle h, int steps, int samples, const double* dx0, const double* w, const double* u_lo,
+                             const double* u_hi, double* X_cl, double* U_cl, altro_track_stats* stats) {
+  return MpcTrackImpl(h, steps, samples, dx0, w, u_lo, u_hi, X_cl, U_cl, stats, 0, "altro_mpc_track");
+}
+altro_status altro_mpc_track_device(altro_handle h, int steps, int samples, const void* dx0_device, const void* w_device,
+                                    const void* u_lo_device, const void* u_hi_device, void* X_cl_device, void* U_cl_device,
+                                    void* stats_device) {
+  return MpcTrackImpl(h, steps, samples, (const double*)dx0_device, (const double*)w_device, (const double*)u_lo_device,
+                      (const double*)u_hi_device, (double*)X_cl_device, (double*)U_cl_device, (altro_track_stats*)stats_device, 1,
+                      "altro_mpc_track_device");
+}
+altro_status altro_mpc_run_tracked(altro_handle h, int cycles, int shift, const double* w, const double* u_lo, const double* u_hi,
+                                   double* X_cl, double* U_cl, int* iterations, int* status, altro_track_stats* track) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (cycles < 1) {
+    h->err = "altro_mpc_run_tracked: at least one cycle";
+    return ALTRO_INVALID_ARG;
+  }
+  if ((u_lo == nullptr) != (u_hi == nullptr)) {
+    h->err = "altro_mpc_run_tracked: u_lo and u_hi come together (both or neither)";
+    return ALTRO_INVALID_ARG;
+  }
+  altro_status st = MpcCheck(h, shift, "altro_mpc_run_tracked");
+  if (st != ALTRO_OK) return st;
+  st = Forward(h, [&](EngineBase& e) { return e.MpcTrackedBegin(cycles, shift, u_lo, u_hi); });
+  const size_t per_cycle = (size_t)h->spec.desc.batch * (size_t)shift * (size_t)h->spec.desc.n;
+  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
+    st = altro_solve_al(h);
+    if (st != ALTRO_OK) break;
+    const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
+    st = Forward(h, [&](EngineBase& e) { return e.MpcTrackedCycle(w ? w + (size_t)c * per_cycle : nullptr, TrackOpts(h), pen); });
+    if (st == ALTRO_OK) {  // (as behind altro_mpc_advance: the initial state now lives on the device alone)
+      h->spec.x0.clear();
+      h->spec.x0_per_instance = 0;
+    }
+  }
+  if (h->uploaded) {
+    const std::string err = h->err;
+    const altro_status es = h->engine->MpcTrackedEnd(X_cl, U_cl, iterations, status, reinterpret_cast<TrackStats*>(track));
     if (st == ALTRO_OK && es != ALTRO_OK) {
       h->err = h->engine->LastError();
       st = es;

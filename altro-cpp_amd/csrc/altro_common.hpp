@@ -90,6 +90,25 @@ inline std::vector<int> MpcRowMap(int N, int shift, const std::vector<int>& kb, 
   return src;
 }
 
+// ---- closed-loop tracking (include/altro_mpc.h: altro_mpc_track) --------------------------------------
+// altro_track_stats as the kernel writes it (the C-ABI translation unit asserts that the two layouts agree; a user-model
+// plugin compiles this header without the C header)
+struct TrackStats {
+  int status, steps_done;
+  double cost, violation, max_dx, max_du;
+};
+// One call of Engine::MpcTrack / one launch of k_mpc_track.  Every pointer may be null; host or device memory as the call says.
+struct TrackArgs {
+  int steps, S;
+  const double *dx0, *w;      // [B][S][n], [B][S][steps][n]
+  const double *u_lo, *u_hi;  // [m] each, both or neither
+  double *X_cl, *U_cl;        // [B][S][steps + 1][n], [B][S][steps][m]
+  double* x_end;              // [B][S][n]: row `steps` of X_cl on its own (what altro_mpc_run_tracked advances from)
+  TrackStats* stats;          // [B][S]
+  int check_bounds;           // options.check_forwardpass_bounds, state_max, control_max
+  double state_max, control_max;
+};
+
 // ---- device-visible problem description (lives in global memory, read with scalar loads) ---------
 struct ConDesc {
   int kind;          // altro_constraint_kind
@@ -344,6 +363,13 @@ class EngineBase {
   // closed-loop log of altro_mpc_run: every advance between Begin and End appends what the loop applied
   virtual altro_status MpcLogBegin(int cycles, int shift) = 0;
   virtual altro_status MpcLogEnd(double* X_cl, double* U_cl, int* iterations, int* status) = 0;
+  // closed-loop tracking under the gains on the device (k_mpc_track); changes nothing on the engine
+  virtual altro_status MpcTrack(const TrackArgs& call, int on_device) = 0;
+  // altro_mpc_run_tracked: between Begin and End every Cycle (behind a solve) records the solve's statistics, tracks `shift`
+  // knots with one sample under w ([B][shift][n], host, or nullptr), appends to the log and advances from the tracked state
+  virtual altro_status MpcTrackedBegin(int cycles, int shift, const double* u_lo, const double* u_hi) = 0;
+  virtual altro_status MpcTrackedCycle(const double* w, const TrackArgs& opts, double reset_pen) = 0;
+  virtual altro_status MpcTrackedEnd(double* X_cl, double* U_cl, int* iterations, int* status, TrackStats* track) = 0;
   virtual altro_status GetInitialState(double* x0) = 0;
   virtual altro_status SetPenalties(const double* rho) = 0;
   // rows and cone (1: equality) of every registered constraint, in registration order

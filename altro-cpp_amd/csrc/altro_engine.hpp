@@ -686,6 +686,158 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
   }
+  // ---- closed-loop tracking (include/altro_mpc.h) ---------------------------------------------------
+  // One launch of k_mpc_track, one lane per (instance, sample).  Host arrays are staged through ONE device block that lives
+  // for the call; device arrays are used where they are.  Reads the engine's arrays only: no flag of the engine changes.
+  altro_status MpcTrack(const TrackArgs& call, int on_device) override {
+    if (call.steps < 1 || call.steps > N_ || call.S < 1 || (call.u_lo == nullptr) != (call.u_hi == nullptr)) {
+      err_ = "altro_mpc_track: steps must lie in [1, N], samples must be positive, and u_lo / u_hi come together";
+      return ALTRO_INVALID_ARG;
+    }
+    if (!StepOk()) return ALTRO_NOT_READY;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    if (on_device) {
+      ALTRO_TRY(LaunchTrack(call));
+      return Sync();
+    }
+    // the staged block, in doubles: dx0 | w | u_lo, u_hi | X_cl | U_cl | stats
+    const size_t L = (size_t)B_ * (size_t)call.S, steps = (size_t)call.steps;
+    static_assert(sizeof(TrackStats) % sizeof(double) == 0, "the statistics are staged in a block of doubles");
+    const size_t cnt[6] = {call.dx0 ? L * n : 0,           call.w ? L * steps * n : 0,     call.u_lo ? 2 * (size_t)m : 0,
+                           call.X_cl ? L * (steps + 1) * n : 0, call.U_cl ? L * steps * m : 0,
+                           call.stats ? L * (sizeof(TrackStats) / sizeof(double)) : 0};
+    size_t off[7] = {0};
+    for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + cnt[i];
+    double* blk = nullptr;
+    if (hipMalloc((void**)&blk, std::max<size_t>(off[6], 1) * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      err_ = "altro_mpc_track: out of device memory for " + std::to_string(off[6] * sizeof(double)) + " bytes of staged inputs and logs";
+      return ALTRO_HIP_ERROR;
+    }
+    TrackArgs g = call;
+    hipError_t e = hipSuccess;
+    auto up = [&](const double* src, int i) {
+      if (src && e == hipSuccess) e = hipMemcpyAsync(blk + off[i], src, cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream_);
+      return src ? blk + off[i] : nullptr;
+    };
+    g.dx0 = up(call.dx0, 0);
+    g.w = up(call.w, 1);
+    g.u_lo = up(call.u_lo, 2);
+    if (call.u_hi && e == hipSuccess) e = hipMemcpyAsync(blk + off[2] + m, call.u_hi, m * sizeof(double), hipMemcpyHostToDevice, stream_);
+    g.u_hi = call.u_hi ? blk + off[2] + m : nullptr;
+    g.X_cl = call.X_cl ? blk + off[3] : nullptr;
+    g.U_cl = call.U_cl ? blk + off[4] : nullptr;
+    g.stats = call.stats ? reinterpret_cast<TrackStats*>(blk + off[5]) : nullptr;
+    g.x_end = nullptr;
+    altro_status st = ALTRO_OK;
+    if (e == hipSuccess) st = LaunchTrack(g);
+    if (st == ALTRO_OK) {
+      if (e == hipSuccess) e = hipGetLastError();
+      if (e == hipSuccess && call.X_cl) e = hipMemcpyAsync(call.X_cl, g.X_cl, cnt[3] * sizeof(double), hipMemcpyDeviceToHost, stream_);
+      if (e == hipSuccess && call.U_cl) e = hipMemcpyAsync(call.U_cl, g.U_cl, cnt[4] * sizeof(double), hipMemcpyDeviceToHost, stream_);
+      if (e == hipSuccess && call.stats) e = hipMemcpyAsync(call.stats, g.stats, cnt[5] * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    }
+    const hipError_t es = hipStreamSynchronize(stream_);  // (also after a failure: the block must not go under a copy in flight)
+    hipFree(blk);
+    ALTRO_TRY(st);
+    ALTRO_HIP_CHECK(e);
+    ALTRO_HIP_CHECK(es);
+    return ALTRO_OK;
+  }
+  altro_status MpcTrackedBegin(int cycles, int shift, const double* u_lo, const double* u_hi) override {
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    TrackedDrop();
+    TrackedLog& t = tracked_;
+    const size_t B = (size_t)B_, Lk = (size_t)cycles * shift, sd = sizeof(TrackStats) / sizeof(double);
+    // in doubles: X log | U log | one cycle's X, U | its last state | its disturbance | bounds | statistics [cycles][B]
+    const size_t cnt[8] = {B * (Lk + 1) * n, B * Lk * m, B * ((size_t)shift + 1) * n, B * shift * m, B * n, B * shift * n, 2 * (size_t)m,
+                           (size_t)cycles * B * sd};
+    size_t off[9] = {0};
+    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + cnt[i];
+    if (hipMalloc((void**)&t.blk, off[8] * sizeof(double)) != hipSuccess ||
+        hipMalloc((void**)&t.it, 2 * (size_t)cycles * B * sizeof(int)) != hipSuccess) {
+      (void)hipGetLastError();
+      TrackedDrop();
+      err_ = "altro_mpc_run_tracked: out of device memory for the closed-loop log";
+      return ALTRO_HIP_ERROR;
+    }
+    t.Xlog = t.blk + off[0];
+    t.Ulog = t.blk + off[1];
+    t.Xc = t.blk + off[2];
+    t.Uc = t.blk + off[3];
+    t.xend = t.blk + off[4];
+    t.w = t.blk + off[5];
+    t.ulo = u_lo ? t.blk + off[6] : nullptr;
+    t.uhi = u_hi ? t.blk + off[6] + m : nullptr;
+    t.stats = reinterpret_cast<TrackStats*>(t.blk + off[7]);
+    t.cycles = cycles;
+    t.shift = shift;
+    t.cycle = 0;
+    if (u_lo) ALTRO_HIP_CHECK(CopySync(t.blk + off[6], u_lo, m * sizeof(double), hipMemcpyHostToDevice));
+    if (u_hi) ALTRO_HIP_CHECK(CopySync(t.blk + off[6] + m, u_hi, m * sizeof(double), hipMemcpyHostToDevice));
+    return ALTRO_OK;
+  }
+  altro_status MpcTrackedCycle(const double* w, const TrackArgs& opts, double reset_pen) override {
+    TrackedLog& t = tracked_;
+    if (!t.blk || t.cycle >= t.cycles) {
+      err_ = "altro_mpc_run_tracked: no log is open";
+      return ALTRO_NOT_READY;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    const size_t B = (size_t)B_, s = (size_t)t.shift, Lk = (size_t)t.cycles * s, c = (size_t)t.cycle, cb = (size_t)t.cycles * B;
+    // the statistics of the solve behind this cycle
+    ALTRO_HIP_CHECK(hipMemcpyAsync(t.it + c * B, A_.it_total, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+    ALTRO_HIP_CHECK(hipMemcpyAsync(t.it + cb + c * B, A_.status_al, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+    if (w) ALTRO_HIP_CHECK(hipMemcpyAsync(t.w, w, B * s * n * sizeof(double), hipMemcpyHostToDevice, stream_));
+    TrackArgs g = opts;
+    g.steps = t.shift;
+    g.S = 1;
+    g.dx0 = nullptr;
+    g.w = w ? t.w : nullptr;
+    g.u_lo = t.ulo;
+    g.u_hi = t.uhi;
+    g.X_cl = t.Xc;
+    g.U_cl = t.Uc;
+    g.x_end = t.xend;
+    g.stats = t.stats + c * B;
+    ALTRO_TRY(LaunchTrack(g));
+    // rows c s .. c s + s of every instance's log (the last of them is the next cycle's first, and the log's last row)
+    ALTRO_HIP_CHECK(hipMemcpy2DAsync(t.Xlog + c * s * n, (Lk + 1) * n * sizeof(double), t.Xc, (s + 1) * n * sizeof(double),
+                                     (s + 1) * n * sizeof(double), B, hipMemcpyDeviceToDevice, stream_));
+    ALTRO_HIP_CHECK(hipMemcpy2DAsync(t.Ulog + c * s * m, Lk * m * sizeof(double), t.Uc, s * m * sizeof(double), s * m * sizeof(double), B,
+                                     hipMemcpyDeviceToDevice, stream_));
+    ++t.cycle;
+    return MpcAdvance(t.shift, t.xend, nullptr, 1, reset_pen);
+  }
+  altro_status MpcTrackedEnd(double* X_cl, double* U_cl, int* iterations, int* status, TrackStats* track) override {
+    TrackedLog& t = tracked_;
+    hipError_t e = hipSetDevice(desc_.device_id);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (t.blk && t.cycle == t.cycles) {
+      const size_t B = (size_t)B_, Lk = (size_t)t.cycles * t.shift, cb = (size_t)t.cycles * B;
+      if (e == hipSuccess && X_cl) e = CopySync(X_cl, t.Xlog, B * (Lk + 1) * n * sizeof(double), hipMemcpyDeviceToHost);
+      if (e == hipSuccess && U_cl) e = CopySync(U_cl, t.Ulog, B * Lk * m * sizeof(double), hipMemcpyDeviceToHost);
+      // recorded [cycles][B] (one contiguous row per cycle), handed out [B][cycles]
+      if (e == hipSuccess && (iterations || status)) {
+        std::vector<int> h(2 * cb);
+        e = CopySync(h.data(), t.it, h.size() * sizeof(int), hipMemcpyDeviceToHost);
+        for (size_t c = 0; c < (size_t)t.cycles && e == hipSuccess; ++c)
+          for (size_t b = 0; b < B; ++b) {
+            if (iterations) iterations[b * t.cycles + c] = h[c * B + b];
+            if (status) status[b * t.cycles + c] = h[cb + c * B + b];
+          }
+      }
+      if (e == hipSuccess && track) {
+        std::vector<TrackStats> h(cb);
+        e = CopySync(h.data(), t.stats, h.size() * sizeof(TrackStats), hipMemcpyDeviceToHost);
+        for (size_t c = 0; c < (size_t)t.cycles && e == hipSuccess; ++c)
+          for (size_t b = 0; b < B; ++b) track[b * t.cycles + c] = h[c * B + b];
+      }
+    }
+    TrackedDrop();
+    ALTRO_HIP_CHECK(e);
+    return ALTRO_OK;
+  }
   altro_status GetInitialState(double* x0) override { return DownloadRec(A_.x0, 1, R::nP, 0, n, x0); }
   altro_status SetPenalties(const double* rho) override { return UploadRows(A_.pen, rho); }
   void ConShapes(std::vector<int>* p, std::vector<int>* eq) override {
@@ -723,6 +875,29 @@ class Engine final : public EngineBase {
     ALTRO_TRY(Sync());
     ALTRO_HIP_CHECK(CopySync(dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return ALTRO_OK;
+  }
+  // the launch of k_mpc_track on the engine's stream (every array of `g` in device memory)
+  altro_status LaunchTrack(const TrackArgs& g) {
+    const size_t blocks = ((size_t)B_ * (size_t)g.S + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffull) {
+      err_ = "altro_mpc_track: instances x samples exceed one launch (2^31 - 1 wavefronts)";
+      return ALTRO_INVALID_ARG;
+    }
+    hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
+    return ALTRO_OK;
+  }
+  // closed-loop log of altro_mpc_run_tracked (MpcTrackedBegin .. MpcTrackedEnd): one block of doubles, one of ints
+  struct TrackedLog {
+    double *blk = nullptr, *Xlog = nullptr, *Ulog = nullptr, *Xc = nullptr, *Uc = nullptr, *xend = nullptr, *w = nullptr, *ulo = nullptr,
+           *uhi = nullptr;
+    TrackStats* stats = nullptr;
+    int* it = nullptr;  // iterations [cycles][B], then statuses [cycles][B]
+    int cycles = 0, shift = 0, cycle = 0;
+  };
+  void TrackedDrop() {
+    if (tracked_.blk) hipFree(tracked_.blk);
+    if (tracked_.it) hipFree(tracked_.it);
+    tracked_ = TrackedLog{};
   }
   void MpcLogDrop() {
     if (mpc_log_X_) hipFree(mpc_log_X_);
@@ -914,6 +1089,7 @@ class Engine final : public EngineBase {
     if (A_.hist) hipFree(A_.hist);
     if (A_.hist_len) hipFree(A_.hist_len);
     MpcLogDrop();
+    TrackedDrop();
     if (d_stage_) hipFree(d_stage_);
     d_stage_ = nullptr;
     stage_cap_ = 0;
@@ -2303,6 +2479,7 @@ class Engine final : public EngineBase {
   double *mpc_log_X_ = nullptr, *mpc_log_U_ = nullptr;  // closed-loop log of altro_mpc_run (MpcLogBegin .. MpcLogEnd)
   int* mpc_log_it_ = nullptr;                           // iterations [B][cycles], then statuses [B][cycles]
   int mpc_log_cycles_ = 0, mpc_log_shift_ = 0, mpc_log_cycle_ = 0;
+  TrackedLog tracked_;                                  // closed-loop log of altro_mpc_run_tracked
   std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;
   volatile int* h_counter_ = nullptr;  // pinned + mapped: one word per sweep

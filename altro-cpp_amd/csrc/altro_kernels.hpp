@@ -5171,4 +5171,188 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_advance(DevArrays<T> A, Mpc
   }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Closed-loop tracking (include/altro_mpc.h, altro_mpc_track): iLQR::RolloutClosedLoop (ilqr.hpp:468-499) with alpha = 0
+// for every (instance, disturbance sample), ONE LANE EACH: x_0 = x0 + dx0, then per knot u = Ubar + K (x - Xbar), clipped
+// where bounds are given, x+ = f_d(x, u) + w, the forward pass's bound checks, and along the way the objective cost, the
+// constraint violation and the largest deviations from the plan.  Reads the handle's arrays, writes only the caller's.
+//
+// Lanes run along (instance, sample) with the sample fastest, so the lanes of one instance read the SAME Xbar / Ubar / gain
+// record: one address per instance and wave, broadcast by the memory pipeline.  Those records (and the knot's step, time,
+// model and disturbance) do not depend on the lane's state: they are requested ONE KNOT AHEAD into a second register set, as
+// k_begin_solve does for its controls, which leaves the m x n product and discrete_step on the serial chain.  The step is
+// the very discrete_step<T, M> of k_rollout with step_of / time_of / model_of: without a disturbance the lanes reproduce
+// the rollout's bits.  Violations go through knot_cost<STORE> with a context that has no duals, unit penalties and a
+// store_c that stores nothing (the handle's c_ rows stay); the augmented-Lagrangian value it returns is dropped, the
+// objective is quad_cost alone.  The logs are optional and written straight from the lane: a lane's rows are contiguous,
+// the lanes of a wave lie (steps + 1) n doubles apart -- strided stores, accepted.
+// -------------------------------------------------------------------------------------------------
+template <class T>
+struct CtxTrack {
+  const DevArrays<T>& A;
+  unsigned b;
+  ALTRO_DEV CtxTrack(const DevArrays<T>& A_, int b_) : A(A_), b((unsigned)b_) {}
+  ALTRO_DEV T par(int per_instance, int off, int i) const {
+    return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
+  }
+  ALTRO_DEV T shared(int off) const { return A.pool[off]; }
+  ALTRO_DEV T lam(int) const { return T(0); }
+  ALTRO_DEV T pen(int) const { return T(1); }
+  ALTRO_DEV void store_c(int, T) const {}
+};
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_mpc_track(DevArrays<T> A, const ProblemDesc* __restrict__ pd, TrackArgs g) {
+  constexpr int n = M::n, m = M::m;
+  using R = Rec<T, n, m>;
+  using RS = rec_scalar_t<T, M>;
+  using RR = Rec<RS, n, m>;
+  const size_t lane = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (lane >= (size_t)A.B * (size_t)g.S) return;
+  const int b = (int)(lane / (size_t)g.S);
+  const unsigned Bp = A.Bp;
+  const int N = A.N, steps = g.steps;
+  const bool want_stats = g.stats != nullptr;
+  const T nan = T(__builtin_nan(""));
+  double* const Xl = g.X_cl ? g.X_cl + lane * (size_t)(steps + 1) * n : nullptr;
+  double* const Ul = g.U_cl ? g.U_cl + lane * (size_t)steps * m : nullptr;
+  const double* const wl = g.w ? g.w + lane * (size_t)steps * n : nullptr;
+  const bool clip = g.u_lo != nullptr;
+  const T state_max2 = T(g.state_max * g.state_max), control_max2 = T(g.control_max * g.control_max);
+  const CtxTrack<T> C(A, b);
+
+  T x[R::nP], xk[R::nP], uk[R::mP], xkn[R::nP], ukn[R::mP], u[R::mP], xn[n], wk[n];
+  RS kd[RR::KP], kdn[RR::KP];
+  load_rec<T, R::nP>(A.x0 + (size_t)b * R::nP, x);
+  if (g.dx0) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) x[i] = T((double)x[i] + g.dx0[lane * n + i]);
+  }
+  load_rec<T, R::nP>(RECP(A.X, 0, R::nP), xk);
+  load_rec<T, R::mP>(RECP(A.U, 0, R::mP), uk);
+  load_rec<RS, RR::KP>(RECP((const RS*)A.KD, 0, RR::KP), kd);
+  T h = step_of(A, pd, 0);
+  float t = time_of(A, 0);
+  int md = model_of(A, 0);
+#pragma unroll
+  for (int i = 0; i < R::mP; ++i) u[i] = T(0);
+
+  double cost = 0.0;
+  T viol = T(0), mdx = T(0), mdu = T(0);
+  int status = ALTRO_UNSOLVED, done = steps;
+  bool alive = true;
+  for (int k = 0; k < steps; ++k) {
+    // what the next knot needs and the lane's state does not decide
+    const int kn = k + 1 < N ? k + 1 : N - 1;
+    load_rec<T, R::nP>(RECP(A.X, k + 1, R::nP), xkn);
+    load_rec<T, R::mP>(RECP(A.U, kn, R::mP), ukn);
+    load_rec<RS, RR::KP>(RECP((const RS*)A.KD, kn, RR::KP), kdn);
+    const T hn = step_of(A, pd, kn);
+    const float tn = time_of(A, kn);
+    const int mdn = model_of(A, kn);
+    if (wl) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) wk[i] = T(wl[(size_t)k * n + i]);
+    }
+    // u = Ubar + K (x - Xbar) (ilqr.hpp:477-478 with alpha = 0), then the saturation
+    T dxm = T(0), dum = T(0);
+#pragma unroll
+    for (int l = 0; l < n; ++l) dxm = max_(dxm, abs_(x[l] - xk[l]));
+#pragma unroll
+    for (int i = 0; i < m; ++i) {
+      T s = T(0);
+#pragma unroll
+      for (int l = 0; l < n; ++l) s += T(kd[RR::oK + i + l * m]) * (x[l] - xk[l]);
+      T ui = uk[i] + s;
+      if (clip) ui = min_(max_(ui, T(g.u_lo[i])), T(g.u_hi[i]));
+      u[i] = ui;
+      dum = max_(dum, abs_(ui - uk[i]));
+    }
+    if (alive) {
+      mdx = max_(mdx, dxm);
+      mdu = max_(mdu, dum);
+    }
+    if (want_stats) {
+      int rb;
+      const KnotClass& kc = class_of_knot(A, pd, k, &rb);
+      const T Jk = quad_cost<T, n, m>(C, pd->grp[kc.cost_group], x, u);
+      T v = T(0);
+      knot_cost<T, n, m, true>(C, pd, kc, rb, x, u, &v);
+      if (alive) {
+        cost += (double)Jk;
+        viol = max_(viol, v);
+      }
+    }
+    if (Xl) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) Xl[(size_t)k * n + i] = (double)(alive ? x[i] : nan);
+    }
+    if (Ul) {
+#pragma unroll
+      for (int i = 0; i < m; ++i) Ul[(size_t)k * m + i] = (double)(alive ? u[i] : nan);
+    }
+    discrete_step<T, M>(x, u, h, xn, t, md);
+    if (wl) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) xn[i] += wk[i];
+    }
+    if (g.check_bounds && alive) {  // ||x||_2 > state_max <=> ||x||^2 > state_max^2 (ilqr.hpp:484-495), as the forward pass
+      T sx = T(0), su = T(0);
+#pragma unroll
+      for (int i = 0; i < n; ++i) sx += xn[i] * xn[i];
+#pragma unroll
+      for (int i = 0; i < m; ++i) su += u[i] * u[i];
+      if (sx > state_max2) {
+        status = ALTRO_STATE_LIMIT;
+        alive = false;
+        done = k;
+      } else if (su > control_max2) {
+        status = ALTRO_CONTROL_LIMIT;
+        alive = false;
+        done = k;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < n; ++i) x[i] = alive ? xn[i] : x[i];  // (a stopped lane keeps its last state and idles along)
+#pragma unroll
+    for (int i = 0; i < R::nP; ++i) xk[i] = xkn[i];
+#pragma unroll
+    for (int i = 0; i < R::mP; ++i) uk[i] = ukn[i];
+#pragma unroll
+    for (int i = 0; i < RR::KP; ++i) kd[i] = kdn[i];
+    h = hn;
+    t = tn;
+    md = mdn;
+  }
+  // the state the tracking ends in (xk holds Xbar[steps] by now); the terminal knot's cost and violation iff steps == N
+  if (alive) {
+#pragma unroll
+    for (int l = 0; l < n; ++l) mdx = max_(mdx, abs_(x[l] - xk[l]));
+  }
+#pragma unroll
+  for (int i = 0; i < n; ++i) {
+    const double xe = (double)(alive ? x[i] : nan);
+    if (Xl) Xl[(size_t)steps * n + i] = xe;
+    if (g.x_end) g.x_end[lane * n + i] = xe;
+  }
+  if (!want_stats) return;
+  if (alive && steps == N) {
+#pragma unroll
+    for (int i = 0; i < R::mP; ++i) u[i] = T(0);
+    int rb;
+    const KnotClass& kc = class_of_knot(A, pd, N, &rb);
+    cost += (double)quad_cost<T, n, m>(C, pd->grp[kc.cost_group], x, u);
+    T v = T(0);
+    knot_cost<T, n, m, true>(C, pd, kc, rb, x, u, &v);
+    viol = max_(viol, v);
+  }
+  TrackStats st;
+  st.status = status;
+  st.steps_done = done;
+  st.cost = cost;
+  st.violation = (double)viol;
+  st.max_dx = (double)mdx;
+  st.max_du = (double)mdu;
+  g.stats[lane] = st;
+}
+
 }  // namespace altro_hip

@@ -1307,6 +1307,16 @@ class AugmentedLagrangianiLQR {
     detail::Check(Handle(), altro_mpc_advance(Handle(), shift, x0, 1, w), "altro_mpc_advance");
     ilqr_solver_.Pull(true, false);
   }
+  // Between two solves (include/altro_mpc.h): the plant under the solved plan's feedback policy, simulated ON THE DEVICE for
+  // `steps` knots and `samples` disturbance draws per instance -- what a caller of the reference composes on the host from
+  // GetFeedbackGain() and the model's Evaluate: u = Ubar + K (x - Xbar), clipped to [u_lo, u_hi] where given,
+  // x+ = f(x, u) + w.  dx0 [B][S][n], w [B][S][steps][n], u_lo / u_hi [m], X_cl [B][S][steps+1][n], U_cl [B][S][steps][m],
+  // stats [B][S]; each may be null.  Changes nothing on the solver; the bound checks follow GetOptions().
+  void TrackClosedLoop(int steps, int samples, const double* dx0, const double* w, const double* u_lo, const double* u_hi,
+                       double* X_cl, double* U_cl, altro_track_stats* stats = nullptr) {
+    ilqr_solver_.PushOptions();
+    detail::Check(Handle(), altro_mpc_track(Handle(), steps, samples, dx0, w, u_lo, u_hi, X_cl, U_cl, stats), "altro_mpc_track");
+  }
   // al_solver.hpp:287-302: duals and penalties reset as the options say, statistics reset, "viol" and "pen" logged
   void Init() {
     ilqr_solver_.Push();  // (options and the caller's trajectory)

@@ -57,6 +57,54 @@ altro_status altro_mpc_advance_device(altro_handle h, int shift, const void* x0_
 altro_status altro_mpc_run(altro_handle h, int cycles, int shift, const double* w, double* X_cl, double* U_cl, int* iterations,
                            int* status);
 
+/* ---- between two solves: the plant under the plan's time-varying feedback policy ---------------------------------------
+ * iLQR::RolloutClosedLoop (altro/ilqr/ilqr.hpp:468-499) with alpha = 0, as an entry point of its own: every (instance b,
+ * disturbance sample s) is simulated for `steps` knots under u = Ubar + K (x - Xbar), one GPU lane each, by ONE kernel
+ * launch.  Xbar, Ubar and K are the handle's device arrays as they stand (K is what altro_get_gains returns; under
+ * ALTRO_F32 its fp32 record is widened to fp64 as the forward pass does):
+ *   x_0 = x0[b] + dx0[b][s]
+ *   for k = 0 .. steps-1:
+ *     u_k     = Ubar_k + K_k (x_k - Xbar_k)              (ilqr.hpp:477-478)
+ *     u_k     = min(max(u_k, u_lo), u_hi)                only where the bounds are given
+ *     x_{k+1} = f_d(x_k, u_k, t_k, h_k) + w[b][s][k]     the knot's own step, time and model
+ *     if options.check_forwardpass_bounds: |x_{k+1}|_2 > state_max -> ALTRO_STATE_LIMIT, else |u_k|_2 > control_max ->
+ *       ALTRO_CONTROL_LIMIT (ilqr.hpp:484-495); the sample stops there with steps_done = k
+ * A stopped sample keeps X_cl[0 .. steps_done] and U_cl[0 .. steps_done]; the log rows behind them are quiet NaN.
+ * The call changes NOTHING on the handle: trajectory, duals, stored constraint values, statistics and cost-to-go state stay.
+ * Every model kind is accepted (per-knot steps, times and models, time-varying and discrete user models): nothing moves
+ * along the horizon here.
+ * Refused before any device work: steps outside [1, N], samples < 1 or exactly one of u_lo / u_hi given
+ * (ALTRO_INVALID_ARG); no backward pass has produced gains on this handle yet, or an asynchronous solve is in flight
+ * (ALTRO_NOT_READY); no usable device (ALTRO_HIP_ERROR -- there is no CPU fallback). */
+typedef struct altro_track_stats { /* one per (instance, sample) */
+  int status;       /* ALTRO_UNSOLVED (ran to the end, as ilqr.hpp:497), ALTRO_STATE_LIMIT or ALTRO_CONTROL_LIMIT */
+  int steps_done;   /* knots simulated before a limit stopped the sample (== steps otherwise) */
+  double cost;      /* sum of the knots' OBJECTIVE cost (the quadratic / the user cost, no augmented-Lagrangian terms) along the
+                       path, knots 0 .. steps-1 (0 .. steps_done of a stopped sample), plus the terminal knot's (u = 0) iff it
+                       ran to the end and steps == N; added up in knot order */
+  double violation; /* max constraint violation along the path, same knots, evaluated like altro_max_violation */
+  double max_dx;    /* max_k |x_k - Xbar_k|_inf, k = 0 .. steps_done */
+  double max_du;    /* max_k |u_k - Ubar_k|_inf, k = 0 .. min(steps_done, steps - 1) */
+} altro_track_stats;
+
+/* Host arrays, each may be NULL: dx0[B][S][n] and w[B][S][steps][n] (NULL = zero), u_lo / u_hi [m] (both or neither;
+ * +-inf allowed), X_cl[B][S][steps+1][n], U_cl[B][S][steps][m], stats[B][S] (a large ensemble asks for the statistics only). */
+altro_status altro_mpc_track(altro_handle h, int steps, int samples, const double* dx0, const double* w, const double* u_lo,
+                             const double* u_hi, double* X_cl, double* U_cl, altro_track_stats* stats);
+/* The same with every array pointer in memory of the handle's device: nothing crosses to the host.  Returns when the work
+ * on the handle's stream is done. */
+altro_status altro_mpc_track_device(altro_handle h, int steps, int samples, const void* dx0_device, const void* w_device,
+                                    const void* u_lo_device, const void* u_hi_device, void* X_cl_device, void* U_cl_device,
+                                    void* stats_device);
+/* cycles x (altro_solve_al; track `shift` knots with ONE sample under w[c]; advance by `shift` with x0 = the tracked
+ * x_shift, device to device) -- bit for bit the caller's own loop over altro_solve_al, altro_mpc_track and
+ * altro_mpc_advance.  w: host [cycles][B][shift][n] or NULL.  X_cl, U_cl, iterations, status: shaped as altro_mpc_run gives
+ * them, but X_cl / U_cl hold the TRACKED states and controls, not the planned ones (the last row of X_cl is the initial
+ * state after the last advance); track[B][cycles]: the statistics of every cycle's tracking.  Each may be NULL.  Refuses
+ * what altro_mpc_advance refuses. */
+altro_status altro_mpc_run_tracked(altro_handle h, int cycles, int shift, const double* w, const double* u_lo, const double* u_hi,
+                                   double* X_cl, double* U_cl, int* iterations, int* status, altro_track_stats* track);
+
 /* What the next solve starts from, [B][n]. */
 altro_status altro_get_initial_state(altro_handle h, double* x0);
 /* Counterpart of altro_set_duals for the penalties, [B][rows]. */
