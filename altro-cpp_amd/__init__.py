@@ -237,6 +237,50 @@ class BatchSolver:
         self._call("set_lqr_cost", C.c_int(k_begin), C.c_int(k_end), _dp(Qc), _dp(Rc), _dp(xref),
                    _dp(uref), C.c_int(per))
 
+    def set_lqr_tracking_cost(self, k_begin, k_end, Q, R):
+        """LQRCost(Q, R, xref_k, uref_k) on knots [k_begin, k_end) with the handle's reference path at every knot
+        (set_reference): one cost group however many knots, the terms live on the device."""
+        Q, R = _f64(Q), _f64(R)
+        Qc = np.ascontiguousarray(Q.T)
+        Rc = np.ascontiguousarray(R.T)
+        self._call("set_lqr_tracking_cost", C.c_int(k_begin), C.c_int(k_end), _dp(Qc), _dp(Rc))
+
+    def _reference_shape(self, Xref, Uref):
+        if Xref.ndim not in (2, 3) or Xref.shape[-1] != self.n or (Xref.ndim == 3 and Xref.shape[0] != self.batch):
+            raise ValueError(f"Xref must have shape (rows, {self.n}) or ({self.batch}, rows, {self.n})")
+        if Uref is not None and Uref.shape != Xref.shape[:-1] + (self.m,):
+            raise ValueError(f"Uref must have shape {Xref.shape[:-1] + (self.m,)}")
+        return Xref.shape[-2], 1 if Xref.ndim == 3 else 0
+
+    def set_reference(self, Xref, Uref=None):
+        """The reference path of the tracking costs: Xref [rows][n], Uref [rows][m] (None: zeros), or [B][rows][.] per
+        instance.  Knot k uses row min(offset + k, rows - 1); setting a path puts the offset back to 0."""
+        Xref, Uref = _f64(Xref), _f64(Uref)
+        rows, per = self._reference_shape(Xref, Uref)
+        self._call("set_reference", _dp(Xref), _dp(Uref), C.c_int(rows), C.c_int(per))
+
+    def set_reference_device(self, x_ptr, u_ptr, rows, per_instance):
+        """set_reference with fp64 arrays in memory of this handle's device (u_ptr may be 0)."""
+        self._call("set_reference_device", C.c_void_p(x_ptr or None), C.c_void_p(u_ptr or None), C.c_int(rows),
+                   C.c_int(1 if per_instance else 0))
+
+    def set_reference_offset(self, offset):
+        self._call("set_reference_offset", C.c_int(offset))
+
+    def get_reference_offset(self):
+        off = C.c_int(0)
+        self._call("get_reference_offset", C.byref(off))
+        return off.value
+
+    def get_reference_terms(self):
+        """(q [B][N+1][n], r [B][N+1][m], c [B][N+1]): the linear and constant terms of the tracking costs as the kernels
+        read them; zero on knots without a tracking cost."""
+        q = np.empty((self.batch, self.N + 1, self.n))
+        r = np.empty((self.batch, self.N + 1, self.m))
+        c = np.empty((self.batch, self.N + 1))
+        self._call("get_reference_terms", _dp(q), _dp(r), _dp(c))
+        return q, r, c
+
     def set_user_cost(self, k_begin, k_end, params, type=0):
         """A user cost of the handle's user model (register_model_source) on knots [k_begin, k_end);
         params: [nparams] or [B][nparams]; ``type``: index of the cost class in the source's ALTRO_USER_COSTS list."""

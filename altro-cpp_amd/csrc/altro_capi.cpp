@@ -34,12 +34,13 @@
 
 #include "altro_common.hpp"
 #include "../../include/altro_mpc.h"
+#include "../../include/altro_tracking.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 9  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 10  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -318,6 +319,28 @@ altro_status Forward(altro_handle h, F f) {
   st = f(*h->engine);
   if (st != ALTRO_OK) h->err = h->engine->LastError();
   return st;
+}
+
+// A knot whose cost is a tracking cost, and no reference path yet: the calls that evaluate costs answer ALTRO_NOT_READY
+// here, before any device work.  (After the upload the engine knows: the path may have come through
+// altro_set_reference_device.)
+bool ReferenceMissing(altro_handle h) {
+  if (h->uploaded || h->spec.ref_rows > 0) return false;
+  const int N = h->spec.desc.N;
+  std::vector<int> tracking(N + 1, 0);
+  for (const CostSpec& c : h->spec.costs)  // the last cost set on a knot wins
+    for (int k = std::max(c.k_begin, 0); k < std::min(c.k_end, N + 1); ++k) tracking[k] = c.tracking;
+  for (int k = 0; k <= N; ++k)
+    if (tracking[k]) {
+      h->err = "knot " + std::to_string(k) + " has a tracking cost but no reference path is set (altro_set_reference)";
+      return true;
+    }
+  return false;
+}
+template <class F>
+altro_status ForwardCost(altro_handle h, F f) {
+  if (h && !h->async_pending && ReferenceMissing(h)) return ALTRO_NOT_READY;
+  return Forward(h, f);
 }
 
 // behind a call that ran a backward pass: from now on the device holds gains (altro_mpc_track asks)
@@ -616,6 +639,83 @@ altro_status altro_set_lqr_cost(altro_handle h, int k_begin, int k_end, const do
   h->spec.costs.push_back(std::move(c));
   return ALTRO_OK;
 }
+altro_status altro_set_lqr_tracking_cost(altro_handle h, int k_begin, int k_end, const double* Q, const double* R) {
+  if (!h || !Q || !R) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (DefChanged(h) != ALTRO_OK) return ALTRO_NOT_READY;
+  const altro_desc& d = h->spec.desc;
+  if (k_begin < 0 || k_end > d.N + 1 || k_begin >= k_end) {
+    h->err = "knot range out of bounds";
+    return ALTRO_INVALID_ARG;
+  }
+  CostSpec c;
+  c.k_begin = k_begin;
+  c.k_end = k_end;
+  c.per_instance = 0;
+  c.tracking = 1;
+  c.Q.assign(Q, Q + d.n * d.n);
+  c.R.assign(R, R + d.m * d.m);
+  h->spec.costs.push_back(std::move(c));
+  return ALTRO_OK;
+}
+altro_status altro_set_reference(altro_handle h, const double* Xref, const double* Uref, int rows, int per_instance) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (!Xref || rows < 1) {
+    h->err = "altro_set_reference: the path needs Xref and at least one row";
+    return ALTRO_INVALID_ARG;
+  }
+  if (h->uploaded) {  // (no copy into the recorded definition: the path lives on the device)
+    const altro_status st = h->engine->SetReference(Xref, Uref, rows, per_instance, 0);
+    if (st != ALTRO_OK) h->err = h->engine->LastError();
+    return st;
+  }
+  const altro_desc& d = h->spec.desc;
+  const size_t cnt = (size_t)rows * (per_instance ? d.batch : 1);
+  h->spec.ref_X.assign(Xref, Xref + cnt * d.n);
+  if (Uref) h->spec.ref_U.assign(Uref, Uref + cnt * d.m);
+  else h->spec.ref_U.clear();
+  h->spec.ref_rows = rows;
+  h->spec.ref_per_instance = per_instance ? 1 : 0;
+  h->spec.ref_offset = 0;
+  return ALTRO_OK;
+}
+altro_status altro_set_reference_device(altro_handle h, const void* Xref_device, const void* Uref_device, int rows,
+                                        int per_instance) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (!Xref_device || rows < 1) {
+    h->err = "altro_set_reference_device: the path needs Xref and at least one row";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) {
+    return e.SetReference((const double*)Xref_device, (const double*)Uref_device, rows, per_instance, 1);
+  });
+}
+altro_status altro_set_reference_offset(altro_handle h, int offset) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (offset < 0) {
+    h->err = "altro_set_reference_offset: the offset must not be negative";
+    return ALTRO_INVALID_ARG;
+  }
+  if (h->uploaded) {
+    const altro_status st = h->engine->SetReferenceOffset(offset);
+    if (st != ALTRO_OK) h->err = h->engine->LastError();
+    return st;
+  }
+  h->spec.ref_offset = offset;
+  return ALTRO_OK;
+}
+altro_status altro_get_reference_offset(altro_handle h, int* offset) {
+  if (!h || !offset) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  *offset = h->uploaded ? h->engine->GetReferenceOffset() : h->spec.ref_offset;
+  return ALTRO_OK;
+}
+altro_status altro_get_reference_terms(altro_handle h, double* q, double* r, double* c) {
+  return Forward(h, [&](EngineBase& e) { return e.GetReferenceTerms(q, r, c); });
+}
 altro_status altro_set_user_cost(altro_handle h, int k_begin, int k_end, const double* params, int nparams,
                                  int per_instance) {
   return altro_set_user_cost_type(h, 0, k_begin, k_end, params, nparams, per_instance);
@@ -739,15 +839,16 @@ altro_status altro_set_penalty_scaling(altro_handle h, double phi) {
 
 altro_status altro_solve_al(altro_handle h) {
   if (h) h->ilqr_mode = false;
-  return GainsAfter(h, Forward(h, [&](EngineBase& e) { return e.SolveAL(h->opts); }));
+  return GainsAfter(h, ForwardCost(h, [&](EngineBase& e) { return e.SolveAL(h->opts); }));
 }
 altro_status altro_solve_ilqr(altro_handle h) {
   if (h) h->ilqr_mode = true;
-  return GainsAfter(h, Forward(h, [&](EngineBase& e) { return e.SolveILQR(h->opts); }));
+  return GainsAfter(h, ForwardCost(h, [&](EngineBase& e) { return e.SolveILQR(h->opts); }));
 }
 altro_status altro_solve_al_async(altro_handle h) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
+  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
   // create the device state on the caller's thread: definition errors are reported here, synchronously
   altro_status st = Ensure(h);
   if (st != ALTRO_OK) return st;
@@ -801,15 +902,15 @@ altro_status altro_wait(altro_handle h) {
   if (h->async_status != ALTRO_OK) h->err = h->async_err;
   return GainsAfter(h, h->async_status);
 }
-altro_status altro_al_init(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.AlInit(h->opts); }); }
+altro_status altro_al_init(altro_handle h) { return ForwardCost(h, [&](EngineBase& e) { return e.AlInit(h->opts); }); }
 altro_status altro_solve_setup(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.SolveSetup(h->opts); }); }
 altro_status altro_rollout(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.Rollout(h->opts); }); }
-altro_status altro_cost(altro_handle h, double* J) { return Forward(h, [&](EngineBase& e) { return e.Cost(h->opts, J); }); }
-altro_status altro_update_expansions(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.UpdateExpansions(h->opts); }); }
+altro_status altro_cost(altro_handle h, double* J) { return ForwardCost(h, [&](EngineBase& e) { return e.Cost(h->opts, J); }); }
+altro_status altro_update_expansions(altro_handle h) { return ForwardCost(h, [&](EngineBase& e) { return e.UpdateExpansions(h->opts); }); }
 altro_status altro_backward_pass(altro_handle h) {
   return GainsAfter(h, Forward(h, [&](EngineBase& e) { return e.BackwardPass(h->opts); }));
 }
-altro_status altro_forward_pass(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.ForwardPass(h->opts); }); }
+altro_status altro_forward_pass(altro_handle h) { return ForwardCost(h, [&](EngineBase& e) { return e.ForwardPass(h->opts); }); }
 altro_status altro_update_convergence_statistics(altro_handle h) {
   return Forward(h, [&](EngineBase& e) { return e.UpdateConvergenceStatistics(h->opts); });
 }
@@ -1083,6 +1184,7 @@ altro_status altro_mpc_run(altro_handle h, int cycles, int shift, const double* 
   }
   altro_status st = MpcCheck(h, shift, "altro_mpc_run");
   if (st != ALTRO_OK) return st;
+  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
   st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
   const size_t per_cycle = (size_t)h->spec.desc.batch * h->spec.desc.n;
   for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
@@ -1126,6 +1228,7 @@ altro_status altro_mpc_run_tracked(altro_handle h, int cycles, int shift, const 
   }
   altro_status st = MpcCheck(h, shift, "altro_mpc_run_tracked");
   if (st != ALTRO_OK) return st;
+  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
   st = Forward(h, [&](EngineBase& e) { return e.MpcTrackedBegin(cycles, shift, u_lo, u_hi); });
   const size_t per_cycle = (size_t)h->spec.desc.batch * (size_t)shift * (size_t)h->spec.desc.n;
   for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {

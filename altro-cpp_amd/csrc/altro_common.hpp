@@ -23,6 +23,13 @@ constexpr int kHistFields = 8;
 constexpr int kMaxRuns = 16;  // maximal runs of consecutive knots sharing one class
 constexpr int kMaxFastCircles = 3;  // circles of one constraint that the specialised cost-wave layouts keep in registers
 constexpr int kMaxSharedPool = 128;  // shared parameters that travel to the forward kernel as kernel arguments
+// CostGroupDesc::q_pi / r_pi / c_pi of a tracking group (altro_set_lqr_tracking_cost): the term is neither shared (0) nor per
+// instance (1) but PER KNOT -- element q_off / r_off / c_off + i of the reference-term record of (knot, instance)
+constexpr int kParPerKnot = 2;
+// doubles of one reference-term record: q[n] | r[m] | c, rounded up to a pair (16-byte records)
+constexpr int RefTermRecord(int n, int m) { return (n + m + 1 + 1) & ~1; }
+// doubles of one point of the reference path: x[n] | u[m], rounded up to a pair
+constexpr int RefPathRecord(int n, int m) { return (n + m + 1) & ~1; }
 
 // ---- dtype-independent problem specification (what the altro::problem::Problem setters record) ---
 struct CostSpec {
@@ -31,6 +38,7 @@ struct CostSpec {
   int per_instance;  // bit0 xref, bit1 uref (user cost: params are per instance)
   int user = 0;      // 0: LQR cost; 1 + t: the t-th user cost type of the model's source (ALTRO_USER_COSTS) instead
   std::vector<double> params;  // user cost: [nparams] or [B][nparams]
+  int tracking = 0;  // altro_set_lqr_tracking_cost: xref / uref of knot k are the handle's reference at k (xref, uref stay empty)
 };
 struct ConSpec {
   int kind, k_begin, k_end, nparams, per_instance;
@@ -60,6 +68,10 @@ struct ProblemSpec {
   int traj_per_instance = 0;
   double penalty = -1.0;  // SetPenalty issued before the device state exists
   double phi = -1.0;
+  // altro_set_reference before the device state exists: the path Xref[rows][n], Uref[rows][m] ([B][rows][.] per instance;
+  // ref_U empty = zeros) and the window offset; the engine owns both after the upload
+  std::vector<double> ref_X, ref_U;
+  int ref_rows = 0, ref_per_instance = 0, ref_offset = 0;
 };
 
 // ---- receding-horizon advance (include/altro_mpc.h) --------------------------------------------------
@@ -130,7 +142,7 @@ struct KnotClass {
 struct CostGroupDesc {
   int Q_off, R_off;          // shared pool, column-major n x n and m x m
   int q_off, r_off, c_off;   // pool element (shared) or slot (per instance)
-  int q_pi, r_pi, c_pi;      // per-instance flags
+  int q_pi, r_pi, c_pi;      // 0 shared, 1 per instance, kParPerKnot: from the reference-term record of the knot
   int q_diag, r_diag;        // Q / R are diagonal (every off-diagonal entry is exactly zero)
   int user, u_off, u_pi;     // user cost (altro_set_user_cost): 1 + index of its type; parameters at u_off (pool element / first slot)
 };
@@ -374,6 +386,12 @@ class EngineBase {
   virtual altro_status SetPenalties(const double* rho) = 0;
   // rows and cone (1: equality) of every registered constraint, in registration order
   virtual void ConShapes(std::vector<int>* p, std::vector<int>* eq) = 0;
+  // the reference path of the tracking costs (include/altro_tracking.h: altro_set_reference): host arrays or (on_device) memory
+  // of the engine's device; Uref may be null (zeros).  The terms are recomputed on the device behind every change.
+  virtual altro_status SetReference(const double* Xref, const double* Uref, int rows, int per_instance, int on_device) = 0;
+  virtual altro_status SetReferenceOffset(int offset) = 0;
+  virtual int GetReferenceOffset() = 0;
+  virtual altro_status GetReferenceTerms(double* q, double* r, double* c) = 0;
   virtual const char* LastError() = 0;
 };
 

@@ -284,6 +284,11 @@ struct DevArrays {
   int seg_lo, seg_hi;  // that slice
   int seg_parts;       // segments a streak is split into (1: this sweep does not split -- the host sized the next sweep's grids
                        // for the count it knows, and only every kSegSplitEvery-th sweep may outgrow that)
+  // REFERENCE-TERM RECORDS of the tracking costs (altro_set_lqr_tracking_cost): ref[(k * Bp + b) * ref_rt + e], e = q[0..n) |
+  // r[0..m) | c, written by k_ref_terms alone, ALWAYS fp64.  nullptr: the problem has no tracking cost (no group is marked
+  // kParPerKnot, nothing reads it).  Last in the bundle: the kernel arguments in front of it keep their places.
+  const double* ref;
+  int ref_rt;
 };
 constexpr int kSegSplitEvery = 4;
 constexpr int kSegCancelled = 1, kSegRetired = 2;
@@ -939,11 +944,22 @@ ALTRO_DEV void discrete_jacobian(const T* x, const T* u, T hh, T* J, float t = 0
 //   CtxL  reads them from the copy the forward pass staged in LDS (serial rollout loop: no VMEM
 //         load may sit behind the candidate stores, and every pointer is an LDS pointer so that
 //         the compiler emits ds_read, never flat_load).
+// A parameter marked kParPerKnot (the linear and constant terms of a tracking cost) comes from the reference-term record of
+// the context's knot.  Only CtxGK (and CtxTrackK, altro_kernels.hpp) can read one: the caller names the knot, Ctx(A, b, k)
+// or C.at(k).  CtxG and CtxL take the same calls and ignore the knot -- at() is the context itself -- so the kernels of a
+// handle WITHOUT a tracking cost compile to what they were before tracking costs existed; a handle with one runs the
+// *_trk twins of the general kernels, the same bodies over CtxGK (Engine::FusedOk, Engine::LaunchForward).
+template <class T>
+ALTRO_DEV T ref_term(const DevArrays<T>& A, unsigned k, unsigned b, int e) {
+  return T(A.ref[(k * (unsigned)A.Bp + b) * (unsigned)A.ref_rt + (unsigned)e]);
+}
 template <class T>
 struct CtxG {
+  static constexpr bool kKnotTerms = false;
   const DevArrays<T>& A;
   unsigned b;
-  ALTRO_DEV CtxG(const DevArrays<T>& A_, int b_) : A(A_), b((unsigned)b_) {}
+  ALTRO_DEV CtxG(const DevArrays<T>& A_, int b_, int = 0) : A(A_), b((unsigned)b_) {}
+  ALTRO_DEV const CtxG& at(int) const { return *this; }
   ALTRO_DEV T par(int per_instance, int off, int i) const {
     return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
   }
@@ -953,7 +969,24 @@ struct CtxG {
   ALTRO_DEV void store_c(int r, T c) const { A.cval[(unsigned)r * (unsigned)A.Bp + b] = c; }
 };
 template <class T>
+struct CtxGK {  // CtxG that knows its knot
+  static constexpr bool kKnotTerms = true;
+  const DevArrays<T>& A;
+  unsigned b, k;
+  ALTRO_DEV CtxGK(const DevArrays<T>& A_, int b_, int k_ = 0) : A(A_), b((unsigned)b_), k((unsigned)k_) {}
+  ALTRO_DEV CtxGK at(int k_) const { return CtxGK(A, (int)b, k_); }
+  ALTRO_DEV T par(int per_instance, int off, int i) const {
+    if (per_instance == kParPerKnot) return ref_term(A, k, b, off + i);
+    return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
+  }
+  ALTRO_DEV T shared(int off) const { return A.pool[off]; }
+  ALTRO_DEV T lam(int r) const { return A.lam[(unsigned)r * (unsigned)A.Bp + b]; }
+  ALTRO_DEV T pen(int r) const { return A.pen[(unsigned)r * (unsigned)A.Bp + b]; }
+  ALTRO_DEV void store_c(int r, T c) const { A.cval[(unsigned)r * (unsigned)A.Bp + b] = c; }
+};
+template <class T>
 struct CtxL {
+  static constexpr bool kKnotTerms = false;
   const DevArrays<T>& A;
   unsigned b;
   const T* sPool;  // shared parameters (LDS, one copy per wave)
@@ -964,6 +997,7 @@ struct CtxL {
                    // [row] (the expansions computed AHEAD by the persistent kernel, committed later or dropped)
   ALTRO_DEV CtxL(const DevArrays<T>& A_, int b_, const T* pool_, const T* ip_, const T* lam_, const T* pen_, T* cdst_ = nullptr)
       : A(A_), b((unsigned)b_), sPool(pool_), sIp(ip_), sLam(lam_), sPen(pen_), cdst(cdst_) {}
+  ALTRO_DEV const CtxL& at(int) const { return *this; }
   ALTRO_DEV T par(int per_instance, int off, int i) const {
     const T* base = per_instance ? sIp : sPool;  // both LDS
     return base[off + i];
@@ -1170,6 +1204,7 @@ ALTRO_DEV T knot_cost(const Ctx& C, const ProblemDesc* pd, const KnotClass& kc, 
 template <class T, int n, int m>
 struct RunConsts {
   bool diag;
+  bool per_knot;  // a tracking group: q, r, c change with the knot (load_knot_terms), everything else is the run's
   T Qd[n], Rd[m], q[n], r[m], c;
   int bnd_ci;  // index of the hoisted bound constraint, -1 if none
   T bnd[2 * m];
@@ -1178,6 +1213,7 @@ template <class T, int n, int m, class Ctx>
 ALTRO_DEV void load_run_consts(const Ctx& C, const ProblemDesc* pd, const KnotClass& kc, RunConsts<T, n, m>& R) {
   const CostGroupDesc& g = pd->grp[kc.cost_group];
   R.diag = g.q_diag && g.r_diag && !(kHasUserCost && g.user);  // a user cost goes through quad_cost()
+  R.per_knot = g.q_pi == kParPerKnot;
 #pragma unroll
   for (int i = 0; i < n; ++i) {
     R.Qd[i] = C.shared(g.Q_off + i + i * n);
@@ -1206,6 +1242,16 @@ ALTRO_DEV void load_run_consts(const Ctx& C, const ProblemDesc* pd, const KnotCl
         if ((cd.hi_mask >> j) & 1u) R.bnd[m + j] = C.shared(pi++);
     }
   }
+}
+// The linear and constant terms of a tracking group at the knot of context C (C.at(k)): what load_run_consts hoists for an
+// ordinary group, read once per knot instead.
+template <class T, int n, int m, class Ctx>
+ALTRO_DEV void load_knot_terms(const Ctx& C, const CostGroupDesc& g, RunConsts<T, n, m>& R) {
+#pragma unroll
+  for (int i = 0; i < n; ++i) R.q[i] = C.par(g.q_pi, g.q_off, i);
+#pragma unroll
+  for (int i = 0; i < m; ++i) R.r[i] = C.par(g.r_pi, g.r_off, i);
+  R.c = C.par(g.c_pi, g.c_off, 0);
 }
 // Same value as knot_cost<.., STORE=false> (identical operation order), with the run constants in
 // registers and the constraint list unrolled so that class metadata stays in scalar registers.

@@ -303,10 +303,11 @@ class Engine final : public EngineBase {
   altro_status SolveILQR(const altro_options& o) override { return Solve(o, kFwdILQR); }
 
   altro_status AlInit(const altro_options& o) override {
+    if (!RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     const DevOpts d = ToDevOpts(o);
     hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, d_pd_, d);
-    hipLaunchKernelGGL((k_knot_costs<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
+    LaunchKnotCosts();
     hipLaunchKernelGGL(k_log_viol_pen<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_);
     return Sync();
   }
@@ -322,8 +323,9 @@ class Engine final : public EngineBase {
     return Sync();
   }
   altro_status Cost(const altro_options&, double* J) override {
+    if (!RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL((k_knot_costs<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
+    LaunchKnotCosts();
     hipLaunchKernelGGL(k_sum_costs<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_tmp_);
     ALTRO_TRY(Sync());
     if (J) return DownloadVec(d_tmp_, J);
@@ -331,9 +333,12 @@ class Engine final : public EngineBase {
   }
   altro_status UpdateExpansions(const altro_options&) override {
     ctg_replayable_ = false;  // (the records a replayed backward pass would read are about to change)
-    if (!StepOk()) return ALTRO_NOT_READY;
+    if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL((k_expansions<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
+    if (A_.ref)
+      hipLaunchKernelGGL((k_expansions_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
+    else
+      hipLaunchKernelGGL((k_expansions<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
     return Sync();
   }
   altro_status BackwardPass(const altro_options& o) override {
@@ -380,7 +385,7 @@ class Engine final : public EngineBase {
   altro_status ForwardPass(const altro_options& o) override {
     cur_ = stream_;
     ctg_replayable_ = false;  // (a step-level forward pass moves the trajectory)
-    if (!StepOk()) return ALTRO_NOT_READY;
+    if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     LaunchForward(A_, ToDevOpts(o), (int)kFwdStepOnly, 1, B_);
     return Sync();
@@ -600,6 +605,88 @@ class Engine final : public EngineBase {
     return Sync();
   }
 
+  // ---- the reference path of the tracking costs (include/altro_tracking.h: altro_set_reference) ---------------------
+  // The path lives on the device (d_refpath_, one column or B of them); every change of path or window ends in ONE launch
+  // of k_ref_terms on the engine's stream, which rewrites the term records the cost kernels read (DevArrays::ref).  A handle
+  // without a tracking cost keeps the path and the offset it is given and launches nothing.
+  altro_status SetReference(const double* Xref, const double* Uref, int rows, int per_instance, int on_device) override {
+    if (!Xref || rows < 1) {
+      err_ = "altro_set_reference: the path needs Xref and at least one row";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(Sync());
+    ctg_replayable_ = false;  // (as SetTrajectory: what a replayed backward pass would read belongs to the old reference)
+    const int cols = per_instance ? B_ : 1;
+    const size_t need = (size_t)rows * cols * kRefPT;
+    if (need > refpath_cap_) {
+      if (d_refpath_) ALTRO_HIP_CHECK(hipFree(d_refpath_));
+      d_refpath_ = nullptr;
+      refpath_cap_ = 0;
+      ALTRO_HIP_CHECK(hipMalloc((void**)&d_refpath_, need * sizeof(double)));
+      refpath_cap_ = need;
+    }
+    const double *Xd = Xref, *Ud = Uref;
+    if (!on_device) {
+      const size_t nx = (size_t)rows * cols * n, nu = Uref ? (size_t)rows * cols * m : 0;
+      ALTRO_TRY(EnsureStage(nx + nu));
+      ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, Xref, nx * sizeof(double), hipMemcpyHostToDevice, stream_));
+      if (Uref) ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_ + nx, Uref, nu * sizeof(double), hipMemcpyHostToDevice, stream_));
+      Xd = d_stage_;
+      Ud = Uref ? d_stage_ + nx : nullptr;
+    }
+    hipLaunchKernelGGL((k_ref_pack<n, m>), dim3((cols + kBlock - 1) / kBlock, rows), dim3(kBlock), 0, stream_, Xd, Ud, d_refpath_, rows, cols);
+    ref_rows_ = rows;
+    ref_cols_ = cols;
+    ref_offset_ = 0;
+    LaunchRefTerms();
+    return Sync();
+  }
+  altro_status SetReferenceOffset(int offset) override {
+    if (offset < 0) {
+      err_ = "altro_set_reference_offset: the offset must not be negative";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ctg_replayable_ = false;
+    ref_offset_ = offset;
+    LaunchRefTerms();
+    return Sync();
+  }
+  int GetReferenceOffset() override { return ref_offset_; }
+  altro_status GetReferenceTerms(double* q, double* r, double* c) override {
+    if (!A_.ref) {  // no tracking cost: every knot reads zero
+      const size_t BK = (size_t)B_ * (N_ + 1);
+      if (q) std::fill(q, q + BK * n, 0.0);
+      if (r) std::fill(r, r + BK * m, 0.0);
+      if (c) std::fill(c, c + BK, 0.0);
+      return ALTRO_OK;
+    }
+    if (q) ALTRO_TRY(DownloadRec(A_.ref, N_ + 1, kRefRT, 0, n, q));
+    if (r) ALTRO_TRY(DownloadRec(A_.ref, N_ + 1, kRefRT, n, m, r));
+    if (c) ALTRO_TRY(DownloadRec(A_.ref, N_ + 1, kRefRT, n + m, 1, c));
+    return ALTRO_OK;
+  }
+  // the per-knot costs of the step-level calls (k_knot_costs; its twin on a handle with a tracking cost)
+  void LaunchKnotCosts() {
+    if (A_.ref)
+      hipLaunchKernelGGL((k_knot_costs_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
+    else
+      hipLaunchKernelGGL((k_knot_costs<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
+  }
+  // the term records of the current path and window (nothing to do without a tracking cost or without a path)
+  void LaunchRefTerms() {
+    if (!A_.ref || ref_rows_ < 1) return;
+    hipLaunchKernelGGL((k_ref_terms<T, n, m>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, (const double*)d_refpath_, d_ref_, ref_rows_,
+                       ref_cols_, ref_offset_);
+  }
+  // a cost evaluation on a handle with a tracking cost needs the path
+  bool RefOk() {
+    if (!A_.ref || ref_rows_ > 0) return true;
+    err_ = "a knot has a tracking cost but no reference path is set (altro_set_reference)";
+    return false;
+  }
+
   // ---- receding-horizon advance (include/altro_mpc.h) ----------------------------------------------
   // One launch (k_mpc_advance) on the engine's stream; the row map of a shift is built once and stays on the device.
   // Model-independent: the kernel never calls the dynamics.  Expansions, knot costs, stored constraint values and cost-to-go
@@ -654,6 +741,10 @@ class Engine final : public EngineBase {
       g.cycles = mpc_log_cycles_;
     }
     hipLaunchKernelGGL(k_mpc_advance<T>, dim3((B_ + g.tile - 1) / g.tile, 5), dim3(kMpcThreads), 0, stream_, A_, g);
+    if (A_.ref) {  // the window of a tracking cost's reference moves with the horizon (the end of the path is held)
+      ref_offset_ = (int)std::min<long long>((long long)ref_offset_ + shift, 0x7fffffffLL);
+      LaunchRefTerms();
+    }
     return Sync();
   }
   altro_status MpcLogBegin(int cycles, int shift) override {
@@ -694,7 +785,7 @@ class Engine final : public EngineBase {
       err_ = "altro_mpc_track: steps must lie in [1, N], samples must be positive, and u_lo / u_hi come together";
       return ALTRO_INVALID_ARG;
     }
-    if (!StepOk()) return ALTRO_NOT_READY;
+    if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     if (on_device) {
       ALTRO_TRY(LaunchTrack(call));
@@ -883,7 +974,10 @@ class Engine final : public EngineBase {
       err_ = "altro_mpc_track: instances x samples exceed one launch (2^31 - 1 wavefronts)";
       return ALTRO_INVALID_ARG;
     }
-    hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
+    if (A_.ref)  // (a tracking cost: the twin that reads the reference-term records, CtxTrackK)
+      hipLaunchKernelGGL((k_mpc_track_trk<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
+    else
+      hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
     return ALTRO_OK;
   }
   // closed-loop log of altro_mpc_run_tracked (MpcTrackedBegin .. MpcTrackedEnd): one block of doubles, one of ints
@@ -970,6 +1064,7 @@ class Engine final : public EngineBase {
   bool FusedOk(const DevOpts& d) const {
     if constexpr (!kMfmaBackward) return false;
     return !sw_.force_valu_backward && !sw_.no_fused && mfma_offsets_ok_ && fwd_lds_bytes_ > 0 && !A_.record_ctg && !A_.hk &&
+           !A_.ref &&  // (a tracking cost's term records are global memory: the general kernels, as for per-knot steps)
            d.line_search_max_iterations >= 1 && d.line_search_max_iterations <= kLineSearchLanes && fused_lds_bytes_ <= 160 * 1024;
   }
   // Forward pass launch: instances per wavefront and the LDS-staged variant are chosen from the size
@@ -979,7 +1074,9 @@ class Engine final : public EngineBase {
     // (per-knot steps / times / models: the three-wave kernel takes them for every model without a hand-fused RK4 --
     //  user models, the triple integrator, the 12-state model; the unicycle's fused rollout keeps ONE step as a loop
     //  invariant and goes to k_forward)
-    if (fwd_lds_bytes_ > 0 && d.line_search_max_iterations <= kLineSearchLanes && (!A.hk || !M::kHasFusedRk4)) {
+    // (a tracking cost: k_forward for EVERY model -- its terms are per-knot records in global memory, which the staged
+    //  contexts of k_forward2 do not carry)
+    if (fwd_lds_bytes_ > 0 && d.line_search_max_iterations <= kLineSearchLanes && (!A.hk || !M::kHasFusedRk4) && !A.ref) {
       // two-wave pipeline (rollout wave + cost wave), inputs staged in LDS.  When the instances left
       // would not even fill the CUs one by one, each gets a workgroup of its own: the prologue and the
       // epilogue of the kernel (staging, winner copy) shrink with the instances per workgroup.
@@ -994,9 +1091,12 @@ class Engine final : public EngineBase {
     }
     const dim3 grid((ninst + fwd_per_wave_ - 1) / fwd_per_wave_);
     {
-      // fallback: single wave, reads from HBM (staged block larger than LDS, > 20 line-search trials, or per-knot
-      // steps / times: SetKnotTimes)
-      hipLaunchKernelGGL((k_forward<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
+      // fallback: single wave, reads from HBM (staged block larger than LDS, > 20 line-search trials, per-knot
+      // steps / times: SetKnotTimes, or a tracking cost)
+      if (A.ref)
+        hipLaunchKernelGGL((k_forward_trk<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
+      else
+        hipLaunchKernelGGL((k_forward<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
     }
   }
   static void CpuRelax() {  // one spin-wait hint, whatever the host CPU
@@ -1057,6 +1157,11 @@ class Engine final : public EngineBase {
     allocs_.clear();
     mpc_maps_.clear();
     d_hk_ = d_tk_ = nullptr;
+    d_ref_ = nullptr;
+    if (d_refpath_) hipFree(d_refpath_);
+    d_refpath_ = nullptr;
+    refpath_cap_ = 0;
+    ref_rows_ = ref_cols_ = ref_offset_ = 0;
     DropChains();
     // (the history buffers and the recording switches belong to the handle, not to the upload)
     double* const hist = A_.hist;
@@ -1093,6 +1198,8 @@ class Engine final : public EngineBase {
     if (d_stage_) hipFree(d_stage_);
     d_stage_ = nullptr;
     stage_cap_ = 0;
+    if (d_refpath_) hipFree(d_refpath_);
+    d_refpath_ = nullptr;
     if (d_counter_) hipFree(d_counter_);
     if (h_counter_) hipHostFree((void*)h_counter_);
     for (auto& e : prof_ev_) hipEventDestroy(e);
@@ -1313,6 +1420,14 @@ class Engine final : public EngineBase {
     }
     ALTRO_TRY(Alloc(&d_list_[0], bp));
     ALTRO_TRY(Alloc(&d_list_[1], bp));
+    // the reference-term records, only for a problem with a tracking cost (a group marked kParPerKnot)
+    bool tracking = false;
+    for (int k = 0; k <= N_; ++k) tracking = tracking || pd_.grp[pd_.cls[knot_class_[k]].cost_group].q_pi == kParPerKnot;
+    if (tracking) {
+      ALTRO_TRY(Alloc(&d_ref_, (size_t)(N_ + 1) * kRefRT * bp));
+      A_.ref = d_ref_;
+      A_.ref_rt = kRefRT;
+    }
     return ALTRO_OK;
   }
   // the chains of batched sweeps: how many, their streams, and whether those run side by side
@@ -1663,6 +1778,12 @@ class Engine final : public EngineBase {
     if (st == ALTRO_OK) st = SetInitialStateImpl(s);
     if (st == ALTRO_OK) st = SetKnotTimesImpl(s);
     if (st == ALTRO_OK) st = SetTrajectoryImpl(s);
+    if (st == ALTRO_OK && s.ref_rows > 0) {  // altro_set_reference / altro_set_reference_offset issued before the upload
+      st = SetReference(s.ref_X.data(), s.ref_U.empty() ? nullptr : s.ref_U.data(), s.ref_rows, s.ref_per_instance, 0);
+      if (st == ALTRO_OK && s.ref_offset > 0) st = SetReferenceOffset(s.ref_offset);
+    } else if (st == ALTRO_OK) {
+      ref_offset_ = s.ref_offset;
+    }
     // (a failed upload leaves the engine as it was before it -- Upload() drops whatever a failed UploadImpl built: the
     //  C-ABI keeps the handle "not uploaded" and the next call uploads again instead of meeting "problem definition changed")
     return st;
@@ -1744,7 +1865,7 @@ class Engine final : public EngineBase {
 
   // One solve: the steps below, in this order.
   altro_status Solve(const altro_options& o, int mode) {
-    if (!StepOk()) return ALTRO_NOT_READY;
+    if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     SolveRun r;
     ALTRO_TRY(StartRun(r, o, mode));
@@ -1854,8 +1975,9 @@ class Engine final : public EngineBase {
     // ... nor with cost-to-go records: every shadow column writes P, p into its own CTG column, and neither
     // k_seg_fixup nor the twins' commit copy those back -- altro_get_ctg would return the records of the backward pass at which
     // the instance's OWN column retired
+    // ... nor with a tracking cost: a shadow column would need the reference-term records of its instance (copy_column)
     r.seg_on = seg_total_ > 0 && !A_.hist && !A_.record_ctg && !r.d.fast_forward_stalls && r.C * kBlock <= seg_total_ && !r.loop_on &&
-               sw_.spec_mode == kSpecAuto;  // (the persistent kernel's variants that know the segments: default modes only)
+               !A_.ref && sw_.spec_mode == kSpecAuto;  // (the persistent kernel's variants that know the segments: default modes only)
     r.seg_capc = r.seg_on ? (seg_total_ / r.C) / kBlock * kBlock : 0;
     if (r.seg_on) ALTRO_HIP_CHECK(hipMemsetAsync(d_seg_cursor_, 0, kMaxChains * sizeof(int), stream_));
     // may a sweep of a chain split streaks (SplitsIn)?  Only while the batch has room: a streak split while most of the batch
@@ -1984,15 +2106,21 @@ class Engine final : public EngineBase {
     PoisonLds();
     // (small models only: their expansions are HBM-bound; the 12-state model's are compute-bound and pay for the idle
     //  lanes of a dense launch: config 4 +13 %)
+    // (a handle with a tracking cost: the twin kernel that reads the reference-term records, same launches)
+    auto expansions = [&](dim3 grid, int all, int* order_list, int* order_count) {
+      if (A.ref)
+        hipLaunchKernelGGL((k_expansions_trk<T, M>), grid, dim3(kBlock), 0, ch.st, A, d_pd_, all, order_list, order_count);
+      else
+        hipLaunchKernelGGL((k_expansions<T, M>), grid, dim3(kBlock), 0, ch.st, A, d_pd_, all, order_list, order_count);
+    };
     if (i > 0 && sw_.dense_expansions && !kKdgEligible && 4 * (long long)std::max(1, ch.known) >= span) {  // (thresholds 1/2 ... 1/16 measured: 1/4 ... 1/8 best)
       // a good part of the chain is still iterating: lane = instance (coalesced rows and records), and the list is
       // rebuilt in runs of neighbouring instances for the two kernels that follow (see k_expansions); the launch also
       // covers the chain's slice of shadow columns (instance_of_slot)
-      hipLaunchKernelGGL((k_expansions<T, M>), dim3((span + (ch.split_seen ? r.seg_capc : 0) + kBlock - 1) / kBlock, N_ + 1), dim3(kBlock), 0, ch.st, A, d_pd_, 2,
-                         ListOf(r, i % 2, ch), ch.d_cnt + (r.max_sweeps + 12) + i);
+      expansions(dim3((span + (ch.split_seen ? r.seg_capc : 0) + kBlock - 1) / kBlock, N_ + 1), 2, ListOf(r, i % 2, ch),
+                 ch.d_cnt + (r.max_sweeps + 12) + i);
     } else {
-      hipLaunchKernelGGL((k_expansions<T, M>), dim3(gridB.x, N_ + 1), dim3(kBlock), 0, ch.st, A, d_pd_, 0, (int*)nullptr,
-                         (int*)nullptr);
+      expansions(dim3(gridB.x, N_ + 1), 0, nullptr, nullptr);
     }
     RecordEvent(r, ch);
     LaunchBackward(A, r.d, 0, ninst);
@@ -2400,6 +2528,12 @@ class Engine final : public EngineBase {
   static constexpr bool kTimeVarying = model_knot_path<M>::value;
   static constexpr int kModelCount = model_list<M>::type::size;
   float *d_hk_ = nullptr, *d_tk_ = nullptr;  // per-knot steps / times (SetKnotTimes), owned through allocs_
+  // the reference of the tracking costs, ALWAYS fp64: path points [row][cols][kRefPT] (cols = 1 shared, B per instance; the
+  // engine's own allocation, it grows with the path) and term records [k][Bp][kRefRT] (owned through allocs_; = A_.ref)
+  static constexpr int kRefPT = RefPathRecord(n, m), kRefRT = RefTermRecord(n, m);
+  double *d_refpath_ = nullptr, *d_ref_ = nullptr;
+  size_t refpath_cap_ = 0;
+  int ref_rows_ = 0, ref_cols_ = 0, ref_offset_ = 0;
   altro_desc desc_;
   int B_ = 0, Bp_ = 0, N_ = 0;
   bool uploaded_ = false;

@@ -140,7 +140,7 @@ ALTRO_DEV void hist_push(const DevArrays<T>& A, int b) {
 // iLQR::UpdateExpansionsBlock (ilqr.hpp:670-677) over grid (instance, knot)
 // -------------------------------------------------------------------------------------------------
 // One (instance, knot) of iLQR::UpdateExpansions: returns the knot cost, writes the record.
-template <class T, class M>
+template <class T, class M, class Ctx = CtxG<T>>
 ALTRO_DEV T expansion_body(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, int b, int k) {
   constexpr int n = M::n, m = M::m;
   using R = Rec<T, n, m>;
@@ -153,7 +153,7 @@ ALTRO_DEV T expansion_body(const DevArrays<T>& A, const ProblemDesc* __restrict_
 #pragma unroll
   for (int i = 0; i < R::mP; ++i) ur[i] = T(0);
   if (k < N) load_rec<T, R::mP>(RECP(A.U, k, R::mP), ur);
-  CtxG<T> C(A, b);
+  Ctx C(A, b, k);
   T E[R::EP];
 #pragma unroll
   for (int e = 0; e < R::EP; ++e) E[e] = T(0);
@@ -179,9 +179,11 @@ ALTRO_DEV void publish_count(const DevArrays<T>& A) {
 // HBM-bound).  The blocks of knot 0 also REBUILD the list for the backward and forward kernels of the sweep: runs of
 // up to 64 instances in index order (the runs themselves land in arbitrary order), so that the instances of a
 // workgroup are neighbours there too.
-template <class T, class M>
-__global__ __launch_bounds__(kBlock) void k_expansions(DevArrays<T> A, const ProblemDesc* __restrict__ pd,
-                                                       int all, int* order_list = nullptr, int* order_count = nullptr) {
+// (the kernel's body over the context type: k_expansions with CtxG, k_expansions_trk -- a handle with a tracking cost --
+//  with CtxGK)
+template <class T, class M, class Ctx>
+ALTRO_DEV void expansions_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, int all, int* order_list,
+                                 int* order_count) {
   const int b = instance_of_slot(A, blockIdx.x * kBlock + threadIdx.x, all);
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) publish_count(A);
   if (all == 2 && blockIdx.y == 0) {
@@ -194,7 +196,17 @@ __global__ __launch_bounds__(kBlock) void k_expansions(DevArrays<T> A, const Pro
     }
   }
   if (b < 0) return;
-  expansion_body<T, M>(A, pd, b, blockIdx.y);
+  expansion_body<T, M, Ctx>(A, pd, b, blockIdx.y);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_expansions(DevArrays<T> A, const ProblemDesc* __restrict__ pd,
+                                                       int all, int* order_list = nullptr, int* order_count = nullptr) {
+  expansions_kernel<T, M, CtxG<T>>(A, pd, all, order_list, order_count);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_expansions_trk(DevArrays<T> A, const ProblemDesc* __restrict__ pd,
+                                                           int all, int* order_list = nullptr, int* order_count = nullptr) {
+  expansions_kernel<T, M, CtxGK<T>>(A, pd, all, order_list, order_count);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1340,8 +1352,8 @@ __global__ __launch_bounds__(kBlock) void k_rollout(DevArrays<T> A, const Proble
 // iLQR::Cost (ilqr.hpp:326-334, 758-763): per-knot costs over grid (instance, knot) + c_ stores,
 // then a per-instance ordered sum.
 // -------------------------------------------------------------------------------------------------
-template <class T, class M>
-__global__ __launch_bounds__(kBlock) void k_knot_costs(DevArrays<T> A, const ProblemDesc* __restrict__ pd) {
+template <class T, class M, class Ctx>
+ALTRO_DEV void knot_costs_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd) {
   constexpr int n = M::n, m = M::m;
   using R = Rec<T, n, m>;
   const int b = blockIdx.x * kBlock + threadIdx.x;
@@ -1353,11 +1365,19 @@ __global__ __launch_bounds__(kBlock) void k_knot_costs(DevArrays<T> A, const Pro
 #pragma unroll
   for (int i = 0; i < R::mP; ++i) u[i] = T(0);
   if (k < A.N) load_rec<T, R::mP>(RECP(A.U, k, R::mP), u);
-  CtxG<T> C(A, b);
+  Ctx C(A, b, k);
   T v;
   int rb;
   const KnotClass& kc = class_of_knot(A, pd, k, &rb);
   A.costs[(unsigned)k * Bp + (unsigned)b] = knot_cost<T, n, m, true>(C, pd, kc, rb, x, u, &v);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_knot_costs(DevArrays<T> A, const ProblemDesc* __restrict__ pd) {
+  knot_costs_kernel<T, M, CtxG<T>>(A, pd);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_knot_costs_trk(DevArrays<T> A, const ProblemDesc* __restrict__ pd) {
+  knot_costs_kernel<T, M, CtxGK<T>>(A, pd);
 }
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_sum_costs(DevArrays<T> A, double* out) {
@@ -1788,6 +1808,8 @@ ALTRO_DEV bool conv_stats_and_done_pre(const DevArrays<T>& A, const DevOpts& o, 
 //   twin clone    (tw_enter_clone)    x    x    x      x      x                   x      kColTwinClone
 //   twin commit   (tw_commit)         x         x      x             x            x      kColTwinCommit
 //   k_seg_fixup                       x         x      x             x     x      x      kColSegFixup
+//   (the reference-term records of a tracking cost, DevArrays::ref: no copy copies them -- a handle that has them runs
+//    neither segments nor the persistent kernel, Engine::PlanRun / FusedOk, so no shadow column ever reads a record)
 //
 // A CLONE starts a shadow column that has held nothing of the instance, so it needs the initial state and the per-instance
 // parameters; nothing reads the records it lacks before an expansion step and a backward pass have rewritten them.  The
@@ -2206,6 +2228,10 @@ ALTRO_DEV void rollout_run(const Ctx& C, const ProblemDesc* pd, const DevArrays<
     const T* K = kd + R::oK;
     const T* d = kd + R::oD;
     const int rb = run.rowbase + (k - run.k_begin) * nrows;
+    decltype(auto) Ck = C.at(k);  // (the knot of a tracking group's terms; CtxL: C itself)
+    if constexpr (Ctx::kKnotTerms) {
+      if (RC.per_knot) load_knot_terms<T, n, m>(Ck, pd->grp[kc.cost_group], RC);
+    }
     // duals / penalty of the bound rows: loaded up front so that one wait covers the whole knot
     T blam[2 * m], brho = T(1);
     if (kHasB) {
@@ -2230,7 +2256,7 @@ ALTRO_DEV void rollout_run(const Ctx& C, const ProblemDesc* pd, const DevArrays<
       }
       gs += (double)(gnum / gden);
       if (FK == kFastGeneric) {
-        J += (double)knot_cost_fast<T, n, m>(C, pd, kc, RC, rb, xb, ub);
+        J += (double)knot_cost_fast<T, n, m>(Ck, pd, kc, RC, rb, xb, ub);
       } else {
         // quadratic cost (diagonal Q, R guaranteed by the host for the fast kinds)
         T Jk = T(0);
@@ -2338,10 +2364,23 @@ ALTRO_DEV void rollout_run(const Ctx& C, const ProblemDesc* pd, const DevArrays<
 
 // Single-wave forward pass that reads everything from global memory: the fallback when the staged block of
 // one instance exceeds the LDS, or line_search_max_iterations > 20 (rounds of 20 trials).
+// (k_forward_trk: the same body over CtxGK, for a handle with a tracking cost)
+template <class T, class M, class Ctx>
+ALTRO_DEV void forward_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, const DevOpts& o, int mode, int all,
+                              int per_wave);
 template <class T, class M>
 __global__ __launch_bounds__(kBlock) void k_forward(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o,
                                                     int mode, int all, int per_wave) {
-  using Ctx = CtxG<T>;
+  forward_kernel<T, M, CtxG<T>>(A, pd, o, mode, all, per_wave);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_forward_trk(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o,
+                                                        int mode, int all, int per_wave) {
+  forward_kernel<T, M, CtxGK<T>>(A, pd, o, mode, all, per_wave);
+}
+template <class T, class M, class Ctx>
+ALTRO_DEV void forward_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, const DevOpts& o, int mode, int all,
+                              int per_wave) {
   constexpr bool LDS = false;
   constexpr int n = M::n, m = M::m, nm = n + m;
   constexpr int LS = kLineSearchLanes;
@@ -2358,7 +2397,7 @@ __global__ __launch_bounds__(kBlock) void k_forward(DevArrays<T> A, const Proble
 
   using R = Rec<T, n, m>;
   const T *sX = nullptr, *sU = nullptr, *sKD = nullptr;  // this variant reads from global memory
-  const CtxG<T> C(A, b);
+  const Ctx C(A, b);
   const T hh = T(pd->hstep);
 
   const double J0 = A.J0[b];
@@ -2415,7 +2454,7 @@ __global__ __launch_bounds__(kBlock) void k_forward(DevArrays<T> A, const Proble
       for (int i = 0; i < m; ++i) uz[i] = T(0);
       const KnotRun runN = pd->runs[pd->nruns - 1];  // the terminal knot closes the last run
       const KnotClass& kcN = pd->cls[runN.cls];
-      J += (double)knot_cost<T, n, m, false>(C, pd, kcN, runN.rowbase + (N - runN.k_begin) * kcN.nrows, xb, uz, nullptr);
+      J += (double)knot_cost<T, n, m, false>(C.at(N), pd, kcN, runN.rowbase + (N - runN.k_begin) * kcN.nrows, xb, uz, nullptr);
       if (valid) {
         T* cand = A.trial + (tb + (unsigned)N * (unsigned)(LS * nm));
 #pragma unroll
@@ -2476,7 +2515,7 @@ __global__ __launch_bounds__(kBlock) void k_forward(DevArrays<T> A, const Proble
       int rb;
       const KnotClass& kc = class_of_knot(A, pd, k, &rb);
       T v;
-      knot_cost<T, n, m, true>(C, pd, kc, rb, xs, us, &v);
+      knot_cost<T, n, m, true>(C.at(k), pd, kc, rb, xs, us, &v);
       viol = max_(viol, v);
       if (accepted) {
         T xr[R::nP], ur[R::mP];
@@ -5172,6 +5211,108 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_advance(DevArrays<T> A, Mpc
 }
 
 // -------------------------------------------------------------------------------------------------
+// The reference path of the tracking costs (include/altro_tracking.h: altro_set_lqr_tracking_cost, altro_set_reference).
+//
+// k_ref_pack brings the caller's rows -- Xref[cols][rows][n], Uref[cols][rows][m] (null: zeros), cols = 1 or B -- into path
+// points path[(row * cols + col) * PT + e], e = x[0..n) | u[0..m), PT = RefPathRecord(n, m): batch-minor at record
+// granularity, 16-byte aligned, like X.
+//
+// k_ref_terms computes, for knot k = blockIdx.y (wave-uniform) and column b, the terms of LQRCost(Q, R, xref, uref)
+// (examples/quadratic_cost.hpp:29-39) at path row min(offset + k, rows - 1): q = -Q xref, r = -R uref,
+// c = 0.5 xref'Q xref + 0.5 uref'R uref, and writes the record ref[(k * Bp + b) * RT + e], e = q | r | c, RT =
+// RefTermRecord(n, m), with 16-byte stores.  THE ONLY PLACE these terms are computed.  The arithmetic is CompileProblem's
+// linear_term (altro_problem.hpp) operation by operation, in T like there, WITHOUT CONTRACTION: sums from zero, left to right,
+// then the negation -- a constant path leaves the bits an ordinary cost group holds in the parameter pool.  The library is
+// built with -ffp-contract=fast, under which the compiler disregards a contraction pragma; every product therefore passes
+// through pin() before it is added, which no multiply-add can be formed across.  Knots whose cost
+// is no tracking cost get a zero record.  Q, R and the row index depend on the knot alone: scalar loads.
+// -------------------------------------------------------------------------------------------------
+template <int n, int m>
+__global__ __launch_bounds__(kBlock) void k_ref_pack(const double* __restrict__ Xref, const double* __restrict__ Uref,
+                                                     double* __restrict__ path, int rows, int cols) {
+  constexpr int PT = RefPathRecord(n, m);
+  const int c = blockIdx.x * kBlock + threadIdx.x, row = blockIdx.y;
+  if (c >= cols) return;
+  double p[PT];
+#pragma unroll
+  for (int e = 0; e < PT; ++e) p[e] = 0.0;
+  const size_t src = (size_t)c * (size_t)rows + (size_t)row;
+#pragma unroll
+  for (int i = 0; i < n; ++i) p[i] = Xref[src * n + i];
+  if (Uref) {
+#pragma unroll
+    for (int i = 0; i < m; ++i) p[n + i] = Uref[src * m + i];
+  }
+  store_rec<double, PT>(path + ((size_t)row * (size_t)cols + (size_t)c) * PT, p);
+}
+template <class T, int n, int m>
+__global__ __launch_bounds__(kBlock) void k_ref_terms(DevArrays<T> A, const ProblemDesc* __restrict__ pd,
+                                                      const double* __restrict__ path, double* __restrict__ ref, int rows,
+                                                      int cols, int offset) {
+  constexpr int PT = RefPathRecord(n, m), RT = RefTermRecord(n, m);
+  const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
+  if (b >= A.B) return;
+  const CostGroupDesc& g = pd->grp[pd->cls[A.knot_class[k]].cost_group];
+  double rec[RT];
+#pragma unroll
+  for (int e = 0; e < RT; ++e) rec[e] = 0.0;
+  if (g.q_pi == kParPerKnot) {
+    const long long want = (long long)offset + (long long)k;
+    const int row = (int)(want < (long long)(rows - 1) ? want : (long long)(rows - 1));  // the end of the path is held
+    const int col = cols > 1 ? b : 0;
+    double p[PT];
+    load_rec<double, PT>(path + ((size_t)row * (size_t)cols + (size_t)col) * PT, p);
+    T xr[n], ur[m], Wx[n > m ? n : m];
+#pragma unroll
+    for (int i = 0; i < n; ++i) xr[i] = T(p[i]);
+#pragma unroll
+    for (int i = 0; i < m; ++i) ur[i] = T(p[n + i]);
+    T xQx = T(0), uRu = T(0);
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      T sacc = T(0);
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        T p = A.pool[g.Q_off + i + j * n] * xr[j];
+        pin(p);
+        sacc += p;
+      }
+      Wx[i] = sacc;
+      rec[i] = (double)(-sacc);
+    }
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      T p = xr[i] * Wx[i];
+      pin(p);
+      xQx += p;
+    }
+#pragma unroll
+    for (int i = 0; i < m; ++i) {
+      T sacc = T(0);
+#pragma unroll
+      for (int j = 0; j < m; ++j) {
+        T p = A.pool[g.R_off + i + j * m] * ur[j];
+        pin(p);
+        sacc += p;
+      }
+      Wx[i] = sacc;
+      rec[n + i] = (double)(-sacc);
+    }
+#pragma unroll
+    for (int i = 0; i < m; ++i) {
+      T p = ur[i] * Wx[i];
+      pin(p);
+      uRu += p;
+    }
+    T hx = T(0.5) * xQx, hu = T(0.5) * uRu;
+    pin(hx);
+    pin(hu);
+    rec[n + m] = (double)(hx + hu);
+  }
+  store_rec<double, RT>(ref + ((size_t)(unsigned)k * (size_t)A.Bp + (size_t)b) * RT, rec);
+}
+
+// -------------------------------------------------------------------------------------------------
 // Closed-loop tracking (include/altro_mpc.h, altro_mpc_track): iLQR::RolloutClosedLoop (ilqr.hpp:468-499) with alpha = 0
 // for every (instance, disturbance sample), ONE LANE EACH: x_0 = x0 + dx0, then per knot u = Ubar + K (x - Xbar), clipped
 // where bounds are given, x+ = f_d(x, u) + w, the forward pass's bound checks, and along the way the objective cost, the
@@ -5191,7 +5332,8 @@ template <class T>
 struct CtxTrack {
   const DevArrays<T>& A;
   unsigned b;
-  ALTRO_DEV CtxTrack(const DevArrays<T>& A_, int b_) : A(A_), b((unsigned)b_) {}
+  ALTRO_DEV CtxTrack(const DevArrays<T>& A_, int b_, int = 0) : A(A_), b((unsigned)b_) {}
+  ALTRO_DEV const CtxTrack& at(int) const { return *this; }
   ALTRO_DEV T par(int per_instance, int off, int i) const {
     return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
   }
@@ -5200,8 +5342,33 @@ struct CtxTrack {
   ALTRO_DEV T pen(int) const { return T(1); }
   ALTRO_DEV void store_c(int, T) const {}
 };
+template <class T>
+struct CtxTrackK {  // CtxTrack that knows its knot: the terms of a tracking cost (k_mpc_track_trk)
+  const DevArrays<T>& A;
+  unsigned b, k;
+  ALTRO_DEV CtxTrackK(const DevArrays<T>& A_, int b_, int k_ = 0) : A(A_), b((unsigned)b_), k((unsigned)k_) {}
+  ALTRO_DEV CtxTrackK at(int k_) const { return CtxTrackK(A, (int)b, k_); }
+  ALTRO_DEV T par(int per_instance, int off, int i) const {
+    if (per_instance == kParPerKnot) return ref_term(A, k, b, off + i);
+    return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
+  }
+  ALTRO_DEV T shared(int off) const { return A.pool[off]; }
+  ALTRO_DEV T lam(int) const { return T(0); }
+  ALTRO_DEV T pen(int) const { return T(1); }
+  ALTRO_DEV void store_c(int, T) const {}
+};
+template <class T, class M, class Ctx>
+ALTRO_DEV void mpc_track_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, const TrackArgs& g);
 template <class T, class M>
 __global__ __launch_bounds__(kBlock) void k_mpc_track(DevArrays<T> A, const ProblemDesc* __restrict__ pd, TrackArgs g) {
+  mpc_track_kernel<T, M, CtxTrack<T>>(A, pd, g);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_mpc_track_trk(DevArrays<T> A, const ProblemDesc* __restrict__ pd, TrackArgs g) {
+  mpc_track_kernel<T, M, CtxTrackK<T>>(A, pd, g);
+}
+template <class T, class M, class Ctx>
+ALTRO_DEV void mpc_track_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, const TrackArgs& g) {
   constexpr int n = M::n, m = M::m;
   using R = Rec<T, n, m>;
   using RS = rec_scalar_t<T, M>;
@@ -5218,7 +5385,7 @@ __global__ __launch_bounds__(kBlock) void k_mpc_track(DevArrays<T> A, const Prob
   const double* const wl = g.w ? g.w + lane * (size_t)steps * n : nullptr;
   const bool clip = g.u_lo != nullptr;
   const T state_max2 = T(g.state_max * g.state_max), control_max2 = T(g.control_max * g.control_max);
-  const CtxTrack<T> C(A, b);
+  const Ctx C(A, b);
 
   T x[R::nP], xk[R::nP], uk[R::mP], xkn[R::nP], ukn[R::mP], u[R::mP], xn[n], wk[n];
   RS kd[RR::KP], kdn[RR::KP];
@@ -5274,9 +5441,10 @@ __global__ __launch_bounds__(kBlock) void k_mpc_track(DevArrays<T> A, const Prob
     if (want_stats) {
       int rb;
       const KnotClass& kc = class_of_knot(A, pd, k, &rb);
-      const T Jk = quad_cost<T, n, m>(C, pd->grp[kc.cost_group], x, u);
+      decltype(auto) Ck = C.at(k);
+      const T Jk = quad_cost<T, n, m>(Ck, pd->grp[kc.cost_group], x, u);
       T v = T(0);
-      knot_cost<T, n, m, true>(C, pd, kc, rb, x, u, &v);
+      knot_cost<T, n, m, true>(Ck, pd, kc, rb, x, u, &v);
       if (alive) {
         cost += (double)Jk;
         viol = max_(viol, v);
@@ -5340,9 +5508,10 @@ __global__ __launch_bounds__(kBlock) void k_mpc_track(DevArrays<T> A, const Prob
     for (int i = 0; i < R::mP; ++i) u[i] = T(0);
     int rb;
     const KnotClass& kc = class_of_knot(A, pd, N, &rb);
-    cost += (double)quad_cost<T, n, m>(C, pd->grp[kc.cost_group], x, u);
+    decltype(auto) CN = C.at(N);
+    cost += (double)quad_cost<T, n, m>(CN, pd->grp[kc.cost_group], x, u);
     T v = T(0);
-    knot_cost<T, n, m, true>(C, pd, kc, rb, x, u, &v);
+    knot_cost<T, n, m, true>(CN, pd, kc, rb, x, u, &v);
     viol = max_(viol, v);
   }
   TrackStats st;

@@ -119,6 +119,17 @@ CompiledProblem<T> CompileProblem(const ProblemSpec& s, int n, int m, int N, int
     for (int j = 0; j < m; ++j)
       for (int i = 0; i < m; ++i)
         if (i != j && R[i + j * m] != T(0)) g.r_diag = 0;
+    if (c.tracking) {
+      // LQRCost(Q, R, xref_k, uref_k) with the handle's reference at every knot (altro_set_lqr_tracking_cost): the terms
+      // live in the reference-term records, which k_ref_terms fills -- element q_off / r_off / c_off of the knot's record
+      g.q_pi = g.r_pi = g.c_pi = kParPerKnot;
+      g.q_off = 0;
+      g.r_off = n;
+      g.c_off = n + m;
+      group_of_cost[ci] = pd.ngroups;
+      pd.grp[pd.ngroups++] = g;
+      continue;
+    }
     const bool xpi = (c.per_instance & 1) != 0, upi = (c.per_instance & 2) != 0;
     g.q_pi = xpi;
     g.r_pi = upi;

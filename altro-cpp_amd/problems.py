@@ -50,6 +50,60 @@ def unicycle_turn90(make, batch=1, N=100, dtype=F64, constraints=True, xf=None, 
     return s
 
 
+def slalom_path(batch, N, rows):
+    """The reference path of tracking_slalom: (Xref [B][rows][3], Uref [B][rows][2], h).  Instance b (its parameter
+    repeats with b mod 5) drives at v = 0.6 + 0.05 b with heading theta_j = a sin(1.2 t_j), a = 0.3 + 0.05 b, t_j = j h;
+    x, y are the running sums of v cos(theta_j) h, v sin(theta_j) h from 0; uref_j = (v, 1.2 a cos(1.2 t_j))."""
+    h = _f32step(3.0, N)
+    hd = float(h)
+    X = np.zeros((batch, rows, 3))
+    U = np.zeros((batch, rows, 2))
+    t = np.arange(rows) * hd
+    for b in range(batch):
+        p = b % 5
+        a, v = 0.3 + 0.05 * p, 0.6 + 0.05 * p
+        th = a * np.sin(1.2 * t)
+        X[b, 1:, 0] = np.cumsum(v * np.cos(th) * hd)[:-1]
+        X[b, 1:, 1] = np.cumsum(v * np.sin(th) * hd)[:-1]
+        X[b, :, 2] = th
+        U[b, :, 0] = v
+        U[b, :, 1] = 1.2 * a * np.cos(1.2 * t)
+    return X, U, h
+
+
+def tracking_slalom(make, batch=1, N=24, rows=None, offset=0, bounds=True, dtype=F64, per_knot=False, **kw):
+    """A unicycle following a slalom path (slalom_path) over a window of N + 1 rows that starts at row ``offset`` and holds
+    the path's last row: LQR tracking cost Q = diag(10, 10, 1) h, R = 0.1 h I on [0, N), Qf = diag(10, 10, 1), R = 0 on
+    knot N, control bound +-0.7 on [0, N), x0 = xref[offset] + (0, 0.1, 0), initial guess U = (0.1, 0.1).
+
+    ``per_knot``: the reference's idiom instead -- one set_lqr_cost per knot from the same path rows (what the CPU oracle
+    takes, and what exceeds the cost groups of the device library)."""
+    rows = N + 1 + 12 if rows is None else rows
+    s = make(3, 2, N, batch, dtype)
+    Xref, Uref, h = slalom_path(batch, N, rows)
+    hd = float(h)
+    Q = np.diag([10.0, 10.0, 1.0]) * hd
+    R = np.eye(2) * (0.1 * hd)
+    Qf = np.diag([10.0, 10.0, 1.0])
+    s.set_model(MODEL_UNICYCLE)
+    s.set_uniform_step(h)
+    if per_knot:
+        for k in range(N + 1):
+            row = min(offset + k, rows - 1)
+            s.set_lqr_cost(k, k + 1, Q if k < N else Qf, R if k < N else R * 0, Xref[:, row], Uref[:, row])
+    else:
+        s.set_lqr_tracking_cost(0, N, Q, R)
+        s.set_lqr_tracking_cost(N, N + 1, Qf, R * 0)
+        s.set_reference(Xref, Uref)
+        if offset:
+            s.set_reference_offset(offset)
+    if bounds:
+        s.add_control_bound(0, N, [-0.7, -0.7], [0.7, 0.7])
+    s.set_initial_state(Xref[:, min(offset, rows - 1)] + np.array([0.0, 0.1, 0.0]))
+    s.set_trajectory(None, np.tile(np.array([0.1, 0.1]), (N, 1)))
+    return s
+
+
 THREE_OBSTACLE_CIRCLES = np.array([[0.25 * 3.0, 0.25 * 3.0, 0.425],
                                    [0.5 * 3.0, 0.5 * 3.0, 0.425],
                                    [0.75 * 3.0, 0.75 * 3.0, 0.425]])

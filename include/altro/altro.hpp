@@ -36,6 +36,7 @@
 
 #include "../altro_hip.h"
 #include "../altro_mpc.h"
+#include "../altro_tracking.h"
 
 namespace altro {
 
@@ -730,7 +731,21 @@ class Problem {
     bool per_knot_models = false;
     for (int k = 0; k < N_; ++k) per_knot_models = per_knot_models || knot_model_[k] != 0;
     if (per_knot_models) Check(h, altro_set_knot_models(h, knot_model_.data(), N_), "altro_set_knot_models");
+    // The library holds a few DISTINCT cost functions (kCostFunctionLimit).  A problem whose runs of identical costs fit
+    // is emitted run by run, as always.  One that does not -- the reference's path-following idiom, SetCostFunction(LQRCost(
+    // Q, R, xref_k, uref_k), k) with a reference of its own on every knot -- is emitted as TRACKING ranges
+    // (include/altro_tracking.h): consecutive LQR knots that agree in Q, R, the terminal flag and the per-instance shape
+    // of their references become one range, and the references travel as one path of N + 1 rows, row k = knot k's.
+    int runs = 0;
     for (int k = 0; k <= N_;) {
+      int e = k + 1;
+      while (e <= N_ && costs_[e] == costs_[k]) ++e;
+      ++runs;
+      k = e;
+    }
+    const bool tracking = runs > kCostFunctionLimit;
+    if (tracking) ApplyTrackingCosts(h);
+    for (int k = tracking ? N_ + 1 : 0; k <= N_;) {
       int e = k + 1;
       while (e <= N_ && costs_[e] == costs_[k]) ++e;
       const auto& c = costs_[k];
@@ -769,8 +784,56 @@ class Problem {
   }
   int StateDimension() const { return n_; }
   int ControlDimension() const { return m_; }
+  static constexpr int kCostFunctionLimit = 8;  // distinct cost functions of one problem in the library (its cost groups)
 
  private:
+  // the costs of a problem with more runs of identical costs than the library holds: see Apply
+  void ApplyTrackingCosts(altro_handle h) const {
+    using detail::Check;
+    auto same_shape = [&](const examples::QuadraticCost& a, const examples::QuadraticCost& b) {
+      return !a.user && !b.user && a.Q == b.Q && a.R == b.R && a.terminal == b.terminal && a.xref.size() == b.xref.size() &&
+             a.uref.size() == b.uref.size();
+    };
+    bool per_instance = false, any_tracking = false;
+    for (int k = 0; k <= N_; ++k)
+      per_instance = per_instance || (!costs_[k].user && ((int)costs_[k].xref.size() > n_ || (int)costs_[k].uref.size() > m_));
+    const int cols = per_instance ? batch_ : 1;
+    std::vector<double> Xref((size_t)cols * (N_ + 1) * n_, 0.0), Uref((size_t)cols * (N_ + 1) * m_, 0.0);
+    for (int k = 0; k <= N_;) {
+      const auto& c = costs_[k];
+      int e = k + 1;
+      if (c.user) {
+        while (e <= N_ && costs_[e] == c) ++e;
+        Check(h, altro_set_user_cost_type(h, c.user_type, k, e, c.user_params.data(), c.user_nparams,
+                                          (int)c.user_params.size() > c.user_nparams ? 1 : 0), "altro_set_user_cost_type");
+        k = e;
+        continue;
+      }
+      bool constant = true;
+      while (e <= N_ && same_shape(costs_[e], c)) {
+        constant = constant && costs_[e] == c;
+        ++e;
+      }
+      if (constant) {  // one reference for the whole range: an ordinary cost, as ever
+        const int per = ((int)c.xref.size() > n_ ? 1 : 0) | ((int)c.uref.size() > m_ ? 2 : 0);
+        Check(h, altro_set_lqr_cost(h, k, e, c.Q.data(), c.R.data(), c.xref.data(), c.uref.data(), per), "altro_set_lqr_cost");
+      } else {
+        Check(h, altro_set_lqr_tracking_cost(h, k, e, c.Q.data(), c.R.data()), "altro_set_lqr_tracking_cost");
+        any_tracking = true;
+        for (int j = k; j < e; ++j)
+          for (int b = 0; b < cols; ++b) {
+            const auto& cj = costs_[j];
+            const double* xr = cj.xref.data() + ((int)cj.xref.size() > n_ ? (size_t)b * n_ : 0);
+            const double* ur = cj.uref.data() + ((int)cj.uref.size() > m_ ? (size_t)b * m_ : 0);
+            std::copy(xr, xr + n_, Xref.begin() + ((size_t)b * (N_ + 1) + j) * n_);
+            std::copy(ur, ur + m_, Uref.begin() + ((size_t)b * (N_ + 1) + j) * m_);
+          }
+      }
+      k = e;
+    }
+    if (any_tracking)
+      Check(h, altro_set_reference(h, Xref.data(), Uref.data(), N_ + 1, per_instance ? 1 : 0), "altro_set_reference");
+  }
   void Range(int k) const {
     if (k < 0 || k > N_) throw std::runtime_error("Invalid knot point index.");
   }
@@ -1306,6 +1369,21 @@ class AugmentedLagrangianiLQR {
     ilqr_solver_.PushOptions();  // (rows that start afresh take the caller's initial_penalty)
     detail::Check(Handle(), altro_mpc_advance(Handle(), shift, x0, 1, w), "altro_mpc_advance");
     ilqr_solver_.Pull(true, false);
+  }
+  // The reference path of the tracking costs (include/altro_tracking.h): Xref [rows][n], Uref [rows][m] (null: zeros), or
+  // [B][rows][.] with per_instance; knot k follows row min(offset + k, rows - 1), and AdvanceHorizon moves the offset along.
+  // A problem whose per-knot SetCostFunction loop was emitted as tracking ranges holds the N + 1 rows of that loop; a longer
+  // path set here replaces them.
+  void SetReference(const double* Xref, const double* Uref, int rows, bool per_instance = false) {
+    detail::Check(Handle(), altro_set_reference(Handle(), Xref, Uref, rows, per_instance ? 1 : 0), "altro_set_reference");
+  }
+  void SetReferenceOffset(int offset) {
+    detail::Check(Handle(), altro_set_reference_offset(Handle(), offset), "altro_set_reference_offset");
+  }
+  int GetReferenceOffset() {
+    int offset = 0;
+    detail::Check(Handle(), altro_get_reference_offset(Handle(), &offset), "altro_get_reference_offset");
+    return offset;
   }
   // Between two solves (include/altro_mpc.h): the plant under the solved plan's feedback policy, simulated ON THE DEVICE for
   // `steps` knots and `samples` disturbance draws per instance -- what a caller of the reference composes on the host from

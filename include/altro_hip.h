@@ -300,6 +300,10 @@ altro_status altro_set_lqr_cost(altro_handle h, int k_begin, int k_end, const do
                                 const double* R, const double* xref, const double* uref,
                                 int per_instance);
 
+/* A different xref_k, uref_k on every knot -- the reference's per-knot loop of SetCostFunction(LQRCost(Q, R, xref_k,
+ * uref_k), k) -- is a TRACKING COST with the references on the device: include/altro_tracking.h (the entries live in a header
+ * of their own because the CPU oracle, which mirrors every function of this one, keeps a cost per knot and needs none). */
+
 /* Problem::SetCostFunction(std::make_shared<UserCost>(params), k) for k_begin <= k < k_end (problem.hpp:113-127)
  * with the UserCost of the handle's user model (altro_register_model_source).  params: UserCost::nparams doubles,
  * [B][nparams] when per_instance != 0.  The last cost set on a knot wins, whichever kind. */

@@ -17,8 +17,11 @@
  *                     takes lambda and rho of its rows at src; attached to k only, its rows start afresh -- lambda = 0,
  *                     rho = options.initial_penalty if that is > 0, else 1 (a new ConstraintValues,
  *                     altro/constraints/constraint_values.hpp:39-51).  The terminal knot's rows stay.
+ *   reference window  on a handle with a tracking cost (altro_set_lqr_tracking_cost): offset_new = offset_old + shift, and
+ *                     the term records are recomputed on the device for the new window (altro_set_reference_offset); a
+ *                     handle without a tracking cost keeps its offset
  * Everything else stays: options, statistics, history, the guess altro_reset_trajectory restores, and the costs, which
- * remain attached to knot indices.  Expansions, knot costs, stored constraint values and cost-to-go records are not moved;
+ * remain attached to knot indices (a tracking cost's Q, R too: only its reference moves).  Expansions, knot costs, stored constraint values and cost-to-go records are not moved;
  * the next solve recomputes them (altro_get_ctg answers ALTRO_NOT_READY until then).
  *
  * Refused: shift out of range (ALTRO_INVALID_ARG); a handle with per-knot steps, times or models, or a time-varying or
