@@ -159,6 +159,7 @@ class BatchSolver:
         self._p = _prefix
         self.n, self.m, self.N, self.batch, self.dtype = int(n), int(m), int(N), int(batch), int(dtype)
         self._h = C.c_void_p()
+        self._knot_nparams = {}  # registration index of a knot constraint -> (nparams, knots)
         d = Desc(self.n, self.m, self.N, self.batch, self.dtype, int(device_id))
         f = self._fn("create")
         f.restype = C.c_int
@@ -313,6 +314,66 @@ class BatchSolver:
         c = _f64(circles)
         c = c.reshape(c.shape[0], -1) if c.ndim == 3 else c.reshape(-1)
         self.add_constraint(CON_CIRCLE, k_begin, k_end, c)
+
+    # -- knot constraints (include/altro_knot_params.h): parameters that change from knot to knot --------------------------
+    def add_knot_constraint(self, kind, k_begin, k_end, nparams, user_type=0):
+        """A constraint of ``kind`` on knots [k_begin, k_end) whose parameters at knot k are row min(offset + k, rows - 1)
+        of its track (set_constraint_track): ONE constraint however many knots.  Returns its registration index."""
+        idx = C.c_int(-1)
+        self._call("add_knot_constraint", C.c_int(kind), C.c_int(user_type), C.c_int(k_begin), C.c_int(k_end), C.c_int(nparams),
+                   C.byref(idx))
+        self._knot_nparams[idx.value] = (int(nparams), int(k_end) - int(k_begin))
+        return idx.value
+
+    def add_knot_circle_constraint(self, k_begin, k_end, ncircles, track=None):
+        """Moving circles: the track rows are (cx, cy, r) per circle -- [rows][ncircles][3] or [B][rows][ncircles][3]."""
+        idx = self.add_knot_constraint(CON_CIRCLE, k_begin, k_end, 3 * int(ncircles))
+        if track is not None:
+            t = _f64(track)
+            self.set_constraint_track(idx, t.reshape(t.shape[:-2] + (-1,)) if t.shape[-1] == 3 and t.ndim >= 3 else t)
+        return idx
+
+    def add_knot_control_bound(self, k_begin, k_end, lb=None, ub=None):
+        """A control bound that changes along the horizon: lb, ub are [rows][m] or [B][rows][m], every entry finite."""
+        if (lb is None) != (ub is None):
+            raise ValueError("a knot control bound takes lb and ub together (every entry of its track is finite)")
+        idx = self.add_knot_constraint(CON_CONTROL_BOUND, k_begin, k_end, 2 * self.m)
+        if lb is not None:
+            self.set_constraint_track(idx, np.concatenate([_f64(lb), _f64(ub)], axis=-1))
+        return idx
+
+    def _track_shape(self, index, P):
+        np_ = self._knot_nparams.get(index, (P.shape[-1], 0))[0]  # (an index this handle does not know: the library refuses it)
+        if P.ndim not in (2, 3) or P.shape[-1] != np_ or (P.ndim == 3 and P.shape[0] != self.batch):
+            raise ValueError(f"the track must have shape (rows, {np_}) or ({self.batch}, rows, {np_})")
+        return P.shape[-2], 1 if P.ndim == 3 else 0
+
+    def set_constraint_track(self, index, P):
+        """The parameter track of knot constraint ``index``: [rows][nparams], or [B][rows][nparams] per instance.  Any time
+        between solves; the window offset (set_track_offset) stays."""
+        P = _f64(P)
+        rows, per = self._track_shape(index, P)
+        self._call("set_constraint_track", C.c_int(index), _dp(P), C.c_int(rows), C.c_int(per))
+
+    def set_constraint_track_device(self, index, ptr, rows, per_instance):
+        """set_constraint_track with an fp64 array in memory of this handle's device."""
+        self._call("set_constraint_track_device", C.c_int(index), C.c_void_p(ptr or None), C.c_int(rows),
+                   C.c_int(1 if per_instance else 0))
+
+    def set_track_offset(self, offset):
+        self._call("set_track_offset", C.c_int(offset))
+
+    def get_track_offset(self):
+        off = C.c_int(0)
+        self._call("get_track_offset", C.byref(off))
+        return off.value
+
+    def get_knot_params(self, index):
+        """[B][k_end - k_begin][nparams]: the parameters of knot constraint ``index`` as the kernels read them."""
+        np_, knots = self._knot_nparams.get(index, (1, 1))  # (an unknown index: the library refuses it before it writes)
+        out = np.empty((self.batch, knots, np_))
+        self._call("get_knot_params", C.c_int(index), _dp(out))
+        return out
 
     def set_initial_state(self, x0):
         x0 = _f64(x0)

@@ -35,12 +35,13 @@
 #include "altro_common.hpp"
 #include "../../include/altro_mpc.h"
 #include "../../include/altro_tracking.h"
+#include "../../include/altro_knot_params.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 10  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 11  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -325,7 +326,14 @@ altro_status Forward(altro_handle h, F f) {
 // here, before any device work.  (After the upload the engine knows: the path may have come through
 // altro_set_reference_device.)
 bool ReferenceMissing(altro_handle h) {
-  if (h->uploaded || h->spec.ref_rows > 0) return false;
+  if (h->uploaded) return false;
+  // ... and likewise a knot constraint without a parameter track (include/altro_knot_params.h)
+  for (size_t i = 0; i < h->spec.cons.size(); ++i)
+    if (h->spec.cons[i].knot && h->spec.cons[i].track_rows < 1) {
+      h->err = "constraint " + std::to_string(i) + " is a knot constraint but has no parameter track (altro_set_constraint_track)";
+      return true;
+    }
+  if (h->spec.ref_rows > 0) return false;
   const int N = h->spec.desc.N;
   std::vector<int> tracking(N + 1, 0);
   for (const CostSpec& c : h->spec.costs)  // the last cost set on a knot wins
@@ -776,6 +784,134 @@ altro_status altro_add_constraint(altro_handle h, int kind, int k_begin, int k_e
   h->spec.cons.push_back(std::move(c));
   return ALTRO_OK;
 }
+// ---- knot constraints (include/altro_knot_params.h) ----------------------------------------------------------------------
+altro_status altro_add_knot_constraint(altro_handle h, int kind, int user_type, int k_begin, int k_end, int nparams, int* index) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (DefChanged(h) != ALTRO_OK) return ALTRO_NOT_READY;
+  const altro_desc& d = h->spec.desc;
+  if (k_begin < 0 || k_end > d.N + 1 || k_begin >= k_end) {
+    h->err = "altro_add_knot_constraint: knot range out of bounds";
+    return ALTRO_INVALID_ARG;
+  }
+  bool fits = false;
+  if (kind == ALTRO_CON_GOAL) fits = nparams == d.n;
+  else if (kind == ALTRO_CON_CONTROL_BOUND) fits = nparams == 2 * d.m;
+  else if (kind == ALTRO_CON_CIRCLE) fits = nparams > 0 && nparams % 3 == 0;
+  else if (kind == ALTRO_CON_USER) fits = nparams >= 1 && user_type >= 0;  // (the type's own count: checked with the model's source)
+  else {
+    h->err = "altro_add_knot_constraint: unknown constraint kind";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!fits) {
+    h->err = "altro_add_knot_constraint: nparams does not fit the kind (goal: n, control bound: 2m, circle: 3 per circle, "
+             "user: the type's nparams, at least one)";
+    return ALTRO_INVALID_ARG;
+  }
+  int knots = 0;
+  for (const ConSpec& c : h->spec.cons) knots += c.knot;
+  if (knots >= kMaxKnotCons) {
+    h->err = "altro_add_knot_constraint: too many knot constraints";
+    return ALTRO_UNSUPPORTED;
+  }
+  ConSpec c;
+  c.kind = kind;
+  c.k_begin = k_begin;
+  c.k_end = k_end;
+  c.nparams = nparams;
+  c.per_instance = 0;
+  c.user_type = kind == ALTRO_CON_USER ? user_type : 0;
+  c.knot = 1;
+  h->spec.cons.push_back(std::move(c));
+  if (index) *index = (int)h->spec.cons.size() - 1;
+  return ALTRO_OK;
+}
+namespace {
+// what both track setters refuse before any device work; the ConSpec of the constraint through *out
+altro_status TrackCheck(altro_handle h, int index, const void* P, int rows, const char* who, ConSpec** out) {
+  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
+    h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!P || rows < 1) {
+    h->err = std::string(who) + ": the track needs at least one row";
+    return ALTRO_INVALID_ARG;
+  }
+  *out = &h->spec.cons[index];
+  return ALTRO_OK;
+}
+}  // namespace
+altro_status altro_set_constraint_track(altro_handle h, int index, const double* P, int rows, int per_instance) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  ConSpec* c = nullptr;
+  altro_status st = TrackCheck(h, index, P, rows, "altro_set_constraint_track", &c);
+  if (st != ALTRO_OK) return st;
+  const altro_desc& d = h->spec.desc;
+  const size_t cnt = (size_t)rows * (per_instance ? d.batch : 1) * c->nparams;
+  if (c->kind == ALTRO_CON_CONTROL_BOUND) {
+    // the rows of a bound are chosen from its finite entries at problem definition (basic_constraints.hpp:138-145): a knot
+    // bound has all 2m rows on every knot, so every entry of its track is finite; ValidateBounds (:131-136) row by row
+    for (size_t e = 0; e < cnt; ++e)
+      if (!(std::abs(P[e]) < std::numeric_limits<double>::max())) {
+        h->err = "altro_set_constraint_track: every entry of a control bound's track must be finite";
+        return ALTRO_INVALID_ARG;
+      }
+    for (size_t r = 0; r < cnt / c->nparams; ++r)
+      for (int j = 0; j < d.m; ++j)
+        if (!(P[r * c->nparams + j] <= P[r * c->nparams + d.m + j])) {
+          h->err = "Lower bound isn't less than the upper bound.";
+          return ALTRO_INVALID_ARG;
+        }
+  }
+  if (h->uploaded) {  // (no copy into the recorded definition: the track lives on the device)
+    st = h->engine->SetConstraintTrack(index, P, rows, per_instance, 0);
+    if (st != ALTRO_OK) h->err = h->engine->LastError();
+    return st;
+  }
+  c->track.assign(P, P + cnt);
+  c->track_rows = rows;
+  c->track_per_instance = per_instance ? 1 : 0;
+  return ALTRO_OK;
+}
+altro_status altro_set_constraint_track_device(altro_handle h, int index, const void* P_device, int rows, int per_instance) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  ConSpec* c = nullptr;
+  const altro_status st = TrackCheck(h, index, P_device, rows, "altro_set_constraint_track_device", &c);
+  if (st != ALTRO_OK) return st;
+  return Forward(h, [&](EngineBase& e) { return e.SetConstraintTrack(index, (const double*)P_device, rows, per_instance, 1); });
+}
+altro_status altro_set_track_offset(altro_handle h, int offset) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (offset < 0) {
+    h->err = "altro_set_track_offset: the offset must not be negative";
+    return ALTRO_INVALID_ARG;
+  }
+  if (h->uploaded) {
+    const altro_status st = h->engine->SetTrackOffset(offset);
+    if (st != ALTRO_OK) h->err = h->engine->LastError();
+    return st;
+  }
+  h->spec.track_offset = offset;
+  return ALTRO_OK;
+}
+altro_status altro_get_track_offset(altro_handle h, int* offset) {
+  if (!h || !offset) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  *offset = h->uploaded ? h->engine->GetTrackOffset() : h->spec.track_offset;
+  return ALTRO_OK;
+}
+altro_status altro_get_knot_params(altro_handle h, int index, double* out) {
+  if (!h || !out) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
+    h->err = "altro_get_knot_params: constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.GetKnotParams(index, out); });
+}
 altro_status altro_set_initial_state(altro_handle h, const double* x0, int per_instance) {
   if (!h || !x0) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
@@ -1041,6 +1177,8 @@ altro_status MpcConShapes(altro_handle h, std::vector<int>* p, std::vector<int>*
           rows = h->spec.desc.n;
         } else if (c.kind == ALTRO_CON_CIRCLE) {
           rows = c.nparams / 3;
+        } else if (c.kind == ALTRO_CON_CONTROL_BOUND && c.knot) {  // (a knot bound: every entry of its track is finite)
+          rows = 2 * m;
         } else if (c.kind == ALTRO_CON_CONTROL_BOUND) {  // (the finite bounds: GetFiniteIndices, basic_constraints.hpp:138-145)
           for (int j = 0; j < 2 * m && j < c.nparams; ++j) rows += std::abs(c.params[j]) < std::numeric_limits<double>::max() ? 1 : 0;
         } else {

@@ -30,6 +30,11 @@ constexpr int kParPerKnot = 2;
 constexpr int RefTermRecord(int n, int m) { return (n + m + 1 + 1) & ~1; }
 // doubles of one point of the reference path: x[n] | u[m], rounded up to a pair
 constexpr int RefPathRecord(int n, int m) { return (n + m + 1) & ~1; }
+// ConDesc::per_instance of a KNOT constraint (include/altro_knot_params.h: altro_add_knot_constraint): its parameters are
+// neither shared (0) nor per instance (1) but PER KNOT -- elements param_off + i of the knot-parameter record of (knot,
+// instance), DevArrays::kpar, which k_knot_params copies from the constraint's parameter track
+constexpr int kParPerKnotCon = 3;
+constexpr int kMaxKnotCons = 16;  // knot constraints of one handle (they travel to k_knot_params as one kernel argument)
 
 // ---- dtype-independent problem specification (what the altro::problem::Problem setters record) ---
 struct CostSpec {
@@ -44,6 +49,11 @@ struct ConSpec {
   int kind, k_begin, k_end, nparams, per_instance;
   std::vector<double> params;
   int user_type = 0;  // ALTRO_CON_USER: index of the constraint type in the model's source (ALTRO_USER_CONSTRAINTS)
+  // altro_add_knot_constraint: the parameters of knot k are row min(offset + k, rows - 1) of the constraint's track (params
+  // stays empty).  A track set before the device state exists waits here: track[rows][nparams] or [B][rows][nparams].
+  int knot = 0;
+  std::vector<double> track;
+  int track_rows = 0, track_per_instance = 0;
 };
 struct ProblemSpec {
   altro_desc desc{};
@@ -72,6 +82,7 @@ struct ProblemSpec {
   // ref_U empty = zeros) and the window offset; the engine owns both after the upload
   std::vector<double> ref_X, ref_U;
   int ref_rows = 0, ref_per_instance = 0, ref_offset = 0;
+  int track_offset = 0;  // altro_set_track_offset before the device state exists: the window of every constraint track
 };
 
 // ---- receding-horizon advance (include/altro_mpc.h) --------------------------------------------------
@@ -121,13 +132,25 @@ struct TrackArgs {
   double state_max, control_max;
 };
 
+// ---- knot constraints (include/altro_knot_params.h) ----------------------------------------------------
+// One launch of k_knot_params: every knot constraint of the handle, its knots, its place in the knot-parameter record and
+// its track on the device -- track[(col * rows + row) * np + e], the caller's layout, cols = 1 (shared) or B.
+struct KnotTrack {
+  const double* track;  // nullptr: no track set yet (the record keeps zeros)
+  int k_begin, k_end, np, off, rows, cols;
+};
+struct KnotParArgs {
+  int ncon, kt, offset, pad;
+  KnotTrack c[kMaxKnotCons];
+};
+
 // ---- device-visible problem description (lives in global memory, read with scalar loads) ---------
 struct ConDesc {
   int kind;          // altro_constraint_kind
   int type;          // 0 equality (dual cone = identity), 1 inequality (negative orthant)
   int p;             // rows
-  int per_instance;  // params in the per-instance pool ([slot][Bp]) instead of the shared pool
-  int param_off;     // first slot / element of this constraint's parameters
+  int per_instance;  // params in the per-instance pool ([slot][Bp]) instead of the shared pool; kParPerKnotCon: per knot
+  int param_off;     // first slot / element of this constraint's parameters (per knot: element of the knot's record)
   int row_off;       // row offset inside the knot
   unsigned lo_mask;  // CONTROL_BOUND: controls with a finite lower bound (basic_constraints.hpp:138-145); USER: index of the type
   unsigned hi_mask;  // CONTROL_BOUND: controls with a finite upper bound
@@ -392,6 +415,13 @@ class EngineBase {
   virtual altro_status SetReferenceOffset(int offset) = 0;
   virtual int GetReferenceOffset() = 0;
   virtual altro_status GetReferenceTerms(double* q, double* r, double* c) = 0;
+  // the parameter tracks of the knot constraints (include/altro_knot_params.h): `index` is the registration index of a knot
+  // constraint; P is host memory or (on_device) memory of the engine's device.  The records the kernels read are rewritten on
+  // the device behind every change.
+  virtual altro_status SetConstraintTrack(int index, const double* P, int rows, int per_instance, int on_device) = 0;
+  virtual altro_status SetTrackOffset(int offset) = 0;
+  virtual int GetTrackOffset() = 0;
+  virtual altro_status GetKnotParams(int index, double* out) = 0;
   virtual const char* LastError() = 0;
 };
 

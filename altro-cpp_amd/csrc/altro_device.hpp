@@ -289,6 +289,12 @@ struct DevArrays {
   // kParPerKnot, nothing reads it).  Last in the bundle: the kernel arguments in front of it keep their places.
   const double* ref;
   int ref_rt;
+  // KNOT-PARAMETER RECORDS of the knot constraints (altro_add_knot_constraint): kpar[(k * Bp + b) * kpar_kt + e], the
+  // parameters of every knot constraint at knot k side by side (ConDesc::param_off is e of the first), copied from the
+  // constraints' tracks by k_knot_params alone, ALWAYS fp64.  nullptr: the problem has no knot constraint (no ConDesc is
+  // marked kParPerKnotCon, nothing reads it).
+  const double* kpar;
+  int kpar_kt;
 };
 constexpr int kSegSplitEvery = 4;
 constexpr int kSegCancelled = 1, kSegRetired = 2;
@@ -954,6 +960,10 @@ ALTRO_DEV T ref_term(const DevArrays<T>& A, unsigned k, unsigned b, int e) {
   return T(A.ref[(k * (unsigned)A.Bp + b) * (unsigned)A.ref_rt + (unsigned)e]);
 }
 template <class T>
+ALTRO_DEV T knot_par(const DevArrays<T>& A, unsigned k, unsigned b, int e) {
+  return T(A.kpar[(k * (unsigned)A.Bp + b) * (unsigned)A.kpar_kt + (unsigned)e]);
+}
+template <class T>
 struct CtxG {
   static constexpr bool kKnotTerms = false;
   const DevArrays<T>& A;
@@ -977,6 +987,7 @@ struct CtxGK {  // CtxG that knows its knot
   ALTRO_DEV CtxGK at(int k_) const { return CtxGK(A, (int)b, k_); }
   ALTRO_DEV T par(int per_instance, int off, int i) const {
     if (per_instance == kParPerKnot) return ref_term(A, k, b, off + i);
+    if (per_instance == kParPerKnotCon) return knot_par(A, k, b, off + i);
     return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
   }
   ALTRO_DEV T shared(int off) const { return A.pool[off]; }
@@ -1033,6 +1044,17 @@ ALTRO_DEV T circle_value(T dx, T dy, T rr) {
 template <class T>
 ALTRO_DEV T violation(int type, T c) {
   return type == 0 ? abs_(c) : abs_(c - min_(T(0), c));
+}
+
+// One finite bound of a CONTROL_BOUND constraint, element pi of its parameters: the shared pool, or -- a knot bound, which
+// only a context that knows its knot can meet (CtxGK, CtxTrackK) -- the knot-parameter record.  The other contexts compile
+// to the pool read they always had.
+template <class T, class Ctx>
+ALTRO_DEV T bound_par(const Ctx& C, const ConDesc& cd, int pi) {
+  if constexpr (Ctx::kKnotTerms) {
+    if (cd.per_instance == kParPerKnotCon) return C.par(kParPerKnotCon, pi, 0);
+  }
+  return C.shared(pi);
 }
 
 // QuadraticCost::Evaluate (examples/quadratic_cost.cpp:8-11); H == 0 for LQRCost.  When Q / R are
@@ -1147,7 +1169,7 @@ ALTRO_DEV T knot_cost(const Ctx& C, const ProblemDesc* pd, const KnotClass& kc, 
 #pragma unroll
       for (int j = 0; j < m; ++j)
         if ((cd.lo_mask >> j) & 1u) {
-          T c = C.shared(pi) - u[j];
+          T c = bound_par<T>(C, cd, pi) - u[j];
           T lam = C.lam(r);
           T lp = dual_proj(1, lam - rho * c);
           a += lp * lp;
@@ -1162,7 +1184,7 @@ ALTRO_DEV T knot_cost(const Ctx& C, const ProblemDesc* pd, const KnotClass& kc, 
 #pragma unroll
       for (int j = 0; j < m; ++j)
         if ((cd.hi_mask >> j) & 1u) {
-          T c = u[j] - C.shared(pi);
+          T c = u[j] - bound_par<T>(C, cd, pi);
           T lam = C.lam(r);
           T lp = dual_proj(1, lam - rho * c);
           a += lp * lp;
@@ -1207,6 +1229,7 @@ struct RunConsts {
   bool per_knot;  // a tracking group: q, r, c change with the knot (load_knot_terms), everything else is the run's
   T Qd[n], Rd[m], q[n], r[m], c;
   int bnd_ci;  // index of the hoisted bound constraint, -1 if none
+  bool bnd_per_knot;  // ... a knot bound: its values change with the knot (load_knot_bounds)
   T bnd[2 * m];
 };
 template <class T, int n, int m, class Ctx>
@@ -1226,6 +1249,7 @@ ALTRO_DEV void load_run_consts(const Ctx& C, const ProblemDesc* pd, const KnotCl
   }
   R.c = C.par(g.c_pi, g.c_off, 0);
   R.bnd_ci = -1;
+  R.bnd_per_knot = false;
 #pragma unroll
   for (int j = 0; j < 2 * m; ++j) R.bnd[j] = T(0);
 #pragma unroll
@@ -1233,15 +1257,28 @@ ALTRO_DEV void load_run_consts(const Ctx& C, const ProblemDesc* pd, const KnotCl
     if (ci < kc.ncon && R.bnd_ci < 0 && kc.con[ci].kind == ALTRO_CON_CONTROL_BOUND) {
       R.bnd_ci = ci;
       const ConDesc& cd = kc.con[ci];
-      int pi = cd.param_off;
+      R.bnd_per_knot = cd.per_instance == kParPerKnotCon;
+      // a knot bound has nothing to hoist: load_knot_bounds reads all of it on every knot
+      bool hoist = true;
+      if constexpr (Ctx::kKnotTerms) hoist = !R.bnd_per_knot;
+      if (hoist) {
+        int pi = cd.param_off;
 #pragma unroll
-      for (int j = 0; j < m; ++j)
-        if ((cd.lo_mask >> j) & 1u) R.bnd[j] = C.shared(pi++);
+        for (int j = 0; j < m; ++j)
+          if ((cd.lo_mask >> j) & 1u) R.bnd[j] = bound_par<T>(C, cd, pi++);
 #pragma unroll
-      for (int j = 0; j < m; ++j)
-        if ((cd.hi_mask >> j) & 1u) R.bnd[m + j] = C.shared(pi++);
+        for (int j = 0; j < m; ++j)
+          if ((cd.hi_mask >> j) & 1u) R.bnd[m + j] = bound_par<T>(C, cd, pi++);
+      }
     }
   }
+}
+// The values of a hoisted KNOT bound at the knot of context C (C.at(k)): all 2m of them, lower bounds then upper bounds (a
+// knot bound has every row) -- what load_run_consts hoists for an ordinary bound, read once per knot instead.
+template <class T, int n, int m, class Ctx>
+ALTRO_DEV void load_knot_bounds(const Ctx& C, const ConDesc& cd, RunConsts<T, n, m>& R) {
+#pragma unroll
+  for (int j = 0; j < 2 * m; ++j) R.bnd[j] = C.par(kParPerKnotCon, cd.param_off, j);
 }
 // The linear and constant terms of a tracking group at the knot of context C (C.at(k)): what load_run_consts hoists for an
 // ordinary group, read once per knot instead.
@@ -1297,7 +1334,7 @@ ALTRO_DEV T knot_cost_fast(const Ctx& C, const ProblemDesc* pd, const KnotClass&
 #pragma unroll
         for (int j = 0; j < m; ++j)
           if ((cd.lo_mask >> j) & 1u) {
-            T c = (hoisted ? R.bnd[j] : C.shared(pi)) - u[j];
+            T c = (hoisted ? R.bnd[j] : bound_par<T>(C, cd, pi)) - u[j];
             T lam = C.lam(r);
             T lp = dual_proj(1, lam - rho * c);
             a += lp * lp;
@@ -1308,7 +1345,7 @@ ALTRO_DEV T knot_cost_fast(const Ctx& C, const ProblemDesc* pd, const KnotClass&
 #pragma unroll
         for (int j = 0; j < m; ++j)
           if ((cd.hi_mask >> j) & 1u) {
-            T c = u[j] - (hoisted ? R.bnd[m + j] : C.shared(pi));
+            T c = u[j] - (hoisted ? R.bnd[m + j] : bound_par<T>(C, cd, pi));
             T lam = C.lam(r);
             T lp = dual_proj(1, lam - rho * c);
             a += lp * lp;
@@ -1424,7 +1461,7 @@ ALTRO_DEV T knot_cost_expansion(const Ctx& C, const ProblemDesc* pd, const KnotC
 #pragma unroll
       for (int j = 0; j < m; ++j)
         if ((cd.lo_mask >> j) & 1u) {
-          T c = C.shared(pi) - u[j];
+          T c = bound_par<T>(C, cd, pi) - u[j];
           T lam = C.lam(r);
           T v = lam - rho * c;
           T lp = dual_proj(1, v);
@@ -1440,7 +1477,7 @@ ALTRO_DEV T knot_cost_expansion(const Ctx& C, const ProblemDesc* pd, const KnotC
 #pragma unroll
       for (int j = 0; j < m; ++j)
         if ((cd.hi_mask >> j) & 1u) {
-          T c = u[j] - C.shared(pi);
+          T c = u[j] - bound_par<T>(C, cd, pi);
           T lam = C.lam(r);
           T v = lam - rho * c;
           T lp = dual_proj(1, v);

@@ -335,7 +335,7 @@ class Engine final : public EngineBase {
     ctg_replayable_ = false;  // (the records a replayed backward pass would read are about to change)
     if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (A_.ref)
+    if (KnotRouted(A_))
       hipLaunchKernelGGL((k_expansions_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
     else
       hipLaunchKernelGGL((k_expansions<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
@@ -669,7 +669,7 @@ class Engine final : public EngineBase {
   }
   // the per-knot costs of the step-level calls (k_knot_costs; its twin on a handle with a tracking cost)
   void LaunchKnotCosts() {
-    if (A_.ref)
+    if (KnotRouted(A_))
       hipLaunchKernelGGL((k_knot_costs_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
     else
       hipLaunchKernelGGL((k_knot_costs<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
@@ -682,9 +682,97 @@ class Engine final : public EngineBase {
   }
   // a cost evaluation on a handle with a tracking cost needs the path
   bool RefOk() {
+    for (const KnotCon& c : kcons_)
+      if (c.rows < 1) {
+        err_ = "constraint " + std::to_string(c.index) + " is a knot constraint but has no parameter track (altro_set_constraint_track)";
+        return false;
+      }
     if (!A_.ref || ref_rows_ > 0) return true;
     err_ = "a knot has a tracking cost but no reference path is set (altro_set_reference)";
     return false;
+  }
+  // a handle whose cost kernels must know their knot: a tracking cost or a knot constraint (either record may be missing).
+  // It runs the *_trk twins of the general kernels, and neither the persistent kernel nor segments (FusedOk, PlanRun).
+  static bool KnotRouted(const DevArrays<T>& A) { return A.ref != nullptr || A.kpar != nullptr; }
+
+  // ---- the parameter tracks of the knot constraints (include/altro_knot_params.h) -----------------------------------------
+  // Every knot constraint owns a track on the device, in the caller's layout ([rows][np], or [B][rows][np]); every change of a
+  // track or of the window ends in ONE launch of k_knot_params on the engine's stream, which rewrites the records the cost
+  // kernels read (DevArrays::kpar).
+  struct KnotCon {
+    int index, k_begin, k_end, np, off, kind;  // registration index; knots; parameters; element in the record; kind
+    double* d_track = nullptr;
+    size_t cap = 0;
+    int rows = 0, cols = 0;
+  };
+  KnotCon* FindKnotCon(int index, const char* who) {
+    for (KnotCon& c : kcons_)
+      if (c.index == index) return &c;
+    err_ = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
+    return nullptr;
+  }
+  altro_status SetConstraintTrack(int index, const double* P, int rows, int per_instance, int on_device) override {
+    KnotCon* c = FindKnotCon(index, "altro_set_constraint_track");
+    if (!c) return ALTRO_INVALID_ARG;
+    if (!P || rows < 1) {
+      err_ = "altro_set_constraint_track: the track needs at least one row";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(Sync());
+    ctg_replayable_ = false;  // (as SetTrajectory: what a replayed backward pass would read belongs to the old parameters)
+    const int cols = per_instance ? B_ : 1;
+    const size_t need = (size_t)rows * cols * c->np;
+    if (need > c->cap) {
+      if (c->d_track) ALTRO_HIP_CHECK(hipFree(c->d_track));
+      c->d_track = nullptr;
+      c->cap = 0;
+      c->rows = 0;
+      ALTRO_HIP_CHECK(hipMalloc((void**)&c->d_track, need * sizeof(double)));
+      c->cap = need;
+    }
+    ALTRO_HIP_CHECK(hipMemcpyAsync(c->d_track, P, need * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    c->rows = rows;
+    c->cols = cols;
+    LaunchKnotParams();
+    return Sync();
+  }
+  altro_status SetTrackOffset(int offset) override {
+    if (offset < 0) {
+      err_ = "altro_set_track_offset: the offset must not be negative";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ctg_replayable_ = false;
+    track_offset_ = offset;
+    LaunchKnotParams();
+    return Sync();
+  }
+  int GetTrackOffset() override { return track_offset_; }
+  altro_status GetKnotParams(int index, double* out) override {
+    KnotCon* c = FindKnotCon(index, "altro_get_knot_params");
+    if (!c || !out) return ALTRO_INVALID_ARG;
+    return DownloadRec(A_.kpar + (size_t)c->k_begin * Bp_ * A_.kpar_kt, c->k_end - c->k_begin, A_.kpar_kt, c->off, c->np, out);
+  }
+  // the records of the current tracks and window (nothing to do without a knot constraint)
+  void LaunchKnotParams() {
+    if (!A_.kpar) return;
+    KnotParArgs g{};
+    g.ncon = (int)kcons_.size();
+    g.kt = A_.kpar_kt;
+    g.offset = track_offset_;
+    for (int j = 0; j < g.ncon; ++j) {
+      const KnotCon& c = kcons_[j];
+      g.c[j] = KnotTrack{c.rows > 0 ? c.d_track : nullptr, c.k_begin, c.k_end, c.np, c.off, c.rows, c.cols};
+    }
+    hipLaunchKernelGGL((k_knot_params<0>), GridBK(), dim3(kBlock), 0, stream_, g, d_kpar_, B_, Bp_);
+  }
+  void DropKnotCons() {
+    for (KnotCon& c : kcons_)
+      if (c.d_track) hipFree(c.d_track);
+    kcons_.clear();
+    d_kpar_ = nullptr;
+    track_offset_ = 0;
   }
 
   // ---- receding-horizon advance (include/altro_mpc.h) ----------------------------------------------
@@ -744,6 +832,10 @@ class Engine final : public EngineBase {
     if (A_.ref) {  // the window of a tracking cost's reference moves with the horizon (the end of the path is held)
       ref_offset_ = (int)std::min<long long>((long long)ref_offset_ + shift, 0x7fffffffLL);
       LaunchRefTerms();
+    }
+    if (A_.kpar) {  // ... and so does the window of the knot constraints' tracks (the last row is held)
+      track_offset_ = (int)std::min<long long>((long long)track_offset_ + shift, 0x7fffffffLL);
+      LaunchKnotParams();
     }
     return Sync();
   }
@@ -974,7 +1066,7 @@ class Engine final : public EngineBase {
       err_ = "altro_mpc_track: instances x samples exceed one launch (2^31 - 1 wavefronts)";
       return ALTRO_INVALID_ARG;
     }
-    if (A_.ref)  // (a tracking cost: the twin that reads the reference-term records, CtxTrackK)
+    if (KnotRouted(A_))  // (a tracking cost or a knot constraint: the twin that reads the per-knot records, CtxTrackK)
       hipLaunchKernelGGL((k_mpc_track_trk<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
     else
       hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
@@ -1064,7 +1156,8 @@ class Engine final : public EngineBase {
   bool FusedOk(const DevOpts& d) const {
     if constexpr (!kMfmaBackward) return false;
     return !sw_.force_valu_backward && !sw_.no_fused && mfma_offsets_ok_ && fwd_lds_bytes_ > 0 && !A_.record_ctg && !A_.hk &&
-           !A_.ref &&  // (a tracking cost's term records are global memory: the general kernels, as for per-knot steps)
+           !KnotRouted(A_) &&  // (a tracking cost's term records and a knot constraint's parameter records are global
+                               //  memory: the general kernels, as for per-knot steps)
            d.line_search_max_iterations >= 1 && d.line_search_max_iterations <= kLineSearchLanes && fused_lds_bytes_ <= 160 * 1024;
   }
   // Forward pass launch: instances per wavefront and the LDS-staged variant are chosen from the size
@@ -1076,7 +1169,7 @@ class Engine final : public EngineBase {
     //  invariant and goes to k_forward)
     // (a tracking cost: k_forward for EVERY model -- its terms are per-knot records in global memory, which the staged
     //  contexts of k_forward2 do not carry)
-    if (fwd_lds_bytes_ > 0 && d.line_search_max_iterations <= kLineSearchLanes && (!A.hk || !M::kHasFusedRk4) && !A.ref) {
+    if (fwd_lds_bytes_ > 0 && d.line_search_max_iterations <= kLineSearchLanes && (!A.hk || !M::kHasFusedRk4) && !KnotRouted(A)) {
       // two-wave pipeline (rollout wave + cost wave), inputs staged in LDS.  When the instances left
       // would not even fill the CUs one by one, each gets a workgroup of its own: the prologue and the
       // epilogue of the kernel (staging, winner copy) shrink with the instances per workgroup.
@@ -1093,7 +1186,7 @@ class Engine final : public EngineBase {
     {
       // fallback: single wave, reads from HBM (staged block larger than LDS, > 20 line-search trials, per-knot
       // steps / times: SetKnotTimes, or a tracking cost)
-      if (A.ref)
+      if (KnotRouted(A))
         hipLaunchKernelGGL((k_forward_trk<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
       else
         hipLaunchKernelGGL((k_forward<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
@@ -1162,6 +1255,7 @@ class Engine final : public EngineBase {
     d_refpath_ = nullptr;
     refpath_cap_ = 0;
     ref_rows_ = ref_cols_ = ref_offset_ = 0;
+    DropKnotCons();
     DropChains();
     // (the history buffers and the recording switches belong to the handle, not to the upload)
     double* const hist = A_.hist;
@@ -1200,6 +1294,7 @@ class Engine final : public EngineBase {
     stage_cap_ = 0;
     if (d_refpath_) hipFree(d_refpath_);
     d_refpath_ = nullptr;
+    DropKnotCons();
     if (d_counter_) hipFree(d_counter_);
     if (h_counter_) hipHostFree((void*)h_counter_);
     for (auto& e : prof_ev_) hipEventDestroy(e);
@@ -1347,9 +1442,12 @@ class Engine final : public EngineBase {
     con_ke_ = cp.con_ke;
     con_p_ = cp.con_p;
     con_eq_ = cp.con_eq;
+    con_knot_off_ = cp.con_knot_off;
+    knot_record_ = cp.knot_record;
     const double lim = 2147483647.0;
     auto biggest = [&]() {
-      return std::max({(double)(N_ + 1) * RR::EP * Bp_, (double)(N_ + 1) * nm * kLineSearchLanes * Bp_, (double)std::max(pd_.total_rows, 1) * Bp_});
+      return std::max({(double)(N_ + 1) * RR::EP * Bp_, (double)(N_ + 1) * nm * kLineSearchLanes * Bp_, (double)std::max(pd_.total_rows, 1) * Bp_,
+                       (double)(N_ + 1) * knot_record_ * Bp_});  // (knot_par indexes the knot-parameter records with 32 bits)
     };
     // (the shadow columns widen every array; a batch that fits 32-bit indexing without them must not be refused
     //  because of them)
@@ -1427,6 +1525,12 @@ class Engine final : public EngineBase {
       ALTRO_TRY(Alloc(&d_ref_, (size_t)(N_ + 1) * kRefRT * bp));
       A_.ref = d_ref_;
       A_.ref_rt = kRefRT;
+    }
+    // the knot-parameter records, only for a problem with a knot constraint (a ConDesc marked kParPerKnotCon)
+    if (knot_record_ > 0) {
+      ALTRO_TRY(Alloc(&d_kpar_, (size_t)(N_ + 1) * knot_record_ * bp));
+      A_.kpar = d_kpar_;
+      A_.kpar_kt = knot_record_;
     }
     return ALTRO_OK;
   }
@@ -1784,6 +1888,25 @@ class Engine final : public EngineBase {
     } else if (st == ALTRO_OK) {
       ref_offset_ = s.ref_offset;
     }
+    // the knot constraints, and whatever altro_set_constraint_track / altro_set_track_offset recorded before the upload
+    for (KnotCon& c : kcons_)
+      if (c.d_track) hipFree(c.d_track);
+    kcons_.clear();
+    for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i) {
+      if (con_knot_off_[i] < 0) continue;
+      KnotCon c;
+      c.index = (int)i;
+      c.k_begin = s.cons[i].k_begin;
+      c.k_end = s.cons[i].k_end;
+      c.np = s.cons[i].nparams;
+      c.off = con_knot_off_[i];
+      c.kind = s.cons[i].kind;
+      kcons_.push_back(c);
+    }
+    if (st == ALTRO_OK) track_offset_ = s.track_offset;
+    for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i)
+      if (con_knot_off_[i] >= 0 && s.cons[i].track_rows > 0)
+        st = SetConstraintTrack((int)i, s.cons[i].track.data(), s.cons[i].track_rows, s.cons[i].track_per_instance, 0);
     // (a failed upload leaves the engine as it was before it -- Upload() drops whatever a failed UploadImpl built: the
     //  C-ABI keeps the handle "not uploaded" and the next call uploads again instead of meeting "problem definition changed")
     return st;
@@ -1975,9 +2098,10 @@ class Engine final : public EngineBase {
     // ... nor with cost-to-go records: every shadow column writes P, p into its own CTG column, and neither
     // k_seg_fixup nor the twins' commit copy those back -- altro_get_ctg would return the records of the backward pass at which
     // the instance's OWN column retired
-    // ... nor with a tracking cost: a shadow column would need the reference-term records of its instance (copy_column)
+    // ... nor with a tracking cost or a knot constraint: a shadow column would need the reference-term records / the
+    // knot-parameter records of its instance (copy_column)
     r.seg_on = seg_total_ > 0 && !A_.hist && !A_.record_ctg && !r.d.fast_forward_stalls && r.C * kBlock <= seg_total_ && !r.loop_on &&
-               !A_.ref && sw_.spec_mode == kSpecAuto;  // (the persistent kernel's variants that know the segments: default modes only)
+               !KnotRouted(A_) && sw_.spec_mode == kSpecAuto;  // (the persistent kernel's variants that know the segments: default modes only)
     r.seg_capc = r.seg_on ? (seg_total_ / r.C) / kBlock * kBlock : 0;
     if (r.seg_on) ALTRO_HIP_CHECK(hipMemsetAsync(d_seg_cursor_, 0, kMaxChains * sizeof(int), stream_));
     // may a sweep of a chain split streaks (SplitsIn)?  Only while the batch has room: a streak split while most of the batch
@@ -2108,7 +2232,7 @@ class Engine final : public EngineBase {
     //  lanes of a dense launch: config 4 +13 %)
     // (a handle with a tracking cost: the twin kernel that reads the reference-term records, same launches)
     auto expansions = [&](dim3 grid, int all, int* order_list, int* order_count) {
-      if (A.ref)
+      if (KnotRouted(A))
         hipLaunchKernelGGL((k_expansions_trk<T, M>), grid, dim3(kBlock), 0, ch.st, A, d_pd_, all, order_list, order_count);
       else
         hipLaunchKernelGGL((k_expansions<T, M>), grid, dim3(kBlock), 0, ch.st, A, d_pd_, all, order_list, order_count);
@@ -2534,6 +2658,12 @@ class Engine final : public EngineBase {
   double *d_refpath_ = nullptr, *d_ref_ = nullptr;
   size_t refpath_cap_ = 0;
   int ref_rows_ = 0, ref_cols_ = 0, ref_offset_ = 0;
+  // the knot constraints and their tracks (each track the engine's own allocation, it grows with the track), the window
+  // offset they share, and the records [k][Bp][knot_record_] (owned through allocs_; = A_.kpar), ALWAYS fp64
+  std::vector<KnotCon> kcons_;
+  std::vector<int> con_knot_off_;
+  int knot_record_ = 0, track_offset_ = 0;
+  double* d_kpar_ = nullptr;
   altro_desc desc_;
   int B_ = 0, Bp_ = 0, N_ = 0;
   bool uploaded_ = false;

@@ -1808,8 +1808,9 @@ ALTRO_DEV bool conv_stats_and_done_pre(const DevArrays<T>& A, const DevOpts& o, 
 //   twin clone    (tw_enter_clone)    x    x    x      x      x                   x      kColTwinClone
 //   twin commit   (tw_commit)         x         x      x             x            x      kColTwinCommit
 //   k_seg_fixup                       x         x      x             x     x      x      kColSegFixup
-//   (the reference-term records of a tracking cost, DevArrays::ref: no copy copies them -- a handle that has them runs
-//    neither segments nor the persistent kernel, Engine::PlanRun / FusedOk, so no shadow column ever reads a record)
+//   (the reference-term records of a tracking cost, DevArrays::ref, and the knot-parameter records of the knot constraints,
+//    DevArrays::kpar: no copy copies them -- a handle that has either runs neither segments nor the persistent kernel,
+//    Engine::PlanRun / FusedOk / KnotRouted, so no shadow column ever reads a record)
 //
 // A CLONE starts a shadow column that has held nothing of the instance, so it needs the initial state and the per-instance
 // parameters; nothing reads the records it lacks before an expansion step and a backward pass have rewritten them.  The
@@ -2231,6 +2232,7 @@ ALTRO_DEV void rollout_run(const Ctx& C, const ProblemDesc* pd, const DevArrays<
     decltype(auto) Ck = C.at(k);  // (the knot of a tracking group's terms; CtxL: C itself)
     if constexpr (Ctx::kKnotTerms) {
       if (RC.per_knot) load_knot_terms<T, n, m>(Ck, pd->grp[kc.cost_group], RC);
+      if (RC.bnd_per_knot) load_knot_bounds<T, n, m>(Ck, kc.con[RC.bnd_ci], RC);
     }
     // duals / penalty of the bound rows: loaded up front so that one wait covers the whole knot
     T blam[2 * m], brho = T(1);
@@ -2277,9 +2279,9 @@ ALTRO_DEV void rollout_run(const Ctx& C, const ProblemDesc* pd, const DevArrays<
           const T rho = C.pen(rb + c_row);
           T a = T(0), bsum = T(0);
           for (int i = 0; i < c_p; ++i) {
-            T dx = xb[0] - C.par(c_pi, c_off, 3 * i);
-            T dy = xb[1] - C.par(c_pi, c_off, 3 * i + 1);
-            T rr = C.par(c_pi, c_off, 3 * i + 2);
+            T dx = xb[0] - Ck.par(c_pi, c_off, 3 * i);  // (Ck: a knot circle moves with the knot)
+            T dy = xb[1] - Ck.par(c_pi, c_off, 3 * i + 1);
+            T rr = Ck.par(c_pi, c_off, 3 * i + 2);
             T c = circle_value(dx, dy, rr);
             T lam = C.lam(rb + c_row + i);
             T lp = dual_proj(1, lam - rho * c);
@@ -5313,6 +5315,38 @@ __global__ __launch_bounds__(kBlock) void k_ref_terms(DevArrays<T> A, const Prob
 }
 
 // -------------------------------------------------------------------------------------------------
+// The knot-parameter records of the knot constraints (include/altro_knot_params.h: altro_add_knot_constraint,
+// altro_set_constraint_track).  For knot k = blockIdx.y (wave-uniform) and column b, every knot constraint attached to k has
+// row min(offset + k, rows - 1) of its track copied into the record kpar[(k * Bp + b) * kt + off + e]; a constraint that
+// is not attached, or has no track yet, leaves zeros, and so does the padding element.  A COPY: a constant track leaves the
+// bits an ordinary constraint holds in the parameter pool.  The row, and every constraint's range, place and width, depend
+// on the knot alone (scalar registers); model-independent, no LDS.  THE ONLY PLACE the records are written.
+// Memory pattern: the tracks stay in the caller's layout, so with a per-instance track neighbouring lanes read rows * np
+// doubles apart (a cache line per lane), and the copy goes one double at a time -- a track's row starts at any multiple of 8
+// bytes when np is odd (three numbers per circle).  One launch per advance or setter call, N + 1 records of KT doubles per
+// instance; DESIGN.md section 5.4 has the time.
+// (The template parameter is always 0: it gives the kernel, defined in a header that every inst_*.hip includes, inline
+// linkage.)
+// -------------------------------------------------------------------------------------------------
+template <int Unused>
+__global__ __launch_bounds__(kBlock) void k_knot_params(KnotParArgs g, double* __restrict__ kpar, int B, int Bp) {
+  const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
+  if (b >= B) return;
+  double* rec = kpar + ((size_t)(unsigned)k * (size_t)Bp + (size_t)b) * (size_t)g.kt;
+  int filled = 0;
+  for (int j = 0; j < g.ncon; ++j) {
+    const KnotTrack& c = g.c[j];
+    const bool live = c.track != nullptr && k >= c.k_begin && k < c.k_end;
+    const long long want = (long long)g.offset + (long long)k;
+    const int row = (int)(want < (long long)(c.rows - 1) ? want : (long long)(c.rows - 1));  // the end of the track is held
+    const double* src = live ? c.track + ((size_t)(c.cols > 1 ? b : 0) * (size_t)c.rows + (size_t)row) * (size_t)c.np : nullptr;
+    for (int e = 0; e < c.np; ++e) rec[c.off + e] = live ? src[e] : 0.0;
+    filled = c.off + c.np;
+  }
+  for (int e = filled; e < g.kt; ++e) rec[e] = 0.0;
+}
+
+// -------------------------------------------------------------------------------------------------
 // Closed-loop tracking (include/altro_mpc.h, altro_mpc_track): iLQR::RolloutClosedLoop (ilqr.hpp:468-499) with alpha = 0
 // for every (instance, disturbance sample), ONE LANE EACH: x_0 = x0 + dx0, then per knot u = Ubar + K (x - Xbar), clipped
 // where bounds are given, x+ = f_d(x, u) + w, the forward pass's bound checks, and along the way the objective cost, the
@@ -5330,6 +5364,7 @@ __global__ __launch_bounds__(kBlock) void k_ref_terms(DevArrays<T> A, const Prob
 // -------------------------------------------------------------------------------------------------
 template <class T>
 struct CtxTrack {
+  static constexpr bool kKnotTerms = false;
   const DevArrays<T>& A;
   unsigned b;
   ALTRO_DEV CtxTrack(const DevArrays<T>& A_, int b_, int = 0) : A(A_), b((unsigned)b_) {}
@@ -5343,13 +5378,15 @@ struct CtxTrack {
   ALTRO_DEV void store_c(int, T) const {}
 };
 template <class T>
-struct CtxTrackK {  // CtxTrack that knows its knot: the terms of a tracking cost (k_mpc_track_trk)
+struct CtxTrackK {  // CtxTrack that knows its knot: the terms of a tracking cost, knot constraints (k_mpc_track_trk)
+  static constexpr bool kKnotTerms = true;
   const DevArrays<T>& A;
   unsigned b, k;
   ALTRO_DEV CtxTrackK(const DevArrays<T>& A_, int b_, int k_ = 0) : A(A_), b((unsigned)b_), k((unsigned)k_) {}
   ALTRO_DEV CtxTrackK at(int k_) const { return CtxTrackK(A, (int)b, k_); }
   ALTRO_DEV T par(int per_instance, int off, int i) const {
     if (per_instance == kParPerKnot) return ref_term(A, k, b, off + i);
+    if (per_instance == kParPerKnotCon) return knot_par(A, k, b, off + i);
     return per_instance ? A.ipool[(unsigned)(off + i) * (unsigned)A.Bp + b] : A.pool[off + i];
   }
   ALTRO_DEV T shared(int off) const { return A.pool[off]; }

@@ -30,6 +30,10 @@ struct CompiledProblem {
   std::vector<std::vector<T>> ip;  // per-instance slots, each [B]
   std::vector<int> knot_class, knot_rowbase;
   std::vector<int> con_kb, con_ke, con_p, con_eq;  // knots, rows and cone of every registered constraint (MpcRowMap)
+  // knot constraints (altro_add_knot_constraint): element of every registered constraint's parameters in the knot-parameter
+  // record (-1: an ordinary constraint), and the doubles of one record (their sum, rounded up to a pair; 0: none)
+  std::vector<int> con_knot_off;
+  int knot_record = 0;
 
   CompiledProblem& Fail(altro_status st, const std::string& what) {
     status = st;
@@ -166,21 +170,24 @@ CompiledProblem<T> CompileProblem(const ProblemSpec& s, int n, int m, int N, int
 
   // --- constraints: per knot, equalities first then inequalities, insertion order kept ----------
   std::vector<ConDesc> built(s.cons.size());
+  cp.con_knot_off.assign(s.cons.size(), -1);
+  int nknot = 0;
   for (size_t i = 0; i < s.cons.size(); ++i) {
     const ConSpec& c = s.cons[i];
     ConDesc d{};
     d.kind = c.kind;
-    d.per_instance = c.per_instance ? 1 : 0;
+    d.per_instance = c.knot ? kParPerKnotCon : (c.per_instance ? 1 : 0);
     if (c.kind == ALTRO_CON_GOAL) {
       if (c.nparams != n) return cp.Fail(ALTRO_INVALID_ARG, "goal constraint needs n parameters");
       d.type = 0;
       d.p = n;
     } else if (c.kind == ALTRO_CON_CONTROL_BOUND) {
-      if (c.nparams != 2 * m || c.per_instance) return cp.Fail(ALTRO_INVALID_ARG, "control bound needs 2m shared parameters");
+      if (c.nparams != 2 * m || (c.per_instance && !c.knot)) return cp.Fail(ALTRO_INVALID_ARG, "control bound needs 2m shared parameters");
       d.type = 1;
       for (int j = 0; j < m; ++j) {  // GetFiniteIndices, basic_constraints.hpp:138-145
-        if (std::abs(c.params[j]) < std::numeric_limits<double>::max()) d.lo_mask |= 1u << j;
-        if (std::abs(c.params[m + j]) < std::numeric_limits<double>::max()) d.hi_mask |= 1u << j;
+        // (a knot bound: every entry of its track is finite -- the setters refuse anything else -- so it has all 2m rows)
+        if (c.knot || std::abs(c.params[j]) < std::numeric_limits<double>::max()) d.lo_mask |= 1u << j;
+        if (c.knot || std::abs(c.params[m + j]) < std::numeric_limits<double>::max()) d.hi_mask |= 1u << j;
       }
       d.p = __builtin_popcount(d.lo_mask) + __builtin_popcount(d.hi_mask);
     } else if (c.kind == ALTRO_CON_CIRCLE) {
@@ -206,7 +213,14 @@ CompiledProblem<T> CompileProblem(const ProblemSpec& s, int n, int m, int N, int
     } else {
       return cp.Fail(ALTRO_INVALID_ARG, "unknown constraint kind");
     }
-    if (d.kind == ALTRO_CON_CONTROL_BOUND) {
+    if (c.knot) {
+      // the parameters live in the knot-parameter records, which k_knot_params fills from the constraint's track
+      if (nknot >= kMaxKnotCons) return cp.Fail(ALTRO_UNSUPPORTED, "too many knot constraints");
+      ++nknot;
+      d.param_off = cp.knot_record;
+      cp.con_knot_off[i] = cp.knot_record;
+      cp.knot_record += c.nparams;
+    } else if (d.kind == ALTRO_CON_CONTROL_BOUND) {
       d.param_off = (int)pool.size();
       for (int j = 0; j < m; ++j)
         if ((d.lo_mask >> j) & 1u) pool.push_back(T(c.params[j]));
@@ -217,6 +231,7 @@ CompiledProblem<T> CompileProblem(const ProblemSpec& s, int n, int m, int N, int
     }
     built[i] = d;
   }
+  cp.knot_record = (cp.knot_record + 1) & ~1;
   for (size_t i = 0; i < s.cons.size(); ++i) {  // (what the row map of a receding-horizon advance is built from: MpcRowMap)
     cp.con_kb.push_back(s.cons[i].k_begin);
     cp.con_ke.push_back(s.cons[i].k_end);

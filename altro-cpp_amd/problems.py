@@ -104,6 +104,79 @@ def tracking_slalom(make, batch=1, N=24, rows=None, offset=0, bounds=True, dtype
     return s
 
 
+def moving_obstacle_tracks(batch, N, rows):
+    """The parameter tracks of moving_obstacles: (circles [B][rows][6], bounds [B][rows][4]).  With Xref = slalom_path,
+    p = b mod 5 and j the row: circle 0 = (Xref[b,10,0] + 0.02 p, Xref[b,10,1] + 0.45 - 0.045 j, 0.10 + 0.01 p) crosses the
+    path from above, circle 1 = (Xref[b,j,0] + 0.05, Xref[b,j,1] - 0.30 + 0.004 j, 0.15) rides beside it; the bound is
+    +-(0.9 - 0.008 j + 0.01 p) on both controls."""
+    Xref, _, _ = slalom_path(batch, N, rows)
+    j = np.arange(rows, dtype=np.float64)
+    circles = np.zeros((batch, rows, 6))
+    bounds = np.zeros((batch, rows, 4))
+    for b in range(batch):
+        p = b % 5
+        circles[b, :, 0] = Xref[b, 10, 0] + 0.02 * p
+        circles[b, :, 1] = Xref[b, 10, 1] + 0.45 - 0.045 * j
+        circles[b, :, 2] = 0.10 + 0.01 * p
+        circles[b, :, 3] = Xref[b, :, 0] + 0.05
+        circles[b, :, 4] = Xref[b, :, 1] - 0.30 + 0.004 * j
+        circles[b, :, 5] = 0.15
+        ub = 0.9 - 0.008 * j + 0.01 * p
+        bounds[b, :, 0] = bounds[b, :, 1] = -ub
+        bounds[b, :, 2] = bounds[b, :, 3] = ub
+    return circles, bounds
+
+
+def moving_obstacles(make, batch=1, N=24, rows=None, offset=0, per_knot=False, dtype=F64, **kw):
+    """tracking_slalom(bounds=False) -- same cost, path, x0 and guess -- with two moving circles on [1, N) and a control
+    bound that tightens along the horizon on [0, N) (moving_obstacle_tracks), as knot constraints: the circle first, then the
+    bound, all tracks per instance, the window of the tracks at row ``offset`` like the path's.
+
+    ``per_knot``: the reference's idiom instead -- one ordinary add_constraint per knot from the same track rows, the circle
+    before the bound on every knot, and the cost per knot as well (what the CPU oracle takes, and what exceeds the knot
+    classes of the device library)."""
+    rows = N + 13 if rows is None else rows
+    s = tracking_slalom(make, batch=batch, N=N, rows=rows, offset=offset, bounds=False, dtype=dtype, per_knot=per_knot)
+    circles, bounds = moving_obstacle_tracks(batch, N, rows)
+    if per_knot:
+        for k in range(N):
+            row = min(offset + k, rows - 1)
+            if k >= 1:
+                s.add_constraint(CON_CIRCLE, k, k + 1, circles[:, row])
+            s.add_constraint(CON_CONTROL_BOUND, k, k + 1, bounds[:, row])
+    else:
+        s.knot_circle = s.add_knot_constraint(CON_CIRCLE, 1, N, 6)
+        s.knot_bound = s.add_knot_constraint(CON_CONTROL_BOUND, 0, N, 4)
+        s.set_constraint_track(s.knot_circle, circles)
+        s.set_constraint_track(s.knot_bound, bounds)
+        if offset:
+            s.set_track_offset(offset)
+    return s
+
+
+def ramped_bound_track(batch, rows):
+    """The track of ramped_bounds: [B][rows][4], +-(0.5 + 0.05 row + 0.02 (b mod 5)) * 256 on both controls."""
+    ub = (0.5 + 0.05 * np.arange(rows, dtype=np.float64)[None, :] + 0.02 * (np.arange(batch) % 5)[:, None]) * 256.0
+    return np.stack([-ub, -ub, ub, ub], axis=-1)
+
+
+def ramped_bounds(make, batch=1, N=10, rows=16, offset=0, per_knot=False, dtype=F64, **kw):
+    """triple_integrator(goal_only=True) with a per-instance control bound on [0, N) that widens along the track
+    (ramped_bound_track), as a knot constraint; no tracking cost.  ``per_knot``: one ordinary control bound per knot from the
+    same rows (the reference's idiom, what the CPU oracle takes)."""
+    s = triple_integrator(make, batch=batch, N=N, dtype=dtype, goal_only=True)
+    track = ramped_bound_track(batch, rows)
+    if per_knot:
+        for k in range(N):
+            s.add_constraint(CON_CONTROL_BOUND, k, k + 1, track[:, min(offset + k, rows - 1)])
+    else:
+        s.knot_bound = s.add_knot_constraint(CON_CONTROL_BOUND, 0, N, 4)
+        s.set_constraint_track(s.knot_bound, track)
+        if offset:
+            s.set_track_offset(offset)
+    return s
+
+
 THREE_OBSTACLE_CIRCLES = np.array([[0.25 * 3.0, 0.25 * 3.0, 0.425],
                                    [0.5 * 3.0, 0.5 * 3.0, 0.425],
                                    [0.75 * 3.0, 0.75 * 3.0, 0.425]])

@@ -37,6 +37,7 @@
 #include "../altro_hip.h"
 #include "../altro_mpc.h"
 #include "../altro_tracking.h"
+#include "../altro_knot_params.h"
 
 namespace altro {
 
@@ -763,16 +764,48 @@ class Problem {
     size_t maxc = 0;
     if (with_constraints)
       for (const auto& v : cons_) maxc = std::max(maxc, v.size());
+    // The library holds a few DISTINCT knot classes and runs of them (kKnotClassLimit, kKnotRunLimit).  A problem whose runs
+    // of identical constraints fit is emitted run by run, as always.  One that does not -- the reference's moving-obstacle
+    // idiom, SetConstraint(std::make_shared<CircleConstraint>(...), k) with an object of its own on every knot -- is emitted
+    // as KNOT CONSTRAINTS (include/altro_knot_params.h) where it qualifies: consecutive knots whose j-th constraints agree in
+    // kind and shape and differ only in parameters (CircleConstraint, GoalConstraint, ControlBound with finite bounds) become
+    // one knot constraint, and their parameters travel as a track of N + 1 rows, row k = knot k's.
+    const bool knot_tracks = maxc > 0 && !ConstraintRunsFit(tracking);
     for (size_t j = 0; j < maxc; ++j)
       for (int k = 0; k <= N_;) {
         if (cons_[k].size() <= j) {
           ++k;
           continue;
         }
-        int e = k + 1;
-        while (e <= N_ && cons_[e].size() > j && cons_[e][j] == cons_[k][j]) ++e;
         const auto& c = cons_[k][j];
         const int per = (int)c.params.size() > c.nparams ? 1 : 0;
+        int e = k + 1;
+        if (knot_tracks && KnotKind(c)) {
+          bool constant = true;
+          while (e <= N_ && cons_[e].size() > j && SameForm(cons_[e][j], c) && KnotKind(cons_[e][j])) {
+            constant = constant && cons_[e][j] == c;
+            ++e;
+          }
+          // (a per-instance ControlBound exists as a knot constraint only: an ordinary bound's rows are shared)
+          if (!constant || (c.kind == ALTRO_CON_CONTROL_BOUND && per)) {
+            int index = -1;
+            Check(h, altro_add_knot_constraint(h, c.kind, 0, k, e, c.nparams, &index), "altro_add_knot_constraint");
+            // row r of the track is knot r's parameters; the rows in front of and behind the range repeat its ends
+            const int cols = per ? batch_ : 1;
+            std::vector<double> track((size_t)cols * (N_ + 1) * c.nparams);
+            for (int b = 0; b < cols; ++b)
+              for (int r = 0; r <= N_; ++r) {
+                const auto& cr = cons_[std::min(std::max(r, k), e - 1)][j];
+                std::copy(cr.params.begin() + (size_t)b * c.nparams, cr.params.begin() + (size_t)(b + 1) * c.nparams,
+                          track.begin() + ((size_t)b * (N_ + 1) + r) * c.nparams);
+              }
+            Check(h, altro_set_constraint_track(h, index, track.data(), N_ + 1, per), "altro_set_constraint_track");
+            k = e;
+            continue;
+          }
+        } else {
+          while (e <= N_ && cons_[e].size() > j && cons_[e][j] == c) ++e;
+        }
         if (c.kind == ALTRO_CON_USER)
           Check(h, altro_add_user_constraint_type(h, c.user_type, k, e, c.params.data(), c.nparams, per),
                 "altro_add_user_constraint_type");
@@ -785,6 +818,8 @@ class Problem {
   int StateDimension() const { return n_; }
   int ControlDimension() const { return m_; }
   static constexpr int kCostFunctionLimit = 8;  // distinct cost functions of one problem in the library (its cost groups)
+  static constexpr int kKnotClassLimit = 8;     // distinct (cost, constraint list) combinations over the knots in the library
+  static constexpr int kKnotRunLimit = 16;      // ... and runs of consecutive knots of one combination
 
  private:
   // the costs of a problem with more runs of identical costs than the library holds: see Apply
@@ -833,6 +868,55 @@ class Problem {
     }
     if (any_tracking)
       Check(h, altro_set_reference(h, Xref.data(), Uref.data(), N_ + 1, per_instance ? 1 : 0), "altro_set_reference");
+  }
+  // a constraint that may become a knot constraint: the built-in kinds, a bound only with every entry finite
+  static bool KnotKind(const examples::ConstraintDesc& c) {
+    if (c.kind == ALTRO_CON_CIRCLE || c.kind == ALTRO_CON_GOAL) return true;
+    if (c.kind != ALTRO_CON_CONTROL_BOUND) return false;
+    for (double v : c.params)
+      if (!(std::abs(v) < std::numeric_limits<double>::max())) return false;
+    return true;
+  }
+  // same kind and shape, whatever the parameters
+  static bool SameForm(const examples::ConstraintDesc& a, const examples::ConstraintDesc& b) {
+    return a.kind == b.kind && a.nparams == b.nparams && a.params.size() == b.params.size() && a.user_type == b.user_type;
+  }
+  // Does the run-by-run emission of Apply stay within the knot classes and runs of the library?  A knot's class is its
+  // cost (the run of identical costs it lies in; a tracking range: the run of costs of one shape) and, for every position
+  // j, the run of identical j-th constraints it lies in.  This is the library's own keying: a class is (the cost CALL, the
+  // constraint CALLS) on the knot, Apply makes one call per run, and the library does not merge two calls with equal
+  // contents -- costs A, B, A, B are four cost groups there as well.
+  bool ConstraintRunsFit(bool tracking) const {
+    std::vector<std::vector<int>> sig(N_ + 1);
+    int cost_run = 0;
+    for (int k = 0; k <= N_; ++k) {
+      if (k > 0) {
+        const auto &a = costs_[k - 1], &b = costs_[k];
+        const bool same = tracking && !a.user && !b.user
+                              ? a.Q == b.Q && a.R == b.R && a.terminal == b.terminal && a.xref.size() == b.xref.size() &&
+                                    a.uref.size() == b.uref.size()
+                              : a == b;
+        if (!same) ++cost_run;
+      }
+      sig[k].push_back(cost_run);
+    }
+    size_t maxc = 0;
+    for (const auto& v : cons_) maxc = std::max(maxc, v.size());
+    for (size_t j = 0; j < maxc; ++j) {
+      int run = 0;
+      for (int k = 0; k <= N_; ++k) {
+        if (cons_[k].size() <= j) continue;
+        if (k > 0 && !(cons_[k - 1].size() > j && cons_[k - 1][j] == cons_[k][j])) ++run;
+        sig[k].push_back((int)j * (N_ + 2) + run + 1);
+      }
+    }
+    std::vector<std::vector<int>> classes;
+    int runs = 0;
+    for (int k = 0; k <= N_; ++k) {
+      if (std::find(classes.begin(), classes.end(), sig[k]) == classes.end()) classes.push_back(sig[k]);
+      if (k == 0 || sig[k] != sig[k - 1]) ++runs;
+    }
+    return (int)classes.size() <= kKnotClassLimit && runs <= kKnotRunLimit;
   }
   void Range(int k) const {
     if (k < 0 || k > N_) throw std::runtime_error("Invalid knot point index.");
@@ -1383,6 +1467,25 @@ class AugmentedLagrangianiLQR {
   int GetReferenceOffset() {
     int offset = 0;
     detail::Check(Handle(), altro_get_reference_offset(Handle(), &offset), "altro_get_reference_offset");
+    return offset;
+  }
+  // Knot constraints (include/altro_knot_params.h): a constraint of `kind` on knots [k_begin, k_end) whose parameters at knot
+  // k are row min(offset + k, rows - 1) of its track -- P [rows][nparams], or [B][rows][nparams] with per_instance -- and
+  // AdvanceHorizon moves the offset along.  AddKnotConstraint belongs to the problem definition (before the first Solve)
+  // and returns the registration index that SetConstraintTrack takes.  A problem whose per-knot SetConstraint loop was
+  // emitted as knot constraints holds the N + 1 rows of that loop; a longer track set here replaces them.
+  int AddKnotConstraint(int kind, int k_begin, int k_end, int nparams, int user_type = 0) {
+    int index = -1;
+    detail::Check(Handle(), altro_add_knot_constraint(Handle(), kind, user_type, k_begin, k_end, nparams, &index), "altro_add_knot_constraint");
+    return index;
+  }
+  void SetConstraintTrack(int index, const double* P, int rows, bool per_instance = false) {
+    detail::Check(Handle(), altro_set_constraint_track(Handle(), index, P, rows, per_instance ? 1 : 0), "altro_set_constraint_track");
+  }
+  void SetTrackOffset(int offset) { detail::Check(Handle(), altro_set_track_offset(Handle(), offset), "altro_set_track_offset"); }
+  int GetTrackOffset() {
+    int offset = 0;
+    detail::Check(Handle(), altro_get_track_offset(Handle(), &offset), "altro_get_track_offset");
     return offset;
   }
   // Between two solves (include/altro_mpc.h): the plant under the solved plan's feedback policy, simulated ON THE DEVICE for

@@ -20,6 +20,11 @@
  *   reference window  on a handle with a tracking cost (altro_set_lqr_tracking_cost): offset_new = offset_old + shift, and
  *                     the term records are recomputed on the device for the new window (altro_set_reference_offset); a
  *                     handle without a tracking cost keeps its offset
+ *   track window      on a handle with a knot constraint (altro_add_knot_constraint, altro_knot_params.h): the track offset
+ *                     that all its constraint tracks share moves likewise, track offset_new = track offset_old + shift
+ *                     (saturating at INT_MAX), and the knot-parameter records are copied anew on the device in the same
+ *                     call (altro_set_track_offset); the constraint itself is ONE constraint of the row map above, so its
+ *                     duals and penalties travel like any other's; a handle without a knot constraint keeps its offset
  * Everything else stays: options, statistics, history, the guess altro_reset_trajectory restores, and the costs, which
  * remain attached to knot indices (a tracking cost's Q, R too: only its reference moves).  Expansions, knot costs, stored constraint values and cost-to-go records are not moved;
  * the next solve recomputes them (altro_get_ctg answers ALTRO_NOT_READY until then).
