@@ -691,6 +691,85 @@ class BatchSolver:
         rho = _f64(rho)
         self._call("set_penalties", _dp(rho))
 
+    # -- multi-start (include/altro_multistart.h) ---------------------------------------------------
+    # A handle of batch = P * starts instances holds P problems; start g of problem p is instance p * starts + g.
+    def _problems(self, starts):
+        starts = int(starts)
+        return self.batch // starts if starts >= 1 and self.batch % starts == 0 else 0
+
+    @staticmethod
+    def _ip(a):
+        return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def multistart_select(self, starts):
+        """The winning start of every problem, int32 [P], by the rule of include/altro_multistart.h over the status, cost
+        and violation ``get_stats`` reports.  Changes nothing on the handle."""
+        win = np.zeros(max(self._problems(starts), 1), dtype=np.int32)
+        self._call("multistart_select", C.c_int(starts), self._ip(win))
+        return win[:self._problems(starts)]
+
+    def multistart_select_device(self, starts, winner_ptr):
+        self._call("multistart_select_device", C.c_int(starts), C.c_void_p(winner_ptr or None))
+
+    def multistart_spread(self, starts):
+        """Select, then copy the winner's column (X, U, gains, duals, penalties, constraint values, knot costs) over the
+        other starts of its problem, on the device.  Returns the winners, int32 [P]."""
+        win = np.zeros(max(self._problems(starts), 1), dtype=np.int32)
+        self._call("multistart_spread", C.c_int(starts), self._ip(win))
+        return win[:self._problems(starts)]
+
+    def multistart_spread_device(self, starts, winner_ptr=0):
+        self._call("multistart_spread_device", C.c_int(starts), C.c_void_p(winner_ptr or None))
+
+    def _perturbation(self, starts, dU):
+        dU = _f64(dU)
+        shapes = ((int(starts), self.N, self.m), (self.batch, self.N, self.m))
+        if dU is not None and dU.shape not in shapes:
+            raise ValueError(f"dU must have shape {shapes[0]} or {shapes[1]}")
+        # (starts == batch: both shapes coincide, and so do the two layouts)
+        return dU, 1 if dU is not None and dU.shape[0] == self.batch and int(starts) != self.batch else 0
+
+    def multistart_perturb(self, starts, dU):
+        """U += dU, a plain fp64 addition on the device; dU [starts][N][m] (one block per start, shared by all problems) or
+        [B][N][m]."""
+        dU, per_instance = self._perturbation(starts, dU)
+        self._call("multistart_perturb", C.c_int(starts), _dp(dU), C.c_int(per_instance))
+
+    def multistart_perturb_device(self, starts, du_ptr, per_instance):
+        self._call("multistart_perturb_device", C.c_int(starts), C.c_void_p(du_ptr or None), C.c_int(1 if per_instance else 0))
+
+    def multistart_get_best(self, starts):
+        """The winners only: dict(X [P][N+1][n], U [P][N][m], stats [P] of STATS_DTYPE, winner [P])."""
+        P = self._problems(starts)
+        X = np.zeros((max(P, 1), self.N + 1, self.n))
+        U = np.zeros((max(P, 1), self.N, self.m))
+        stats = np.zeros(max(P, 1), dtype=STATS_DTYPE)
+        win = np.zeros(max(P, 1), dtype=np.int32)
+        self._call("multistart_get_best", C.c_int(starts), _dp(X), _dp(U), stats.ctypes.data_as(C.c_void_p), self._ip(win))
+        return dict(X=X[:P], U=U[:P], stats=stats[:P], winner=win[:P])
+
+    def multistart_get_best_device(self, starts, x_ptr=0, u_ptr=0, stats_ptr=0, winner_ptr=0):
+        """multistart_get_best with every array in memory of this handle's device (any pointer may be 0, not all)."""
+        self._call("multistart_get_best_device", C.c_int(starts), *(C.c_void_p(p or None) for p in (x_ptr, u_ptr, stats_ptr, winner_ptr)))
+
+    def mpc_run_multistart(self, starts, cycles, shift, w=None, dU=None):
+        """``cycles`` x (solve; multistart_spread; mpc_advance(shift, w=w[c]); multistart_perturb(dU) unless it is None) with
+        nothing crossing to the host inside the loop.  Returns dict(X_cl, U_cl, iterations, status as mpc_run gives them,
+        per instance, and winner [P][cycles])."""
+        w = _f64(w)
+        if w is not None and w.shape != (cycles, self.batch, self.n):
+            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {self.n})")
+        dU, per_instance = self._perturbation(starts, dU)
+        L = max(cycles, 0) * max(shift, 0)
+        X = np.zeros((self.batch, L + 1, self.n))
+        U = np.zeros((self.batch, L, self.m))
+        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        win = np.zeros((max(self._problems(starts), 1), max(cycles, 1)), dtype=np.int32)
+        self._call("mpc_run_multistart", C.c_int(starts), C.c_int(cycles), C.c_int(shift), _dp(w), _dp(dU), C.c_int(per_instance),
+                   _dp(X), _dp(U), self._ip(it), self._ip(st), self._ip(win))
+        return dict(X_cl=X, U_cl=U, iterations=it, status=st, winner=win[:self._problems(starts), :max(cycles, 0)])
+
     # -- device interop ---------------------------------------------------------------------------
     def pack_results_device(self, device_ptr):
         self._call("pack_results_device", C.c_void_p(device_ptr))

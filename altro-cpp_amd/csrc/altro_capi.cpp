@@ -36,12 +36,13 @@
 #include "../../include/altro_mpc.h"
 #include "../../include/altro_tracking.h"
 #include "../../include/altro_knot_params.h"
+#include "../../include/altro_multistart.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 11  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 12  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -50,6 +51,7 @@ struct altro_solver_s {
   bool uploaded = false;
   bool ilqr_mode = false;
   bool has_gains = false;  // a backward pass (a solve, altro_backward_pass) has left gains on the device: altro_mpc_track
+  bool has_solved = false;  // a whole solve (altro_solve_al, altro_solve_ilqr, altro_wait) has finished: altro_multistart_select
   std::string err;
   // Asynchronous solve (altro_solve_al_async): ONE worker thread per handle, created on first use and
   // parked on a condition variable between solves.  While a solve is pending the handle only answers
@@ -355,6 +357,12 @@ altro_status ForwardCost(altro_handle h, F f) {
 altro_status GainsAfter(altro_handle h, altro_status st) {
   if (h && st == ALTRO_OK) h->has_gains = true;
   return st;
+}
+
+// behind a whole solve: the statistics the multi-start selection reads exist (include/altro_multistart.h)
+altro_status SolvedAfter(altro_handle h, altro_status st) {
+  if (h && st == ALTRO_OK) h->has_solved = true;
+  return GainsAfter(h, st);
 }
 
 altro_status DefChanged(altro_handle h) {
@@ -975,11 +983,11 @@ altro_status altro_set_penalty_scaling(altro_handle h, double phi) {
 
 altro_status altro_solve_al(altro_handle h) {
   if (h) h->ilqr_mode = false;
-  return GainsAfter(h, ForwardCost(h, [&](EngineBase& e) { return e.SolveAL(h->opts); }));
+  return SolvedAfter(h, ForwardCost(h, [&](EngineBase& e) { return e.SolveAL(h->opts); }));
 }
 altro_status altro_solve_ilqr(altro_handle h) {
   if (h) h->ilqr_mode = true;
-  return GainsAfter(h, ForwardCost(h, [&](EngineBase& e) { return e.SolveILQR(h->opts); }));
+  return SolvedAfter(h, ForwardCost(h, [&](EngineBase& e) { return e.SolveILQR(h->opts); }));
 }
 altro_status altro_solve_al_async(altro_handle h) {
   if (!h) return ALTRO_INVALID_ARG;
@@ -1036,7 +1044,7 @@ altro_status altro_wait(altro_handle h) {
   }
   h->async_pending = false;
   if (h->async_status != ALTRO_OK) h->err = h->async_err;
-  return GainsAfter(h, h->async_status);
+  return SolvedAfter(h, h->async_status);
 }
 altro_status altro_al_init(altro_handle h) { return ForwardCost(h, [&](EngineBase& e) { return e.AlInit(h->opts); }); }
 altro_status altro_solve_setup(altro_handle h) { return Forward(h, [&](EngineBase& e) { return e.SolveSetup(h->opts); }); }
@@ -1398,6 +1406,129 @@ altro_status altro_get_initial_state(altro_handle h, double* x0) {
 altro_status altro_set_penalties(altro_handle h, const double* rho) {
   if (!rho) return ALTRO_INVALID_ARG;
   return Forward(h, [&](EngineBase& e) { return e.SetPenalties(rho); });
+}
+
+}  // extern "C"
+
+// ---- multi-start (include/altro_multistart.h) -------------------------------------------------------------------------
+namespace {
+
+// everything that can be refused without a device; need_solve: the call reads the statistics of a finished solve
+altro_status MsCheck(altro_handle h, int starts, bool need_solve, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const int B = h->spec.desc.batch;
+  if (starts < 1 || B % starts != 0) {
+    h->err = std::string(who) + ": starts must be at least 1 and divide the batch of " + std::to_string(B) + ", got " +
+             std::to_string(starts);
+    return ALTRO_INVALID_ARG;
+  }
+  if (need_solve && !h->has_solved) {
+    h->err = std::string(who) + ": no solve has finished on this handle yet (altro_solve_al, altro_solve_ilqr, altro_wait)";
+    return ALTRO_NOT_READY;
+  }
+  return ALTRO_OK;
+}
+altro_status MsSelectImpl(altro_handle h, int starts, int* winner, int on_device, const char* who) {
+  const altro_status st = MsCheck(h, starts, true, who);
+  if (st != ALTRO_OK) return st;
+  if (!winner) {
+    h->err = std::string(who) + ": winner is required";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.MsSelect(starts, winner, on_device, h->ilqr_mode); });
+}
+altro_status MsSpreadImpl(altro_handle h, int starts, int* winner, int on_device, const char* who) {
+  const altro_status st = MsCheck(h, starts, true, who);
+  if (st != ALTRO_OK) return st;
+  return Forward(h, [&](EngineBase& e) { return e.MsSpread(starts, winner, on_device, h->ilqr_mode); });
+}
+altro_status MsPerturbImpl(altro_handle h, int starts, const double* dU, int per_instance, int on_device, const char* who) {
+  const altro_status st = MsCheck(h, starts, false, who);
+  if (st != ALTRO_OK) return st;
+  if (!dU) {
+    h->err = std::string(who) + ": dU is required";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.MsPerturb(starts, dU, per_instance, on_device); });
+}
+altro_status MsGetBestImpl(altro_handle h, int starts, double* X, double* U, altro_stats* stats, int* winner, int on_device,
+                           const char* who) {
+  const altro_status st = MsCheck(h, starts, true, who);
+  if (st != ALTRO_OK) return st;
+  if (!X && !U && !stats && !winner) {
+    h->err = std::string(who) + ": at least one of X, U, stats, winner is required";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.MsGetBest(starts, X, U, stats, winner, on_device, h->ilqr_mode); });
+}
+
+}  // namespace
+
+extern "C" {
+
+altro_status altro_multistart_select(altro_handle h, int starts, int* winner) {
+  return MsSelectImpl(h, starts, winner, 0, "altro_multistart_select");
+}
+altro_status altro_multistart_select_device(altro_handle h, int starts, void* winner_device) {
+  return MsSelectImpl(h, starts, (int*)winner_device, 1, "altro_multistart_select_device");
+}
+altro_status altro_multistart_spread(altro_handle h, int starts, int* winner) {
+  return MsSpreadImpl(h, starts, winner, 0, "altro_multistart_spread");
+}
+altro_status altro_multistart_spread_device(altro_handle h, int starts, void* winner_device) {
+  return MsSpreadImpl(h, starts, (int*)winner_device, 1, "altro_multistart_spread_device");
+}
+altro_status altro_multistart_perturb(altro_handle h, int starts, const double* dU, int per_instance) {
+  return MsPerturbImpl(h, starts, dU, per_instance, 0, "altro_multistart_perturb");
+}
+altro_status altro_multistart_perturb_device(altro_handle h, int starts, const void* dU_device, int per_instance) {
+  return MsPerturbImpl(h, starts, (const double*)dU_device, per_instance, 1, "altro_multistart_perturb_device");
+}
+altro_status altro_multistart_get_best(altro_handle h, int starts, double* X, double* U, altro_stats* stats, int* winner) {
+  return MsGetBestImpl(h, starts, X, U, stats, winner, 0, "altro_multistart_get_best");
+}
+altro_status altro_multistart_get_best_device(altro_handle h, int starts, void* X_device, void* U_device, void* stats_device,
+                                              void* winner_device) {
+  return MsGetBestImpl(h, starts, (double*)X_device, (double*)U_device, (altro_stats*)stats_device, (int*)winner_device, 1,
+                       "altro_multistart_get_best_device");
+}
+altro_status altro_mpc_run_multistart(altro_handle h, int starts, int cycles, int shift, const double* w, const double* dU,
+                                      int dU_per_instance, double* X_cl, double* U_cl, int* iterations, int* status, int* winner) {
+  altro_status st = MsCheck(h, starts, false, "altro_mpc_run_multistart");
+  if (st != ALTRO_OK) return st;
+  if (cycles < 1) {
+    h->err = "altro_mpc_run_multistart: at least one cycle";
+    return ALTRO_INVALID_ARG;
+  }
+  st = MpcCheck(h, shift, "altro_mpc_run_multistart");
+  if (st != ALTRO_OK) return st;
+  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
+  st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
+  if (st == ALTRO_OK) st = Forward(h, [&](EngineBase& e) { return e.MsRunBegin(starts, cycles, w, dU, dU_per_instance); });
+  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
+    st = altro_solve_al(h);
+    if (st != ALTRO_OK) break;
+    const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
+    st = Forward(h, [&](EngineBase& e) { return e.MsRunCycle(shift, pen, h->ilqr_mode); });
+    if (st == ALTRO_OK) {  // (as behind altro_mpc_advance: the initial state now lives on the device alone)
+      h->spec.x0.clear();
+      h->spec.x0_per_instance = 0;
+    }
+  }
+  if (h->uploaded) {
+    const std::string err = h->err;
+    altro_status es = h->engine->MsRunEnd(winner);  // (also after a failure: both free their device blocks)
+    const altro_status el = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);
+    if (es == ALTRO_OK) es = el;
+    if (st == ALTRO_OK && es != ALTRO_OK) {
+      h->err = h->engine->LastError();
+      st = es;
+    } else {
+      h->err = err;
+    }
+  }
+  return st;
 }
 
 }  // extern "C"

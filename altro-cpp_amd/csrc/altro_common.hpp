@@ -214,6 +214,35 @@ struct DevOpts {
 #define ALTRO_HD inline
 #endif
 constexpr int kBlock = 64;  // one wavefront per workgroup: instances never share data
+
+// ---- multi-start (include/altro_multistart.h): THE selection rule, host and device -----------------------------------
+// The key of a start is the status, cost and violation altro_get_stats reports.  Class 0: solved, both numbers finite --
+// ordered by cost; class 1: any other status, both finite -- by violation, then cost; class 2: a NaN or an infinity.  The
+// lower class wins, comparisons are fp64 `<`, ties go to the lowest start index: a total order.
+ALTRO_HD int ms_class(int status, double cost, double violation) {
+  if (!(__builtin_isfinite(cost) && __builtin_isfinite(violation))) return 2;
+  return status == ALTRO_SOLVED ? 0 : 1;
+}
+// start a STRICTLY before start b, whatever their indices (false on a tie)
+ALTRO_HD bool ms_before(int status_a, double cost_a, double viol_a, int status_b, double cost_b, double viol_b) {
+  const int ca = ms_class(status_a, cost_a, viol_a), cb = ms_class(status_b, cost_b, viol_b);
+  if (ca != cb) return ca < cb;
+  if (ca == 2) return false;
+  if (ca == 1) {
+    if (viol_a < viol_b) return true;
+    if (viol_b < viol_a) return false;
+  }
+  return cost_a < cost_b;
+}
+// the winner among starts 0 .. G-1 (element g of each array at g * stride)
+ALTRO_HD int ms_select(const int* status, const double* cost, const double* violation, int G, int stride) {
+  int w = 0;
+  for (int g = 1; g < G; ++g)
+    if (ms_before(status[g * stride], cost[g * stride], violation[g * stride], status[w * stride], cost[w * stride],
+                  violation[w * stride]))
+      w = g;
+  return w;
+}
 // knots per synchronisation of the persistent kernel's knot loop (the batched sweeps: 2), see producer_syncs_after.
 // Round 2 (hardware barriers only): 4 measured 5.24 -> 5.30 ms on config 2, 5.03 -> 4.74 ms on config 3, the headline kept
 // 2.  Round 3: with the forward waves of config 2 synchronised through sequence words (kSpecFree) a meeting costs the
@@ -422,6 +451,18 @@ class EngineBase {
   virtual altro_status SetTrackOffset(int offset) = 0;
   virtual int GetTrackOffset() = 0;
   virtual altro_status GetKnotParams(int index, double* out) = 0;
+  // multi-start (include/altro_multistart.h): G adjacent columns are the starts of one problem.  Pointers are host arrays
+  // or (on_device) memory of the engine's device; ilqr_mode picks the status as GetStats does.
+  virtual altro_status MsSelect(int G, int* winner, int on_device, bool ilqr_mode) = 0;
+  virtual altro_status MsSpread(int G, int* winner, int on_device, bool ilqr_mode) = 0;
+  virtual altro_status MsPerturb(int G, const double* dU, int per_instance, int on_device) = 0;
+  virtual altro_status MsGetBest(int G, double* X, double* U, altro_stats* stats, int* winner, int on_device, bool ilqr_mode) = 0;
+  // altro_mpc_run_multistart: Begin copies w ([cycles][B][n]) and dU to the device once (either may be null) and opens the
+  // winner log; every Cycle (behind a solve) spreads, advances by `shift` under its w and perturbs; End downloads
+  // winner[P][cycles] (may be null) and frees the block
+  virtual altro_status MsRunBegin(int G, int cycles, const double* w, const double* dU, int dU_per_instance) = 0;
+  virtual altro_status MsRunCycle(int shift, double reset_pen, bool ilqr_mode) = 0;
+  virtual altro_status MsRunEnd(int* winner) = 0;
   virtual const char* LastError() = 0;
 };
 

@@ -869,6 +869,181 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
   }
+  // ---- multi-start (include/altro_multistart.h) -----------------------------------------------------
+  // G adjacent columns are the starts of one problem.  Everything runs on the engine's stream; the winners live in a device
+  // array of the engine (d_ms_win_) unless the caller brings device memory for them.  The C API has checked G against the batch.
+  altro_status MsCheck(int G) {
+    if (G < 1 || B_ % G != 0) {
+      err_ = "multi-start: starts must be at least 1 and divide the batch";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    if (!d_ms_win_) ALTRO_HIP_CHECK(hipMalloc((void**)&d_ms_win_, (size_t)B_ * sizeof(int)));
+    return ALTRO_OK;
+  }
+  // k_ms_select into `win` (device, [P]); log: one more copy at log[p * stride + off]
+  void LaunchMsSelect(int G, bool ilqr_mode, int* win, int* log, int stride, int off) {
+    const int P = B_ / G;
+    hipLaunchKernelGGL(k_ms_select<T>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, stream_, A_, G, P, ilqr_mode ? 1 : 0, win, log,
+                       stride, off);
+  }
+  // where the winners of this call go on the device, and their way back to a host caller
+  int* MsWinDev(int* winner, int on_device) { return winner && on_device ? winner : d_ms_win_; }
+  altro_status MsWinOut(int G, int* winner, int on_device) {
+    ALTRO_TRY(Sync());
+    if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, d_ms_win_, (size_t)(B_ / G) * sizeof(int), hipMemcpyDeviceToHost));
+    return ALTRO_OK;
+  }
+  altro_status MsSelect(int G, int* winner, int on_device, bool ilqr_mode) override {
+    ALTRO_TRY(MsCheck(G));
+    LaunchMsSelect(G, ilqr_mode, MsWinDev(winner, on_device), nullptr, 0, 0);
+    return MsWinOut(G, winner, on_device);
+  }
+  void LaunchMsSpread(int G, const int* win) {
+    static_assert(R::nP * sizeof(T) % 16 == 0 && R::mP * sizeof(T) % 16 == 0 && RR::KP * sizeof(RS) % 16 == 0,
+                  "records are whole 16-byte units");
+    MsSpreadArgs g{};
+    g.G = G;
+    g.B = B_;
+    g.winner = win;
+    g.rec[0] = reinterpret_cast<uint4*>(A_.X);
+    g.rec[1] = reinterpret_cast<uint4*>(A_.U);
+    g.rec[2] = reinterpret_cast<uint4*>(A_.KD);
+    g.rec_knots[0] = N_ + 1;
+    g.rec_knots[1] = N_;
+    g.rec_knots[2] = N_;
+    g.rec_vecs[0] = R::nP * (int)sizeof(T) / 16;
+    g.rec_vecs[1] = R::mP * (int)sizeof(T) / 16;
+    g.rec_vecs[2] = RR::KP * (int)sizeof(RS) / 16;
+    g.rows = pd_.total_rows;
+    g.knots1 = N_ + 1;
+    // lanes for the largest of the seven arrays, capped: the kernel strides over what is left
+    size_t most = (size_t)std::max(pd_.total_rows, N_ + 1) * B_;
+    for (int j = 0; j < 3; ++j) most = std::max(most, (size_t)g.rec_knots[j] * g.rec_vecs[j] * B_);
+    const unsigned gx = (unsigned)std::min<size_t>((most + kMsThreads - 1) / kMsThreads, (size_t)16 * std::max(num_cus_, 1));
+    hipLaunchKernelGGL(k_ms_spread<T>, dim3(gx, 7), dim3(kMsThreads), 0, stream_, A_, g);
+  }
+  altro_status MsSpread(int G, int* winner, int on_device, bool ilqr_mode) override {
+    ALTRO_TRY(MsCheck(G));
+    ctg_replayable_ = false;  // (as SetTrajectory)
+    int* win = MsWinDev(winner, on_device);
+    LaunchMsSelect(G, ilqr_mode, win, nullptr, 0, 0);
+    if (G > 1) LaunchMsSpread(G, win);
+    return MsWinOut(G, winner, on_device);
+  }
+  void LaunchMsPerturb(int G, const double* dU_dev, int per_instance) {
+    const size_t total = (size_t)N_ * B_ * (R::mP / 2);
+    hipLaunchKernelGGL(k_ms_perturb<T>, dim3((unsigned)((total + kMsThreads - 1) / kMsThreads)), dim3(kMsThreads), 0, stream_, A_, dU_dev, G,
+                       per_instance ? 1 : 0, m, R::mP);
+  }
+  altro_status MsPerturb(int G, const double* dU, int per_instance, int on_device) override {
+    ALTRO_TRY(MsCheck(G));
+    if (!dU) {
+      err_ = "altro_multistart_perturb: dU is required";
+      return ALTRO_INVALID_ARG;
+    }
+    ctg_replayable_ = false;
+    if (!on_device) {
+      const size_t cnt = (size_t)(per_instance ? B_ : G) * N_ * m;
+      ALTRO_TRY(EnsureStage(cnt));
+      ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, dU, cnt * sizeof(double), hipMemcpyHostToDevice, stream_));
+      dU = d_stage_;
+    }
+    LaunchMsPerturb(G, dU, per_instance);
+    return Sync();
+  }
+  // The winners' trajectories through k_rec_to_rows with the winner as the source column, their statistics through k_ms_stats.
+  // A host caller's arrays are staged in ONE device block (X | U | stats) and come back with one copy each.
+  altro_status MsGetBest(int G, double* X, double* U, altro_stats* stats, int* winner, int on_device, bool ilqr_mode) override {
+    ALTRO_TRY(MsCheck(G));
+    const int P = B_ / G;
+    const size_t nx = (size_t)P * (N_ + 1) * n, nu = (size_t)P * N_ * m, ns = (size_t)P * sizeof(altro_stats) / sizeof(double);
+    static_assert(sizeof(altro_stats) % sizeof(double) == 0, "altro_stats is a whole number of doubles");
+    double *dX = X, *dU = U;
+    altro_stats* dS = stats;
+    if (!on_device) {
+      ALTRO_TRY(EnsureStage(nx + nu + ns));
+      dX = d_stage_;
+      dU = d_stage_ + nx;
+      dS = reinterpret_cast<altro_stats*>(d_stage_ + nx + nu);
+    }
+    int* win = MsWinDev(winner, on_device);
+    LaunchMsSelect(G, ilqr_mode, win, nullptr, 0, 0);
+    const dim3 gp((P + kBlock - 1) / kBlock);
+    if (X)
+      hipLaunchKernelGGL((k_rec_to_rows<T>), dim3(gp.x, N_ + 1), dim3(kBlock), 0, stream_, (const T*)A_.X, dX, N_ + 1, R::nP, 0, n, P, Bp_,
+                         (const int*)win, G);
+    if (U)
+      hipLaunchKernelGGL((k_rec_to_rows<T>), dim3(gp.x, N_), dim3(kBlock), 0, stream_, (const T*)A_.U, dU, N_, R::mP, 0, m, P, Bp_,
+                         (const int*)win, G);
+    if (stats) hipLaunchKernelGGL(k_ms_stats<T>, gp, dim3(kBlock), 0, stream_, A_, (const int*)win, G, P, ilqr_mode ? 1 : 0, dS);
+    ALTRO_TRY(MsWinOut(G, winner, on_device));
+    if (!on_device) {
+      if (X) ALTRO_HIP_CHECK(CopySync(X, dX, nx * sizeof(double), hipMemcpyDeviceToHost));
+      if (U) ALTRO_HIP_CHECK(CopySync(U, dU, nu * sizeof(double), hipMemcpyDeviceToHost));
+      if (stats) ALTRO_HIP_CHECK(CopySync(stats, dS, (size_t)P * sizeof(altro_stats), hipMemcpyDeviceToHost));
+    }
+    return ALTRO_OK;
+  }
+  // altro_mpc_run_multistart: w and dU go to the device once, the winners of every cycle stay there until the end
+  struct MsRun {
+    double *blk = nullptr, *w = nullptr, *dU = nullptr;
+    int* win = nullptr;  // [P][cycles]
+    int G = 0, cycles = 0, cycle = 0, per_instance = 0;
+  };
+  void MsRunDrop() {
+    if (ms_run_.blk) hipFree(ms_run_.blk);
+    if (ms_run_.win) hipFree(ms_run_.win);
+    ms_run_ = MsRun{};
+  }
+  altro_status MsRunBegin(int G, int cycles, const double* w, const double* dU, int dU_per_instance) override {
+    ALTRO_TRY(MsCheck(G));
+    MsRunDrop();
+    const size_t nw = w ? (size_t)cycles * B_ * n : 0, nd = dU ? (size_t)(dU_per_instance ? B_ : G) * N_ * m : 0;
+    if (nw + nd > 0) {
+      ALTRO_HIP_CHECK(hipMalloc((void**)&ms_run_.blk, (nw + nd) * sizeof(double)));
+      if (w) {
+        ms_run_.w = ms_run_.blk;
+        ALTRO_HIP_CHECK(CopySync(ms_run_.w, w, nw * sizeof(double), hipMemcpyHostToDevice));
+      }
+      if (dU) {
+        ms_run_.dU = ms_run_.blk + nw;
+        ALTRO_HIP_CHECK(CopySync(ms_run_.dU, dU, nd * sizeof(double), hipMemcpyHostToDevice));
+      }
+    }
+    ALTRO_HIP_CHECK(hipMalloc((void**)&ms_run_.win, (size_t)(B_ / G) * cycles * sizeof(int)));
+    ms_run_.G = G;
+    ms_run_.cycles = cycles;
+    ms_run_.per_instance = dU_per_instance;
+    return ALTRO_OK;
+  }
+  altro_status MsRunCycle(int shift, double reset_pen, bool ilqr_mode) override {
+    if (!ms_run_.win || ms_run_.cycle >= ms_run_.cycles) {
+      err_ = "altro_mpc_run_multistart: no cycle left";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    const int G = ms_run_.G, c = ms_run_.cycle++;
+    ctg_replayable_ = false;
+    LaunchMsSelect(G, ilqr_mode, d_ms_win_, ms_run_.win, ms_run_.cycles, c);
+    if (G > 1) LaunchMsSpread(G, d_ms_win_);
+    ALTRO_TRY(MpcAdvance(shift, nullptr, ms_run_.w ? ms_run_.w + (size_t)c * B_ * n : nullptr, 1, reset_pen));
+    if (ms_run_.dU) {
+      LaunchMsPerturb(G, ms_run_.dU, ms_run_.per_instance);
+      return Sync();
+    }
+    return ALTRO_OK;
+  }
+  altro_status MsRunEnd(int* winner) override {
+    hipError_t e = hipSetDevice(desc_.device_id);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e == hipSuccess && winner && ms_run_.win && ms_run_.cycle == ms_run_.cycles)
+      e = CopySync(winner, ms_run_.win, (size_t)(B_ / ms_run_.G) * ms_run_.cycles * sizeof(int), hipMemcpyDeviceToHost);
+    MsRunDrop();
+    ALTRO_HIP_CHECK(e);
+    return ALTRO_OK;
+  }
+
   // ---- closed-loop tracking (include/altro_mpc.h) ---------------------------------------------------
   // One launch of k_mpc_track, one lane per (instance, sample).  Host arrays are staged through ONE device block that lives
   // for the call; device arrays are used where they are.  Reads the engine's arrays only: no flag of the engine changes.
@@ -1289,6 +1464,9 @@ class Engine final : public EngineBase {
     if (A_.hist_len) hipFree(A_.hist_len);
     MpcLogDrop();
     TrackedDrop();
+    MsRunDrop();
+    if (d_ms_win_) hipFree(d_ms_win_);
+    d_ms_win_ = nullptr;
     if (d_stage_) hipFree(d_stage_);
     d_stage_ = nullptr;
     stage_cap_ = 0;
@@ -2744,6 +2922,8 @@ class Engine final : public EngineBase {
   int* mpc_log_it_ = nullptr;                           // iterations [B][cycles], then statuses [B][cycles]
   int mpc_log_cycles_ = 0, mpc_log_shift_ = 0, mpc_log_cycle_ = 0;
   TrackedLog tracked_;                                  // closed-loop log of altro_mpc_run_tracked
+  int* d_ms_win_ = nullptr;                             // winners of the last multi-start call, [B] (MsCheck)
+  MsRun ms_run_;                                        // altro_mpc_run_multistart (MsRunBegin .. MsRunEnd)
   std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;
   volatile int* h_counter_ = nullptr;  // pinned + mapped: one word per sweep

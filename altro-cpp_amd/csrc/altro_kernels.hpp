@@ -1808,6 +1808,7 @@ ALTRO_DEV bool conv_stats_and_done_pre(const DevArrays<T>& A, const DevOpts& o, 
 //   twin clone    (tw_enter_clone)    x    x    x      x      x                   x      kColTwinClone
 //   twin commit   (tw_commit)         x         x      x             x            x      kColTwinCommit
 //   k_seg_fixup                       x         x      x             x     x      x      kColSegFixup
+//   multi-start   (k_ms_spread)       x         x      x                   x             a kernel of its own, see there
 //   (the reference-term records of a tracking cost, DevArrays::ref, and the knot-parameter records of the knot constraints,
 //    DevArrays::kpar: no copy copies them -- a handle that has either runs neither segments nor the persistent kernel,
 //    Engine::PlanRun / FusedOk / KnotRouted, so no shadow column ever reads a record)
@@ -5059,12 +5060,16 @@ __global__ __launch_bounds__(256) void k_merge_lists(ChainLists in, int* __restr
 // The two layout conversions of the host boundary, on the device so that the host only copies contiguous buffers:
 // device records [knots][Bp][EP] (fields off .. off+E) -> the caller's rows [B][knots][E] of doubles, and back
 // (padding elements and padding instances zeroed; `per_instance` = 0: one [knots][E] block shared by the batch).
+// With a column indirection (multi-start, altro_multistart_get_best: `col` holds the winning start of every problem) row b of
+// the output comes from column b * G + col[b] -- B is then the number of problems.
 template <class E_>
 __global__ __launch_bounds__(kBlock) void k_rec_to_rows(const E_* __restrict__ dev, double* __restrict__ out, int knots, int EP,
-                                                        int off, int E, int B, int Bp) {
+                                                        int off, int E, int B, int Bp, const int* __restrict__ col = nullptr,
+                                                        int G = 1) {
   const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
   if (b >= B) return;
-  const E_* src = dev + ((size_t)k * Bp + b) * EP + off;
+  const int c = col ? b * G + col[b] : b;
+  const E_* src = dev + ((size_t)k * Bp + c) * EP + off;
   double* dst = out + ((size_t)b * knots + k) * E;
   for (int e = 0; e < E; ++e) dst[e] = (double)src[e];
 }
@@ -5210,6 +5215,111 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_advance(DevArrays<T> A, Mpc
     mpc_shift_units((job == 3 ? A.lam : A.pen) + b0, g.rows, nb, Bp, [=](int r) { return map[r]; },
                     [=](T v, int su, int) { return su >= 0 ? v : fresh; });
   }
+}
+
+// -------------------------------------------------------------------------------------------------
+// Multi-start (include/altro_multistart.h): G adjacent columns are the STARTS of one problem, P = B / G problems.
+//
+// k_ms_select   one lane per problem walks its G adjacent columns with THE rule (ms_select, altro_common.hpp) over the
+//               status, cost and violation altro_get_stats reports; ~20 bytes per instance, any mapping would do.
+// k_ms_spread   copies the winner's column over the other starts of its problem: kColTraj | kColRows | kColGains | kColCosts
+//               of copy_column's parts.  A kernel of its own, not G - 1 calls of copy_column: copy_column serves ONE (source,
+//               destination) pair with the lanes walking the knots, a stride of Bp records between neighbouring lanes and
+//               8-byte accesses.  Here every real column of the batch is a destination (or a winner, skipped), and the
+//               records of one knot are contiguous over the columns -- arr[(k * Bp + b) * EP + e] -- so the lanes run along
+//               (b, e) in 16-byte units: stores are fully coalesced, and the G lanes that read the same unit of a winner
+//               hit the cache line the first one fetched.  The winner's column is only read and the others are only
+//               written, so no two workgroups need ordering.  Only columns b < B are touched (shadow columns are scratch);
+//               all indexing is by Bp.  The row arrays [row][Bp] are 8-byte elements (a problem's run of G starts begins
+//               at any column, so no 16-byte alignment holds there): one element per lane, coalesced all the same.
+// k_ms_perturb  U += dU, one 16-byte unit (two controls) per lane; a plain fp64 addition, no multiply anywhere near it.
+// k_ms_stats    altro_stats of the winners (GetStats' fields) for altro_multistart_get_best.
+// -------------------------------------------------------------------------------------------------
+constexpr int kMsThreads = 256;
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_ms_select(DevArrays<T> A, int G, int P, int ilqr_mode, int* __restrict__ winner,
+                                                      int* __restrict__ log, int log_stride, int log_off) {
+  const int p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= P) return;
+  const size_t b0 = (size_t)p * G;
+  const int w = ms_select((ilqr_mode ? A.status : A.status_al) + b0, A.cost_cur + b0, A.viol + b0, G, 1);
+  winner[p] = w;
+  if (log) log[(size_t)p * log_stride + log_off] = w;
+}
+struct MsSpreadArgs {
+  int G, B;
+  const int* winner;  // [B / G]
+  uint4* rec[3];      // X, U, gain records as 16-byte units
+  int rec_knots[3];
+  int rec_vecs[3];    // 16-byte units of one record
+  int rows, knots1;   // total constraint rows, N + 1
+};
+template <class T>
+__global__ __launch_bounds__(kMsThreads) void k_ms_spread(DevArrays<T> A, MsSpreadArgs g) {
+  const int job = (int)blockIdx.y;
+  const size_t Bp = (size_t)A.Bp, B = (size_t)g.B;
+  const size_t first = (size_t)blockIdx.x * kMsThreads + threadIdx.x, step = (size_t)gridDim.x * kMsThreads;
+  if (job < 3) {
+    uint4* __restrict__ arr = g.rec[job];
+    const size_t V = (size_t)g.rec_vecs[job], per_knot = B * V, total = (size_t)g.rec_knots[job] * per_knot;
+    for (size_t i = first; i < total; i += step) {
+      const size_t k = i / per_knot, r = i - k * per_knot, b = r / V, v = r - b * V;
+      const int p = (int)(b / (size_t)g.G), w = g.winner[p];
+      const size_t src = (size_t)p * g.G + (size_t)w;
+      if (src != b) arr[(k * Bp + b) * V + v] = arr[(k * Bp + src) * V + v];
+    }
+  } else {
+    T* __restrict__ arr = job == 3 ? A.lam : job == 4 ? A.pen : job == 5 ? A.cval : A.costs;
+    const size_t total = (size_t)(job == 6 ? g.knots1 : g.rows) * B;
+    for (size_t i = first; i < total; i += step) {
+      const size_t r = i / B, b = i - r * B;
+      const int p = (int)(b / (size_t)g.G), w = g.winner[p];
+      const size_t src = (size_t)p * g.G + (size_t)w;
+      if (src != b) arr[r * Bp + b] = arr[r * Bp + src];
+    }
+  }
+}
+// dU[(c * N + k) * m + i], c = the start of column b (per_instance = 0) or b itself
+template <class T>
+__global__ __launch_bounds__(kMsThreads) void k_ms_perturb(DevArrays<T> A, const double* __restrict__ dU, int G, int per_instance,
+                                                           int m, int mP) {
+  static_assert(sizeof(T) == 8, "the controls are fp64 records: two to a 16-byte unit");
+  const size_t V = (size_t)(mP / 2), B = (size_t)A.B, per_knot = B * V, total = (size_t)A.N * per_knot;
+  const size_t i = (size_t)blockIdx.x * kMsThreads + threadIdx.x;
+  if (i >= total) return;
+  const size_t k = i / per_knot, r = i - k * per_knot, b = r / V, v = r - b * V;
+  const size_t c = per_instance ? b : b % (size_t)G;
+  const double* __restrict__ d = dU + (c * (size_t)A.N + k) * (size_t)m;
+  double2* u = reinterpret_cast<double2*>(A.U + (k * (size_t)A.Bp + b) * (size_t)mP) + v;
+  double2 x = *u;
+  const int e = 2 * (int)v;
+  if (e < m) x.x = x.x + d[e];
+  if (e + 1 < m) x.y = x.y + d[e + 1];
+  *u = x;
+}
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_ms_stats(DevArrays<T> A, const int* __restrict__ winner, int G, int P, int ilqr_mode,
+                                                     altro_stats* __restrict__ out) {
+  const int p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= P) return;
+  const size_t b = (size_t)p * G + (size_t)winner[p];
+  altro_stats s;
+  s.status_ilqr = A.status[b];
+  s.status = ilqr_mode ? s.status_ilqr : A.status_al[b];
+  s.iterations_inner = A.it_inner[b];
+  s.iterations_outer = A.it_outer[b];
+  s.iterations_total = A.it_total[b];
+  s.reserved = 0;
+  s.cost = A.cost_cur[b];
+  s.initial_cost = A.initial_cost[b];
+  s.cost_decrease = A.dJ[b];
+  s.gradient = A.grad[b];
+  s.violation = A.viol[b];
+  s.max_penalty = A.penmax[b];
+  s.alpha = A.alpha[b];
+  s.regularization = A.reg_log[b];
+  s.improvement_ratio = A.z[b];
+  out[p] = s;
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@
 #include "../altro_mpc.h"
 #include "../altro_tracking.h"
 #include "../altro_knot_params.h"
+#include "../altro_multistart.h"
 
 namespace altro {
 
@@ -1453,6 +1454,23 @@ class AugmentedLagrangianiLQR {
     ilqr_solver_.PushOptions();  // (rows that start afresh take the caller's initial_penalty)
     detail::Check(Handle(), altro_mpc_advance(Handle(), shift, x0, 1, w), "altro_mpc_advance");
     ilqr_solver_.Pull(true, false);
+  }
+  // Multi-start (include/altro_multistart.h): the batch holds BatchSize() / starts problems with `starts` adjacent instances
+  // each.  Thin calls of the C entry points; the two that change the device's trajectory pull it into the caller's
+  // Trajectory like AdvanceHorizon.
+  void SelectStarts(int starts, int* winner) {
+    detail::Check(Handle(), altro_multistart_select(Handle(), starts, winner), "altro_multistart_select");
+  }
+  void SpreadBestStart(int starts, int* winner = nullptr) {
+    detail::Check(Handle(), altro_multistart_spread(Handle(), starts, winner), "altro_multistart_spread");
+    ilqr_solver_.Pull(true, false);
+  }
+  void PerturbControls(int starts, const double* dU, bool per_instance = false) {
+    detail::Check(Handle(), altro_multistart_perturb(Handle(), starts, dU, per_instance ? 1 : 0), "altro_multistart_perturb");
+    ilqr_solver_.Pull(true, false);
+  }
+  void GetBestStarts(int starts, double* X, double* U, altro_stats* stats = nullptr, int* winner = nullptr) {
+    detail::Check(Handle(), altro_multistart_get_best(Handle(), starts, X, U, stats, winner), "altro_multistart_get_best");
   }
   // The reference path of the tracking costs (include/altro_tracking.h): Xref [rows][n], Uref [rows][m] (null: zeros), or
   // [B][rows][.] with per_instance; knot k follows row min(offset + k, rows - 1), and AdvanceHorizon moves the offset along.
