@@ -11,6 +11,9 @@ the shapes, one per branch of the backward dispatch (altro_engine.hpp, LaunchBac
   (13,2) (6,5)             k_backward_coop (beyond the 16 x 16 tile; m > 4)
   (3,5)                    k_backward (the one-lane-per-instance VALU kernel), n <= 3 with m > 2
 
+The knot-routed twins of the expansion, forward and cost kernels (tracking costs, knot constraints) run the same ten shapes
+in tests/test_knot_shapes_gpu.py.
+
 Every comparison lands in the ledger (tests/_ledger.py) next to its bar."""
 import ctypes
 import os
