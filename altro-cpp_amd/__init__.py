@@ -27,6 +27,7 @@ OK, INVALID_ARG, HIP_ERROR, NOT_READY, UNSUPPORTED = 0, 1, 2, 3, 4
 F64, F32 = 0, 1
 MODEL_UNICYCLE, MODEL_TRIPLE_INTEGRATOR, MODEL_QUADROTOR12 = 1, 2, 3
 CON_GOAL, CON_CONTROL_BOUND, CON_CIRCLE, CON_USER = 1, 2, 3, 4
+TEAM_ALL, TEAM_PRIORITY = 0, 1  # include/altro_team.h
 # altro::SolverStatus, altro/common/solver_stats.hpp:20-31
 (SOLVED, UNSOLVED, STATE_LIMIT, CONTROL_LIMIT, COST_INCREASE, MAX_ITERATIONS, MAX_OUTER_ITERATIONS,
  MAX_INNER_ITERATIONS, MAX_PENALTY, BACKWARD_PASS_REGULARIZATION_FAILED) = range(10)
@@ -769,6 +770,63 @@ class BatchSolver:
         self._call("mpc_run_multistart", C.c_int(starts), C.c_int(cycles), C.c_int(shift), _dp(w), _dp(dU), C.c_int(per_instance),
                    _dp(X), _dp(U), self._ip(it), self._ip(st), self._ip(win))
         return dict(X_cl=X, U_cl=U, iterations=it, status=st, winner=win[:self._problems(starts), :max(cycles, 0)])
+
+    # -- teams (include/altro_team.h) ---------------------------------------------------------------
+    # A handle of batch = T * agents instances holds T teams; agent a of team t is instance t * agents + a.  ``index`` is the
+    # team's knot circle constraint, add_knot_constraint(CON_CIRCLE, k_begin, k_end, 3 * (agents - 1)).
+    def _teams(self, agents):
+        agents = int(agents)
+        return self.batch // agents if agents >= 2 and self.batch % agents == 0 else 0
+
+    def _team_radius(self, agents, radius):
+        radius = _f64(radius)
+        if radius is None or radius.shape not in ((int(agents),), (self.batch,)):
+            raise ValueError(f"radius must have shape ({int(agents)},) or ({self.batch},)")
+        # (agents == batch: both shapes coincide, and so do the two layouts)
+        return radius, 1 if radius.shape[0] == self.batch and int(agents) != self.batch else 0
+
+    def team_fill_tracks(self, agents, index, radius, mode=TEAM_ALL, blend=1.0):
+        """Fill the track of the team constraint from the plans on the device: circle slot i of agent a is peer
+        j = i if i < a else i + 1 with centre X_j[r][0:2] and radius radius[a] + radius[j] (0 for j > a under
+        TEAM_PRIORITY); ``blend`` < 1 moves the centres only that fraction of the way from what the window shows now."""
+        radius, per = self._team_radius(agents, radius)
+        self._call("team_fill_tracks", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_int(mode), C.c_double(blend))
+
+    def team_clearance(self, agents, index, radius):
+        """[T]: per team the minimum over the constraint's knots and all pairs a < j of |p_a - p_j|^2 - (r_a + r_j)^2."""
+        radius, per = self._team_radius(agents, radius)
+        out = np.zeros(max(self._teams(agents), 1))
+        self._call("team_clearance", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), _dp(out))
+        return out[:self._teams(agents)]
+
+    def team_clearance_device(self, agents, index, radius, clear_ptr):
+        """team_clearance into fp64 memory [T] of this handle's device."""
+        radius, per = self._team_radius(agents, radius)
+        self._call("team_clearance_device", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_void_p(clear_ptr or None))
+
+    def team_solve(self, agents, index, radius, mode=TEAM_ALL, blend=1.0, rounds=1):
+        """``rounds`` x (team_fill_tracks; solve)."""
+        radius, per = self._team_radius(agents, radius)
+        self._call("team_solve", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_int(mode), C.c_double(blend),
+                   C.c_int(rounds))
+
+    def mpc_run_team(self, agents, index, radius, mode=TEAM_ALL, blend=1.0, rounds=1, cycles=1, shift=1, w=None):
+        """``cycles`` x (team_solve(rounds); team_clearance into a device log; mpc_advance(shift, w=w[c])) with nothing
+        crossing to the host inside the loop.  Returns dict(X_cl, U_cl, iterations, status as mpc_run gives them, and
+        clear [T][cycles])."""
+        radius, per = self._team_radius(agents, radius)
+        w = _f64(w)
+        if w is not None and w.shape != (cycles, self.batch, self.n):
+            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {self.n})")
+        L = max(cycles, 0) * max(shift, 0)
+        X = np.zeros((self.batch, L + 1, self.n))
+        U = np.zeros((self.batch, L, self.m))
+        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        clear = np.zeros((max(self._teams(agents), 1), max(cycles, 1)))
+        self._call("mpc_run_team", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_int(mode), C.c_double(blend),
+                   C.c_int(rounds), C.c_int(cycles), C.c_int(shift), _dp(w), _dp(X), _dp(U), self._ip(it), self._ip(st), _dp(clear))
+        return dict(X_cl=X, U_cl=U, iterations=it, status=st, clear=clear[:self._teams(agents), :max(cycles, 0)])
 
     # -- device interop ---------------------------------------------------------------------------
     def pack_results_device(self, device_ptr):

@@ -37,12 +37,13 @@
 #include "../../include/altro_tracking.h"
 #include "../../include/altro_knot_params.h"
 #include "../../include/altro_multistart.h"
+#include "../../include/altro_team.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 12  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 13  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -1519,6 +1520,159 @@ altro_status altro_mpc_run_multistart(altro_handle h, int starts, int cycles, in
   if (h->uploaded) {
     const std::string err = h->err;
     altro_status es = h->engine->MsRunEnd(winner);  // (also after a failure: both free their device blocks)
+    const altro_status el = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);
+    if (es == ALTRO_OK) es = el;
+    if (st == ALTRO_OK && es != ALTRO_OK) {
+      h->err = h->engine->LastError();
+      st = es;
+    } else {
+      h->err = err;
+    }
+  }
+  return st;
+}
+
+}  // extern "C"
+
+// ---- teams (include/altro_team.h) ---------------------------------------------------------------------------------------
+namespace {
+
+// everything that can be refused without a device; the radii come back one per instance
+altro_status TeamCheck(altro_handle h, int agents, int index, const double* radius, int radius_per_instance, const char* who,
+                       std::vector<double>* rad) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const int B = h->spec.desc.batch;
+  if (agents < 2 || B % agents != 0) {
+    h->err = std::string(who) + ": agents must be at least 2 and divide the batch of " + std::to_string(B) + ", got " +
+             std::to_string(agents);
+    return ALTRO_INVALID_ARG;
+  }
+  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
+    h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
+    return ALTRO_INVALID_ARG;
+  }
+  const ConSpec& c = h->spec.cons[index];
+  if (c.kind != ALTRO_CON_CIRCLE || c.nparams != 3 * (agents - 1)) {
+    h->err = std::string(who) + ": constraint " + std::to_string(index) + " must be an ALTRO_CON_CIRCLE with nparams = 3 (agents - 1) = " +
+             std::to_string(3 * (agents - 1));
+    return ALTRO_INVALID_ARG;
+  }
+  if (!radius) {
+    h->err = std::string(who) + ": radius is required";
+    return ALTRO_INVALID_ARG;
+  }
+  rad->resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const double r = radius[radius_per_instance ? b : b % agents];
+    if (!(r >= 0.0) || !(r < std::numeric_limits<double>::infinity())) {
+      h->err = std::string(who) + ": every radius must be finite and not negative";
+      return ALTRO_INVALID_ARG;
+    }
+    (*rad)[(size_t)b] = r;
+  }
+  return ALTRO_OK;
+}
+altro_status TeamModeCheck(altro_handle h, int mode, double blend, const char* who) {
+  if (mode != ALTRO_TEAM_ALL && mode != ALTRO_TEAM_PRIORITY) {
+    h->err = std::string(who) + ": the mode is ALTRO_TEAM_ALL or ALTRO_TEAM_PRIORITY";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!(blend > 0.0) || !(blend <= 1.0)) {  // (a NaN fails both)
+    h->err = std::string(who) + ": blend must lie in (0, 1]";
+    return ALTRO_INVALID_ARG;
+  }
+  return ALTRO_OK;
+}
+altro_status TeamClearanceImpl(altro_handle h, int agents, int index, const double* radius, int radius_per_instance, double* clear,
+                               int on_device, const char* who) {
+  std::vector<double> rad;
+  const altro_status st = TeamCheck(h, agents, index, radius, radius_per_instance, who, &rad);
+  if (st != ALTRO_OK) return st;
+  if (!clear) {
+    h->err = std::string(who) + ": clear is required";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) {
+    const altro_status s = e.TeamRadius(rad.data());
+    return s != ALTRO_OK ? s : e.TeamClearance(agents, index, clear, on_device);
+  });
+}
+// rounds x (fill; solve) with the radii already on the device
+altro_status TeamRounds(altro_handle h, int agents, int index, int mode, double blend, int rounds) {
+  altro_status st = ALTRO_OK;
+  for (int r = 0; r < rounds && st == ALTRO_OK; ++r) {
+    st = Forward(h, [&](EngineBase& e) { return e.TeamFill(agents, index, mode, blend); });
+    if (st == ALTRO_OK) st = altro_solve_al(h);
+  }
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+altro_status altro_team_fill_tracks(altro_handle h, int agents, int index, const double* radius, int radius_per_instance, int mode,
+                                    double blend) {
+  std::vector<double> rad;
+  altro_status st = TeamCheck(h, agents, index, radius, radius_per_instance, "altro_team_fill_tracks", &rad);
+  if (st == ALTRO_OK) st = TeamModeCheck(h, mode, blend, "altro_team_fill_tracks");
+  if (st != ALTRO_OK) return st;
+  return Forward(h, [&](EngineBase& e) {
+    const altro_status s = e.TeamRadius(rad.data());
+    return s != ALTRO_OK ? s : e.TeamFill(agents, index, mode, blend);
+  });
+}
+altro_status altro_team_clearance(altro_handle h, int agents, int index, const double* radius, int radius_per_instance, double* clear) {
+  return TeamClearanceImpl(h, agents, index, radius, radius_per_instance, clear, 0, "altro_team_clearance");
+}
+altro_status altro_team_clearance_device(altro_handle h, int agents, int index, const double* radius, int radius_per_instance,
+                                         void* clear_device) {
+  return TeamClearanceImpl(h, agents, index, radius, radius_per_instance, (double*)clear_device, 1, "altro_team_clearance_device");
+}
+altro_status altro_team_solve(altro_handle h, int agents, int index, const double* radius, int radius_per_instance, int mode,
+                              double blend, int rounds) {
+  std::vector<double> rad;
+  altro_status st = TeamCheck(h, agents, index, radius, radius_per_instance, "altro_team_solve", &rad);
+  if (st == ALTRO_OK) st = TeamModeCheck(h, mode, blend, "altro_team_solve");
+  if (st != ALTRO_OK) return st;
+  if (rounds < 1) {
+    h->err = "altro_team_solve: at least one round";
+    return ALTRO_INVALID_ARG;
+  }
+  st = Forward(h, [&](EngineBase& e) { return e.TeamRadius(rad.data()); });
+  if (st == ALTRO_OK) st = TeamRounds(h, agents, index, mode, blend, rounds);
+  return st;
+}
+altro_status altro_mpc_run_team(altro_handle h, int agents, int index, const double* radius, int radius_per_instance, int mode,
+                                double blend, int rounds, int cycles, int shift, const double* w, double* X_cl, double* U_cl,
+                                int* iterations, int* status, double* clear) {
+  std::vector<double> rad;
+  altro_status st = TeamCheck(h, agents, index, radius, radius_per_instance, "altro_mpc_run_team", &rad);
+  if (st == ALTRO_OK) st = TeamModeCheck(h, mode, blend, "altro_mpc_run_team");
+  if (st != ALTRO_OK) return st;
+  if (rounds < 1 || cycles < 1) {
+    h->err = "altro_mpc_run_team: at least one round and one cycle";
+    return ALTRO_INVALID_ARG;
+  }
+  st = MpcCheck(h, shift, "altro_mpc_run_team");
+  if (st != ALTRO_OK) return st;
+  st = Forward(h, [&](EngineBase& e) { return e.TeamRadius(rad.data()); });
+  if (st == ALTRO_OK) st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
+  if (st == ALTRO_OK) st = Forward(h, [&](EngineBase& e) { return e.TeamRunBegin(agents, cycles, w); });
+  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
+    st = TeamRounds(h, agents, index, mode, blend, rounds);
+    if (st != ALTRO_OK) break;
+    const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
+    st = Forward(h, [&](EngineBase& e) { return e.TeamRunCycle(agents, index, shift, pen); });
+    if (st == ALTRO_OK) {  // (as behind altro_mpc_advance: the initial state now lives on the device alone)
+      h->spec.x0.clear();
+      h->spec.x0_per_instance = 0;
+    }
+  }
+  if (h->uploaded) {
+    const std::string err = h->err;
+    altro_status es = h->engine->TeamRunEnd(clear);  // (also after a failure: both free their device blocks)
     const altro_status el = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);
     if (es == ALTRO_OK) es = el;
     if (st == ALTRO_OK && es != ALTRO_OK) {

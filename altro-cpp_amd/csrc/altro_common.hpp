@@ -134,10 +134,12 @@ struct TrackArgs {
 
 // ---- knot constraints (include/altro_knot_params.h) ----------------------------------------------------
 // One launch of k_knot_params: every knot constraint of the handle, its knots, its place in the knot-parameter record and
-// its track on the device -- track[(col * rows + row) * np + e], the caller's layout, cols = 1 (shared) or B.
+// its track on the device -- track[(col * rows + row) * np + e], the caller's layout, cols = 1 (shared) or B.  Knot k reads
+// row min(max(offset - base, 0) + k, rows - 1): base is 0 for every track a caller set, and the window offset at the
+// moment of the fill for a track written by altro_team_fill_tracks (include/altro_team.h), whose row 0 is "now".
 struct KnotTrack {
   const double* track;  // nullptr: no track set yet (the record keeps zeros)
-  int k_begin, k_end, np, off, rows, cols;
+  int k_begin, k_end, np, off, rows, cols, base;
 };
 struct KnotParArgs {
   int ncon, kt, offset, pad;
@@ -463,6 +465,18 @@ class EngineBase {
   virtual altro_status MsRunBegin(int G, int cycles, const double* w, const double* dU, int dU_per_instance) = 0;
   virtual altro_status MsRunCycle(int shift, double reset_pen, bool ilqr_mode) = 0;
   virtual altro_status MsRunEnd(int* winner) = 0;
+  // teams (include/altro_team.h): A adjacent columns are the agents of one team, `index` the registration index of the team's
+  // knot circle constraint.  TeamRadius copies the radii (host, one per instance) to the device, where they stay for the
+  // fills and clearances that follow; clear is [B / A], host or (on_device) memory of the engine's device.
+  virtual altro_status TeamRadius(const double* radius_per_instance) = 0;
+  virtual altro_status TeamFill(int A, int index, int mode, double blend) = 0;
+  virtual altro_status TeamClearance(int A, int index, double* clear, int on_device) = 0;
+  // altro_mpc_run_team: Begin copies w ([cycles][B][n], may be null) to the device once and opens the clearance log; every
+  // Cycle (behind the team solve) logs the clearance and advances by `shift` under its w; End downloads clear[B / A][cycles]
+  // (may be null) and frees the block
+  virtual altro_status TeamRunBegin(int A, int cycles, const double* w) = 0;
+  virtual altro_status TeamRunCycle(int A, int index, int shift, double reset_pen) = 0;
+  virtual altro_status TeamRunEnd(double* clear) = 0;
   virtual const char* LastError() = 0;
 };
 

@@ -704,6 +704,12 @@ class Engine final : public EngineBase {
     double* d_track = nullptr;
     size_t cap = 0;
     int rows = 0, cols = 0;
+    // a track written by altro_team_fill_tracks (include/altro_team.h): row 0 belongs to window offset `base` (0 for every
+    // track a caller set), `team` marks it, and the fill writes into the spare buffer and swaps
+    int base = 0;
+    bool team = false;
+    double* d_spare = nullptr;
+    size_t spare_cap = 0;
   };
   KnotCon* FindKnotCon(int index, const char* who) {
     for (KnotCon& c : kcons_)
@@ -734,6 +740,8 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(hipMemcpyAsync(c->d_track, P, need * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
     c->rows = rows;
     c->cols = cols;
+    c->base = 0;
+    c->team = false;
     LaunchKnotParams();
     return Sync();
   }
@@ -763,13 +771,15 @@ class Engine final : public EngineBase {
     g.offset = track_offset_;
     for (int j = 0; j < g.ncon; ++j) {
       const KnotCon& c = kcons_[j];
-      g.c[j] = KnotTrack{c.rows > 0 ? c.d_track : nullptr, c.k_begin, c.k_end, c.np, c.off, c.rows, c.cols};
+      g.c[j] = KnotTrack{c.rows > 0 ? c.d_track : nullptr, c.k_begin, c.k_end, c.np, c.off, c.rows, c.cols, c.base};
     }
     hipLaunchKernelGGL((k_knot_params<0>), GridBK(), dim3(kBlock), 0, stream_, g, d_kpar_, B_, Bp_);
   }
   void DropKnotCons() {
-    for (KnotCon& c : kcons_)
+    for (KnotCon& c : kcons_) {
       if (c.d_track) hipFree(c.d_track);
+      if (c.d_spare) hipFree(c.d_spare);
+    }
     kcons_.clear();
     d_kpar_ = nullptr;
     track_offset_ = 0;
@@ -1040,6 +1050,135 @@ class Engine final : public EngineBase {
     if (e == hipSuccess && winner && ms_run_.win && ms_run_.cycle == ms_run_.cycles)
       e = CopySync(winner, ms_run_.win, (size_t)(B_ / ms_run_.G) * ms_run_.cycles * sizeof(int), hipMemcpyDeviceToHost);
     MsRunDrop();
+    ALTRO_HIP_CHECK(e);
+    return ALTRO_OK;
+  }
+
+  // ---- teams (include/altro_team.h) -----------------------------------------------------------------
+  // A adjacent columns are the agents of one team; the team's knot circle constraint gets its per-instance track from the
+  // plans in X (k_team_tracks, into the constraint's spare buffer, then the two swap).  The radii live on the device, one per
+  // instance, from TeamRadius on.  Everything runs on the engine's stream.  The C API has checked every argument it can.
+  KnotCon* TeamCheck(int A, int index, const char* who) {
+    if (A < 2 || B_ % A != 0) {
+      err_ = std::string(who) + ": agents must be at least 2 and divide the batch";
+      return nullptr;
+    }
+    KnotCon* c = FindKnotCon(index, who);
+    if (!c) return nullptr;
+    if (c->kind != ALTRO_CON_CIRCLE || c->np != 3 * (A - 1) || n < 2) {
+      err_ = std::string(who) + ": constraint " + std::to_string(index) + " must be a knot circle constraint with 3 (agents - 1) parameters";
+      return nullptr;
+    }
+    return c;
+  }
+  altro_status TeamRadius(const double* radius) override {
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    if (!d_team_rad_) ALTRO_HIP_CHECK(hipMalloc((void**)&d_team_rad_, 2 * (size_t)B_ * sizeof(double)));  // radii | clearances
+    ALTRO_HIP_CHECK(CopySync(d_team_rad_, radius, (size_t)B_ * sizeof(double), hipMemcpyHostToDevice));
+    return ALTRO_OK;
+  }
+  altro_status TeamFill(int A, int index, int mode, double blend) override {
+    KnotCon* c = TeamCheck(A, index, "altro_team_fill_tracks");
+    if (!c) return ALTRO_INVALID_ARG;
+    if (!d_team_rad_) {
+      err_ = "altro_team_fill_tracks: no radii on the device yet";
+      return ALTRO_NOT_READY;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(Sync());
+    ctg_replayable_ = false;  // (as SetConstraintTrack)
+    const int rows = N_ + 1;
+    const size_t need = (size_t)B_ * rows * c->np;
+    if (need > c->spare_cap) {
+      if (c->d_spare) ALTRO_HIP_CHECK(hipFree(c->d_spare));
+      c->d_spare = nullptr;
+      c->spare_cap = 0;
+      ALTRO_HIP_CHECK(hipMalloc((void**)&c->d_spare, need * sizeof(double)));
+      c->spare_cap = need;
+    }
+    TeamFillArgs g{};
+    g.out = c->d_spare;
+    // a track last written by a team fill has this very shape; any other is replaced, not blended
+    g.old = c->team && c->rows == rows && c->cols == B_ && blend != 1.0 ? c->d_track : nullptr;
+    g.radius = d_team_rad_;
+    g.A = A;
+    g.B = B_;
+    g.rows = rows;
+    g.priority = mode == 1 ? 1 : 0;
+    g.ahead = track_offset_ > c->base ? track_offset_ - c->base : 0;
+    g.blend = blend;
+    const size_t total = (size_t)B_ * rows * (A - 1);
+    hipLaunchKernelGGL(k_team_tracks<T>, dim3((unsigned)((total + kTeamThreads - 1) / kTeamThreads)), dim3(kTeamThreads), 0, stream_,
+                       (const T*)A_.X, R::nP, Bp_, g);
+    std::swap(c->d_track, c->d_spare);
+    std::swap(c->cap, c->spare_cap);
+    c->rows = rows;
+    c->cols = B_;
+    c->base = track_offset_;
+    c->team = true;
+    LaunchKnotParams();
+    return Sync();
+  }
+  void LaunchTeamClearance(int A, const KnotCon& c, double* clear, int stride, int off) {
+    const int teams = B_ / A, per_block = kTeamThreads / 64;
+    hipLaunchKernelGGL(k_team_clearance<T>, dim3((teams + per_block - 1) / per_block), dim3(kTeamThreads), 0, stream_, (const T*)A_.X,
+                       R::nP, Bp_, (const double*)d_team_rad_, A, teams, c.k_begin, c.k_end, clear, stride, off);
+  }
+  altro_status TeamClearance(int A, int index, double* clear, int on_device) override {
+    KnotCon* c = TeamCheck(A, index, "altro_team_clearance");
+    if (!c || !d_team_rad_ || !clear) return ALTRO_INVALID_ARG;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    double* dst = on_device ? clear : d_team_rad_ + B_;
+    LaunchTeamClearance(A, *c, dst, 1, 0);
+    ALTRO_TRY(Sync());
+    if (!on_device) ALTRO_HIP_CHECK(CopySync(clear, dst, (size_t)(B_ / A) * sizeof(double), hipMemcpyDeviceToHost));
+    return ALTRO_OK;
+  }
+  // altro_mpc_run_team: w goes to the device once, the clearances of every cycle stay there until the end
+  struct TeamRun {
+    double *blk = nullptr, *w = nullptr, *clear = nullptr;  // clear: [B / A][cycles]
+    int A = 0, cycles = 0, cycle = 0;
+  };
+  void TeamRunDrop() {
+    if (team_run_.blk) hipFree(team_run_.blk);
+    team_run_ = TeamRun{};
+  }
+  altro_status TeamRunBegin(int A, int cycles, const double* w) override {
+    if (A < 2 || B_ % A != 0 || cycles < 1) {
+      err_ = "altro_mpc_run_team: agents must be at least 2 and divide the batch, and there is at least one cycle";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    TeamRunDrop();
+    const size_t nw = w ? (size_t)cycles * B_ * n : 0, nc = (size_t)(B_ / A) * cycles;
+    ALTRO_HIP_CHECK(hipMalloc((void**)&team_run_.blk, (nw + nc) * sizeof(double)));
+    team_run_.clear = team_run_.blk;
+    if (w) {
+      team_run_.w = team_run_.blk + nc;
+      ALTRO_HIP_CHECK(CopySync(team_run_.w, w, nw * sizeof(double), hipMemcpyHostToDevice));
+    }
+    team_run_.A = A;
+    team_run_.cycles = cycles;
+    return ALTRO_OK;
+  }
+  altro_status TeamRunCycle(int A, int index, int shift, double reset_pen) override {
+    KnotCon* c = TeamCheck(A, index, "altro_mpc_run_team");
+    if (!c || !d_team_rad_) return ALTRO_INVALID_ARG;
+    if (!team_run_.blk || A != team_run_.A || team_run_.cycle >= team_run_.cycles) {
+      err_ = "altro_mpc_run_team: no cycle left";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    const int cy = team_run_.cycle++;
+    LaunchTeamClearance(A, *c, team_run_.clear, team_run_.cycles, cy);
+    return MpcAdvance(shift, nullptr, team_run_.w ? team_run_.w + (size_t)cy * B_ * n : nullptr, 1, reset_pen);
+  }
+  altro_status TeamRunEnd(double* clear) override {
+    hipError_t e = hipSetDevice(desc_.device_id);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e == hipSuccess && clear && team_run_.blk && team_run_.cycle == team_run_.cycles)
+      e = CopySync(clear, team_run_.clear, (size_t)(B_ / team_run_.A) * team_run_.cycles * sizeof(double), hipMemcpyDeviceToHost);
+    TeamRunDrop();
     ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
   }
@@ -1467,6 +1606,9 @@ class Engine final : public EngineBase {
     MsRunDrop();
     if (d_ms_win_) hipFree(d_ms_win_);
     d_ms_win_ = nullptr;
+    TeamRunDrop();
+    if (d_team_rad_) hipFree(d_team_rad_);
+    d_team_rad_ = nullptr;
     if (d_stage_) hipFree(d_stage_);
     d_stage_ = nullptr;
     stage_cap_ = 0;
@@ -2067,8 +2209,10 @@ class Engine final : public EngineBase {
       ref_offset_ = s.ref_offset;
     }
     // the knot constraints, and whatever altro_set_constraint_track / altro_set_track_offset recorded before the upload
-    for (KnotCon& c : kcons_)
+    for (KnotCon& c : kcons_) {
       if (c.d_track) hipFree(c.d_track);
+      if (c.d_spare) hipFree(c.d_spare);
+    }
     kcons_.clear();
     for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i) {
       if (con_knot_off_[i] < 0) continue;
@@ -2924,6 +3068,8 @@ class Engine final : public EngineBase {
   TrackedLog tracked_;                                  // closed-loop log of altro_mpc_run_tracked
   int* d_ms_win_ = nullptr;                             // winners of the last multi-start call, [B] (MsCheck)
   MsRun ms_run_;                                        // altro_mpc_run_multistart (MsRunBegin .. MsRunEnd)
+  double* d_team_rad_ = nullptr;                        // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
+  TeamRun team_run_;                                    // altro_mpc_run_team (TeamRunBegin .. TeamRunEnd)
   std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;
   volatile int* h_counter_ = nullptr;  // pinned + mapped: one word per sweep

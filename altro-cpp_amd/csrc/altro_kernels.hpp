@@ -5427,7 +5427,7 @@ __global__ __launch_bounds__(kBlock) void k_ref_terms(DevArrays<T> A, const Prob
 // -------------------------------------------------------------------------------------------------
 // The knot-parameter records of the knot constraints (include/altro_knot_params.h: altro_add_knot_constraint,
 // altro_set_constraint_track).  For knot k = blockIdx.y (wave-uniform) and column b, every knot constraint attached to k has
-// row min(offset + k, rows - 1) of its track copied into the record kpar[(k * Bp + b) * kt + off + e]; a constraint that
+// row min(max(offset - base, 0) + k, rows - 1) of its track (KnotTrack::base, altro_common.hpp) copied into the record kpar[(k * Bp + b) * kt + off + e]; a constraint that
 // is not attached, or has no track yet, leaves zeros, and so does the padding element.  A COPY: a constant track leaves the
 // bits an ordinary constraint holds in the parameter pool.  The row, and every constraint's range, place and width, depend
 // on the knot alone (scalar registers); model-independent, no LDS.  THE ONLY PLACE the records are written.
@@ -5447,13 +5447,122 @@ __global__ __launch_bounds__(kBlock) void k_knot_params(KnotParArgs g, double* _
   for (int j = 0; j < g.ncon; ++j) {
     const KnotTrack& c = g.c[j];
     const bool live = c.track != nullptr && k >= c.k_begin && k < c.k_end;
-    const long long want = (long long)g.offset + (long long)k;
+    const int ahead = g.offset > c.base ? g.offset - c.base : 0;  // (base: 0, or the offset at which a team fill wrote row 0)
+    const long long want = (long long)ahead + (long long)k;
     const int row = (int)(want < (long long)(c.rows - 1) ? want : (long long)(c.rows - 1));  // the end of the track is held
     const double* src = live ? c.track + ((size_t)(c.cols > 1 ? b : 0) * (size_t)c.rows + (size_t)row) * (size_t)c.np : nullptr;
     for (int e = 0; e < c.np; ++e) rec[c.off + e] = live ? src[e] : 0.0;
     filled = c.off + c.np;
   }
   for (int e = filled; e < g.kt; ++e) rec[e] = 0.0;
+}
+
+// -------------------------------------------------------------------------------------------------
+// Teams (include/altro_team.h): A adjacent columns are the AGENTS of one team, T = B / A teams; for agent a every team-mate
+// is a moving circle whose track is the team-mate's plan.  Circle slot i of agent a is peer j = i < a ? i : i + 1.
+//
+// k_team_tracks     writes the whole per-instance track of the team's knot circle constraint, out[(b * rows + r) * np +
+//                   3 i + (cx | cy | radius)], rows = N + 1, np = 3 (A - 1), from X[(r * Bp + peer) * nP + (0 | 1)].  ONE LANE
+//                   PER (instance, row, slot) WITH THE SLOT FASTEST, THEN THE ROW, THEN THE INSTANCE -- the order of `out`, so
+//                   lane i stores the 24 bytes at out + 3 i and a wave stores 1536 contiguous bytes.  The other order (lanes
+//                   along the contiguous run of one knot's X records) would coalesce the loads and scatter the stores
+//                   rows * np * 8 bytes apart, 24 bytes each; the track is 3 (A - 1) / nP times the size of the X it is read
+//                   from (70 MB against 13 MB at 4096 x 101 x 8 agents), every X record is read by A - 1 lanes and the whole
+//                   of X stays in the caches, so the stores decide.  The A - 1 lanes of one (instance, row) read the records
+//                   of ONE team at one knot, A * nP * sizeof(T) contiguous bytes, each with one 16-byte load.  X is indexed by
+//                   Bp, only columns < B are read, and nothing but `out` is written.
+//                   Blending (old != nullptr): cx = old + blend * (new - old), each operation rounded on its own, old = row
+//                   min(ahead + r, rows - 1) of the track before the fill (ahead = max(offset - base, 0): what the window
+//                   shows now).  `out` is a second buffer: row r of the old track is still read by the lanes of rows
+//                   before it.  Radii are never blended: radius[b] + radius[peer], or 0 for a peer of lower priority
+//                   (ALTRO_TEAM_PRIORITY, j > a: c = -d^2 <= 0, never active).
+// k_team_clearance  min over knots [k_begin, k_end) and pairs a < j of (dx dx + dy dy) - R R, R = radius[a] + radius[j]: ONE
+//                   WAVE PER TEAM, the lanes along the knots, every lane over all pairs (the A records of a knot are
+//                   contiguous and stay in L1 over the pair loop), then a wave reduction; a NaN anywhere gives NaN.  min does
+//                   not depend on the order.  The result goes to clear[t * stride + off].
+// Both are model-independent, use no LDS, and keep products away from sums with pin(): the library is built with
+// -ffp-contract=fast, and the tests restate both in numpy bit for bit.
+// -------------------------------------------------------------------------------------------------
+constexpr int kTeamThreads = 256;
+struct TeamFillArgs {
+  double* out;           // [B][rows][3 (A - 1)]
+  const double* old;     // the track before the fill, same shape; nullptr: the centres are bit copies of X
+  const double* radius;  // [B]
+  int A, B, rows, priority, ahead;
+  double blend;
+};
+template <class T>
+__global__ __launch_bounds__(kTeamThreads) void k_team_tracks(const T* __restrict__ X, int nP, int Bp, TeamFillArgs g) {
+#pragma clang fp contract(off)
+  using V = typename VecOf<T>::type;
+  const size_t S = (size_t)(g.A - 1), per_col = (size_t)g.rows * S, total = (size_t)g.B * per_col;
+  const size_t i = (size_t)blockIdx.x * kTeamThreads + threadIdx.x;
+  if (i >= total) return;
+  const size_t b = i / per_col, rem = i - b * per_col;
+  const int r = (int)(rem / S), slot = (int)(rem - (size_t)r * S);
+  const int t = (int)(b / (size_t)g.A), a = (int)(b - (size_t)t * g.A), j = slot < a ? slot : slot + 1;
+  const size_t peer = (size_t)t * g.A + (size_t)j;  // (< B: a whole team lies inside the batch)
+  const V xy = *reinterpret_cast<const V*>(X + ((size_t)r * (size_t)Bp + peer) * (size_t)nP);
+  double cx = (double)xy.x, cy = (double)xy.y;
+  if (g.old) {
+    const int orow = g.ahead < g.rows - 1 - r ? g.ahead + r : g.rows - 1;
+    const double* o = g.old + (b * per_col + (size_t)orow * S + (size_t)slot) * 3;
+    const double ox = o[0], oy = o[1];
+    double dx = cx - ox, dy = cy - oy;
+    pin(dx);
+    pin(dy);
+    double px = g.blend * dx, py = g.blend * dy;
+    pin(px);
+    pin(py);
+    cx = ox + px;
+    cy = oy + py;
+  }
+  double* dst = g.out + 3 * i;
+  dst[0] = cx;
+  dst[1] = cy;
+  dst[2] = g.priority && j > a ? 0.0 : g.radius[b] + g.radius[peer];
+}
+template <class T>
+__global__ __launch_bounds__(kTeamThreads) void k_team_clearance(const T* __restrict__ X, int nP, int Bp, const double* __restrict__ radius,
+                                                                 int A, int teams, int k_begin, int k_end, double* __restrict__ clear,
+                                                                 int stride, int off) {
+#pragma clang fp contract(off)
+  using V = typename VecOf<T>::type;
+  const int lane = threadIdx.x & 63, t = blockIdx.x * (kTeamThreads / 64) + (threadIdx.x >> 6);
+  if (t >= teams) return;  // (a whole wave)
+  const size_t b0 = (size_t)t * (size_t)A;
+  double mn = __builtin_inf();
+  int bad = 0;
+  for (int k = k_begin + lane; k < k_end; k += 64) {
+    const T* row = X + ((size_t)k * (size_t)Bp + b0) * (size_t)nP;
+    for (int a = 0; a + 1 < A; ++a) {
+      const V pa = *reinterpret_cast<const V*>(row + (size_t)a * nP);
+      const double ra = radius[b0 + a];
+      for (int j = a + 1; j < A; ++j) {
+        const V pj = *reinterpret_cast<const V*>(row + (size_t)j * nP);
+        double dx = (double)pa.x - (double)pj.x, dy = (double)pa.y - (double)pj.y, R = ra + radius[b0 + j];
+        pin(dx);
+        pin(dy);
+        pin(R);
+        double xx = dx * dx, yy = dy * dy, RR = R * R;
+        pin(xx);
+        pin(yy);
+        pin(RR);
+        double d2 = xx + yy;
+        pin(d2);
+        const double v = d2 - RR;
+        bad |= v != v;
+        mn = v < mn ? v : mn;
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    const double other = __shfl_xor(mn, s);
+    mn = other < mn ? other : mn;
+  }
+  bad = __any(bad);
+  if (lane == 0) clear[(size_t)t * (size_t)stride + (size_t)off] = bad ? __builtin_nan("") : mn;
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -177,6 +177,57 @@ def ramped_bounds(make, batch=1, N=10, rows=16, offset=0, per_knot=False, dtype=
     return s
 
 
+TEAM_RING_RADIUS = 0.15
+
+
+def team_ring_states(teams, agents):
+    """(x0 [B][3], xf [B][3]) of team_ring: agent a of team t starts on the unit ring at angle phi = 2 pi a / A + 0.1 t heading
+    phi + pi (towards the centre) and goes to the ring's point at angle phi + pi + 0.2 + 0.05 t with the same heading."""
+    t, a = np.divmod(np.arange(teams * agents), agents)
+    phi = 2.0 * np.pi * a / agents + 0.1 * t
+    goal = phi + np.pi + 0.2 + 0.05 * t
+    x0 = np.stack([np.cos(phi), np.sin(phi), phi + np.pi], axis=-1)
+    xf = np.stack([np.cos(goal), np.sin(goal), phi + np.pi], axis=-1)
+    return x0, xf
+
+
+def team_ring(make, teams, agents, N=24, per_knot_track=None, U=None, dtype=F64, **kw):
+    """``teams`` teams of ``agents`` unicycles that swap sides of a ring through its centre (team_ring_states), instance
+    t * agents + a: kTurn90's cost (Q = R = 1e-2 h, Qf = 100, tf = 3) with a per-instance goal, the control bound +-1.5 on
+    [0, N), then the team's knot circle constraint on [1, N) -- ``s.team_circle``, 3 (agents - 1) parameters, every agent's
+    radius ``s.team_radius`` = 0.15 -- seeded with a shared one-row track of radius 0 (never active), so the first solve gives
+    the uncoupled plans that include/altro_team.h's fills start from.  Initial guess U = (0.1, 0), or ``U`` [B][N][2].
+
+    ``per_knot_track`` [B][N+1][3 (agents - 1)]: the reference's idiom instead -- one ordinary circle constraint per knot of
+    [1, N) from row k of the given rows (what the CPU oracle takes)."""
+    B = teams * agents
+    s = make(3, 2, N, B, dtype)
+    h = _f32step(3.0, N)
+    hd = float(h)
+    Q = np.eye(3) * (1e-2 * hd)
+    R = np.eye(2) * (1e-2 * hd)
+    Qf = np.eye(3) * 100.0
+    x0, xf = team_ring_states(teams, agents)
+    s.set_model(MODEL_UNICYCLE)
+    s.set_uniform_step(h)
+    s.set_lqr_cost(0, N, Q, R, xf, np.zeros(2))
+    s.set_lqr_cost(N, N + 1, Qf, R * 0, xf, np.zeros(2))
+    s.team_radius = np.full(agents, TEAM_RING_RADIUS)
+    if per_knot_track is not None:
+        rows = np.asarray(per_knot_track, dtype=np.float64)
+        for k in range(N):
+            s.add_constraint(CON_CONTROL_BOUND, k, k + 1, np.array([-1.5, -1.5, 1.5, 1.5]))
+            if k >= 1:
+                s.add_constraint(CON_CIRCLE, k, k + 1, rows[:, k])
+    else:
+        s.add_control_bound(0, N, [-1.5, -1.5], [1.5, 1.5])
+        s.team_circle = s.add_knot_constraint(CON_CIRCLE, 1, N, 3 * (agents - 1))
+        s.set_constraint_track(s.team_circle, np.zeros((1, 3 * (agents - 1))))
+    s.set_initial_state(x0)
+    s.set_trajectory(None, np.tile(np.array([0.1, 0.0]), (N, 1)) if U is None else np.asarray(U, dtype=np.float64))
+    return s
+
+
 THREE_OBSTACLE_CIRCLES = np.array([[0.25 * 3.0, 0.25 * 3.0, 0.425],
                                    [0.5 * 3.0, 0.5 * 3.0, 0.425],
                                    [0.75 * 3.0, 0.75 * 3.0, 0.425]])

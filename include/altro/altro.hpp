@@ -39,6 +39,7 @@
 #include "../altro_tracking.h"
 #include "../altro_knot_params.h"
 #include "../altro_multistart.h"
+#include "../altro_team.h"
 
 namespace altro {
 
@@ -1471,6 +1472,31 @@ class AugmentedLagrangianiLQR {
   }
   void GetBestStarts(int starts, double* X, double* U, altro_stats* stats = nullptr, int* winner = nullptr) {
     detail::Check(Handle(), altro_multistart_get_best(Handle(), starts, X, U, stats, winner), "altro_multistart_get_best");
+  }
+  // Teams (include/altro_team.h): the batch holds BatchSize() / agents teams of `agents` adjacent instances, and `index` is the
+  // team's knot circle constraint, AddKnotConstraint(ALTRO_CON_CIRCLE, k_begin, k_end, 3 * (agents - 1)).  A caller who writes
+  // the per-knot SetConstraint loop over the other vehicles' predictions calls these instead: the tracks are filled on the
+  // device from the plans it holds.  Thin calls of the C entry points, giving their bits; SolveTeam pulls trajectory and
+  // statistics like Solve().  Seeding (a first, uncoupled Solve() against a one-row track of radius 0) is the caller's job.
+  void FillTeamTracks(int agents, int index, const double* radius, bool radius_per_instance = false, int mode = ALTRO_TEAM_ALL,
+                      double blend = 1.0) {
+    ilqr_solver_.Push();
+    detail::Check(Handle(), altro_team_fill_tracks(Handle(), agents, index, radius, radius_per_instance ? 1 : 0, mode, blend),
+                  "altro_team_fill_tracks");
+  }
+  void TeamClearance(int agents, int index, const double* radius, bool radius_per_instance, double* clear) {
+    ilqr_solver_.Push();
+    detail::Check(Handle(), altro_team_clearance(Handle(), agents, index, radius, radius_per_instance ? 1 : 0, clear),
+                  "altro_team_clearance");
+  }
+  void SolveTeam(int agents, int index, const double* radius, bool radius_per_instance, int mode, double blend, int rounds) {
+    ilqr_solver_.Push();
+    ilqr_solver_.PrepareSolve();
+    detail::Check(Handle(), altro_team_solve(Handle(), agents, index, radius, radius_per_instance ? 1 : 0, mode, blend, rounds),
+                  "altro_team_solve");
+    ilqr_solver_.Pull(true, true);
+    status_ = ilqr_solver_.StatusAL();
+    ilqr_solver_.AfterSolve();
   }
   // The reference path of the tracking costs (include/altro_tracking.h): Xref [rows][n], Uref [rows][m] (null: zeros), or
   // [B][rows][.] with per_instance; knot k follows row min(offset + k, rows - 1), and AdvanceHorizon moves the offset along.
