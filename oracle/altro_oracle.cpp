@@ -375,6 +375,7 @@ struct SolverBase {
   virtual void GetDuals(double* out) = 0;
   virtual void SetDuals(const double* in) = 0;
   virtual void GetPenalties(double* out) = 0;
+  virtual void SetPenalties(const double* in) = 0;
   virtual void GetConVals(double* out) = 0;
   virtual void GetStats(altro_stats* s) = 0;
   virtual Stats& RawStats() = 0;
@@ -1455,6 +1456,9 @@ struct Instance final : SolverBase {
   void GetPenalties(double* out) override {
     ForRows([&](int r, Con& c, int i) { out[r] = (double)c.pen[i]; });
   }
+  void SetPenalties(const double* in) override {
+    ForRows([&](int r, Con& c, int i) { c.pen[i] = T(in[r]); });
+  }
   void GetConVals(double* out) override {
     ForRows([&](int r, Con& c, int i) { out[r] = (double)c.c[i]; });
   }
@@ -2130,6 +2134,10 @@ altro_status oracle_set_duals(oracle_handle h, const double* lam) {
 altro_status oracle_get_penalties(oracle_handle h, double* rho) {
   int rows = oracle_num_constraints(h);
   return ForAll(h, [&](SolverBase& s, int b) { s.GetPenalties(rho + (size_t)b * rows); });
+}
+altro_status oracle_set_penalties(oracle_handle h, const double* rho) {  // counterpart of oracle_set_duals (altro_set_penalties)
+  int rows = oracle_num_constraints(h);
+  return ForAll(h, [&](SolverBase& s, int b) { s.SetPenalties(rho + (size_t)b * rows); });
 }
 altro_status oracle_get_constraint_values(oracle_handle h, double* c) {
   int rows = oracle_num_constraints(h);

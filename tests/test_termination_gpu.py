@@ -29,6 +29,10 @@ Found by these tests and fixed with them (each of the give-up tests named fails 
 kCostIncrease (4) has no test: the reference sets J = J0 before it tests J > J0 (ilqr.hpp:549-557), so the status is
 unreachable.
 
+Every scenario here is built from ordinary costs and constraints.  A handle with a tracking cost or a knot constraint
+(Engine::KnotRouted) runs none of these kernels but the *_trk twins: tests/test_knot_termination_gpu.py takes the same exits
+there.
+
 Engine switches are read when a handle is created: the GPU tests set them before make().  Statuses, iteration counts, alpha
 and the regularisation are compared exactly; values go through the ledger (tests/_ledger.py) to bars of ~10x the measured
 maxima (profiles/r06_parity_errors.json), never below 1e-14 abs / 1e-13 norm-wise."""
