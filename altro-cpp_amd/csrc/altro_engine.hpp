@@ -68,7 +68,10 @@ struct Switches {
   OptInt loop_per_cu;              // ALTRO_HIP_LOOP_PER_CU: at most this many loop workgroups per CU
   int cand_front = 6;              // ALTRO_HIP_CAND_FRONT: line-search trials that own a candidate slot
   bool twin_debug = false;         // ALTRO_HIP_TWIN_DEBUG: mailbox dump of the twins
+  bool twin_debug_all = false;     // ALTRO_HIP_TWIN_DEBUG=all: every segment, every primary and every idle pool workgroup of a large launch too
   int twin_depth = kTwinDefaultDepth;  // ALTRO_HIP_TWIN_DEPTH=n: at most 2^n workers per rejection streak (1: one twin per primary)
+  int twin_min = tw_min_share(kTwinDefaultMin);  // ALTRO_HIP_TWIN_MIN=n: iterations both shares of a split must hold (>= kTwinMinFloor)
+  int twin_spread = kTwinDefaultSpread;  // ALTRO_HIP_TWIN_SPREAD=s: the pool treats segments within 2^s iterations left of each other as equals (0: the longest first, for all)
   int twin_misclaim = 0;           // ALTRO_HIP_TWIN_MISCLAIM=k (tests): every k-th claim assumes a regularisation one ulp off
   const char* sweep_log = nullptr; // ALTRO_HIP_SWEEP_LOG[=all]: timeline of the chains of sweeps
   bool loop_log = false;           // ALTRO_HIP_LOOP_LOG: phase log of the device-side loop
@@ -110,7 +113,10 @@ struct Switches {
     loop_per_cu = number("ALTRO_HIP_LOOP_PER_CU");
     if (const char* e = env("ALTRO_HIP_CAND_FRONT")) cand_front = std::max(0, std::min(kLineSearchLanes - 1, atoi(e)));
     twin_debug = env("ALTRO_HIP_TWIN_DEBUG") != nullptr;
+    twin_debug_all = Is(env("ALTRO_HIP_TWIN_DEBUG"), "all");
     if (const char* e = env("ALTRO_HIP_TWIN_DEPTH")) twin_depth = std::max(1, std::min(kTwinMaxDepth, atoi(e)));
+    if (const char* e = env("ALTRO_HIP_TWIN_MIN")) twin_min = tw_min_share(atoi(e));
+    if (const char* e = env("ALTRO_HIP_TWIN_SPREAD")) twin_spread = std::max(0, std::min(kTwinMaxSpread, atoi(e)));
     if (const char* e = env("ALTRO_HIP_TWIN_MISCLAIM")) twin_misclaim = std::max(0, atoi(e));
     sweep_log = env("ALTRO_HIP_SWEEP_LOG");
     loop_log = env("ALTRO_HIP_LOOP_LOG") != nullptr;
@@ -1714,7 +1720,11 @@ class Engine final : public EngineBase {
       if (sw_.twin && !sw_.fast_forward && !sw_.no_fused) {
         // (a solve that has split rejection streaks hands over at 3/2 of persist_at_, see Solve)
         // (at most 16384: the pool's scan packs a mailbox's position into 16 bits)
-        const int want = std::min({Bp_, 16384, ((persist_at_ * 3 / 2 + 8 + kBlock - 1) / kBlock) * kBlock});
+        // (at least a column per CU: a pool workgroup serves one claim and is gone, and with shares of 4 iterations the
+        //  streaks of a small batch use far more claims than the batch has instances -- batch 48 / 64 with obstacles ran its
+        //  pool of 64 dry half-way and walked its late streaks alone: 2.7 -> 5.9 ms warm; profiles/tail_endgame_experiments.txt)
+        const int per_cu = ((num_cus_ + kBlock - 1) / kBlock) * kBlock;
+        const int want = std::min({std::max(Bp_, per_cu), 16384, ((persist_at_ * 3 / 2 + 8 + kBlock - 1) / kBlock) * kBlock});
         // (only widen while the 32-bit byte offsets hold)
         if (ExpBytes((size_t)(Bp_ + want)) < (size_t)0xffffffffu) twin_cap_ = want;
       }
@@ -2766,9 +2776,13 @@ class Engine final : public EngineBase {
           hipMemsetAsync(d_twin_box_, 0, TwinBoxWords() * sizeof(unsigned long long), stream_);
         // the pool: a workgroup per primary, or -- a small batch -- what the device has CUs left for, one shadow column each.
         // (The variants that carry segments of the batched sweeps keep one twin per primary: their bookkeeping step is full.)
+        // (They also keep the former minimum share: their launch has a straggler for every CU, and a claimer's start-up --
+        //  a first iteration of 75 us -- is paid for with a CU another straggler waits for.  Config 3, alternating runs:
+        //  32.2 - 32.4 ms at 12 against 32.6 - 32.7 at 4, inside a spread of 0.8; profiles/tail_endgame_experiments.txt.)
+        const int min_share = any_split ? std::max(sw_.twin_min, kTwinSegMin) : sw_.twin_min;
         const int pool = std::min(twin_cap_, std::max(ninst, num_cus_ - ninst));
         tw = TwinCtl{d_twin_box_, d_twin_box_ + (size_t)2 * twin_cap_ * kTwWords, ninst, twin_cap_, Bp_ - twin_cap_, kTwinLag, sw_.twin_debug ? 1 : 0,
-                     pool, any_split ? 1 : sw_.twin_depth, sw_.twin_misclaim};
+                     pool, any_split ? 1 : sw_.twin_depth, min_share, sw_.twin_spread, sw_.twin_misclaim};
       }
       const dim3 g(ninst + (tw.base > 0 ? tw.npool : 0)), b3(kFwdWaves * kBlock), b4((kFwdWaves + 1) * kBlock);
       timing_.twin_workgroups = tw.base > 0 ? (int)g.x - ninst : 0;  // twin workgroups of this launch
@@ -2894,13 +2908,18 @@ class Engine final : public EngineBase {
       if (s >= twin_cap_ && w[kTwClaim] != 0) {
         hist[w[kTwHand] & 3]++;
         by_depth[std::min<unsigned long long>(w[kTwGen], kTwinMaxDepth + 1)]++;
-        const int limit = timing_.twin_claims <= 48 ? 1 : 8;  // (every segment of a small launch, every eighth otherwise)
+        const int limit = timing_.twin_claims <= 48 || sw_.twin_debug_all ? 1 : 8;  // (every segment of a small launch, every eighth otherwise)
         if ((shown++ % limit) == 0)
           fprintf(stderr, "  segment %4d depth %d inst %d from %d: it %d..%d hand %d | start %.0f go %.0f cloned %.0f first %.0f snap %.0f claimed %.0f "
                   "done %.0f (loops %llu) verdict %.0f handed %.0f commit %.0f\n", s, (int)w[kTwGen], (int)w[kTwInst] - 1, (int)w[kTwPred] - 1,
                   (int)(w[kTwClaim] >> 32), (int)w[kTwEnd], (int)(w[kTwHand] & 3), us(kTsTStart), us(kTsTGo), us(kTsTCloned), us(kTsTFirst), us(kTsPSnap),
                   us(kTsPClaim), us(kTsTDone), ts[kTsTLoops], us(kTsTVerdict), us(kTsPHand), us(kTsTCommit));
       }
+      if (sw_.twin_debug_all && s < twin_cap_ && ts[kTsPStart] != 0)
+        fprintf(stderr, "  primary %4d: start %.0f snap %.0f claimed %.0f handed %.0f end %.0f\n", s, us(kTsPStart), us(kTsPSnap), us(kTsPClaim),
+                us(kTsPHand), us(kTsPEnd));
+      if (sw_.twin_debug_all && s >= twin_cap_ && w[kTwClaim] == 0 && ts[kTsTIdleEnd] != 0)
+        fprintf(stderr, "  idle %4d: start %.0f left %.0f\n", s, us(kTsTStart), us(kTsTIdleEnd));
       if (w[kTwWhy] != 0) {
         why[w[kTwWhy] & 7]++;
         if (why[w[kTwWhy] & 7] <= 3)

@@ -3930,10 +3930,14 @@ ALTRO_DEV constexpr bool spec_has_wave4(int spec) { return spec == kSpecWave || 
 //   * an idle pool workgroup takes the published segment with the most iterations left and CLAIMS its second half
 //     [mid, seg_end): it becomes the publisher's successor and inherits the publisher's former successor; the publisher
 //     keeps [cur, mid) and may be claimed again, and so may the claimer (halves only; while both shares hold
-//     kTwinMinRemaining iterations; at most tw.depth splits along a line of claims, ALTRO_HIP_TWIN_DEPTH);
+//     tw.min_share iterations, ALTRO_HIP_TWIN_MIN; at most tw.depth splits along a line of claims, ALTRO_HIP_TWIN_DEPTH);
 //   * the claimer clones the publisher's column into its own, sets the entering state of iteration `mid` there (counters
 //     advanced, regularisation stepped through the increase / decrease rule, cost_prev = cost_cur) and runs the SAME code
-//     as every workgroup of this kernel on that column;
+//     as every workgroup of this kernel on that column.  Its clone is a publisher's column like any other the moment it
+//     is in memory: the claimer shows it -- the state its claim names IS the snapshot of its segment -- before its first
+//     iteration, so a streak is split down to the policy's floor in clone times (~10 us a level), not in iterations
+//     (tw_enter_clone; a first iteration that is not a rejection hides the snapshot again and refuses at its joint, like
+//     any streak that breaks);
 //   * a worker arriving at its segment's end -- a JOINT -- compares what it holds with what its successor assumed (bitwise:
 //     regularisation, counters, an unbroken streak since the snapshot).  Equal: it hands over and leaves (a pool workgroup
 //     only after its own predecessor has confirmed IT, so a confirmed joint means that every joint before it holds).
@@ -3968,10 +3972,14 @@ struct TwinCtl {
   int debug;                // stamp the mailbox (ALTRO_HIP_TWIN_DEBUG)
   int npool;                // pool workgroups of this launch (<= cap)
   int depth;                // a streak is split at most `depth` times along any line of claims: <= 2^depth workers (ALTRO_HIP_TWIN_DEPTH)
+  int min_share;            // iterations both shares of a split must hold (ALTRO_HIP_TWIN_MIN; tw_min_share() has clamped it)
+  int spread;               // the pool's scan takes segments whose iterations left agree above bit `spread` for equals, and every pool
+                            // workgroup orders equals its own way (ALTRO_HIP_TWIN_SPREAD; 0: strictly the most iterations left)
   int misclaim;             // test only (ALTRO_HIP_TWIN_MISCLAIM=k): every k-th claim assumes a regularisation one ulp off
 };
 enum TwinStamp { kTsPStart = 0, kTsPSnap = 1, kTsPClaim = 2, kTsPHand = 3, kTsPLoopsAtSnap = 4, kTsTStart = 5, kTsTGo = 6, kTsTCloned = 7,
-                 kTsTFirst = 8, kTsTDone = 9, kTsTVerdict = 10, kTsTCommit = 11, kTsTLoops = 12, kTsPEnd = 13 };
+                 kTsTFirst = 8, kTsTDone = 9, kTsTVerdict = 10, kTsTCommit = 11, kTsTLoops = 12, kTsPEnd = 13,
+                 kTsTIdleEnd = 14 /* a pool workgroup that leaves without a segment (with kTsTStart) */ };
 // One mailbox per WORKER (a primary or a pool workgroup).  Words 0 - 6 are what the worker shows as the publisher of its
 // segment, words 7 - 14 describe the joint at which it ENTERS the chain (pool workgroups only: written by the worker when
 // it claims, answered by its predecessor).
@@ -4011,7 +4019,43 @@ constexpr unsigned long long kTwsSnap = 1, kTwsClosed = 2, kTwsLocked = 4, kTwsF
 #endif
 constexpr int kTwinDefaultDepth = ALTRO_TWIN_DEPTH;  // workers per streak <= 2^depth (ALTRO_HIP_TWIN_DEPTH)
 constexpr int kTwinMaxDepth = 5;        // (the walk that cancels a chain is bounded by 2^kTwinMaxDepth workers)
-constexpr int kTwinMinRemaining = 12;   // iterations left in a streak below which a twin is not worth its start-up
+// The smallest share of a split: a segment is claimable while publisher and claimer both keep that many iterations
+// (TwinCtl::min_share; A/B builds -DALTRO_TWIN_MIN=n, per process ALTRO_HIP_TWIN_MIN).  Rounds 5 and 6 had 12, from the days
+// of one twin per primary; with segments that are claimed again the launch ended on ~130 segments of 14 - 17 iterations that
+// nobody was allowed to help while 100 CUs stood free.  Measured 12 / 8 / 6 / 4 / 3 on config 2: 4 and 3 are level and best,
+// 4 leaves the pool a margin (247 against 305 claims of 322 pool workgroups; profiles/tail_endgame_experiments.txt).
+#ifndef ALTRO_TWIN_MIN
+#define ALTRO_TWIN_MIN 4
+#endif
+constexpr int kTwinDefaultMin = ALTRO_TWIN_MIN;
+constexpr int kTwinSegMin = 12;  // the SEG variants' launches (config 3 after a split, depth 1) keep the former value: LaunchTail
+// What the protocol's timing needs of the value (none of it is needed for the result: a claim that comes too late is
+// refused at its joint and the publisher goes on alone).
+//  - A publisher requests its successor word at the top of an iteration and looks at it behind that iteration.  A claimer
+//    that read "enters iteration p next" may have done so just before the publisher finished p, and its claim may land just
+//    behind the request of p + 1: the publisher then sees it behind iteration p + 2, entering p + 3 -- so a claim must name
+//    an iteration at least kTwinSeeClaim = 3 ahead of the progress word it was derived from.  tw_keep(R, lag) >=
+//    min_share + 1 for every claimable R (R >= 2 min_share, lag >= 0): with the floor of 3 the joint is 4 or more ahead,
+//    one iteration to spare for the claimer's own ~2 us between reading the word and its compare-and-swap.
+//  - The lag (kTwinLag, one iteration) pays for the claimer's start-up -- 7 us of clone and a first iteration of 75 us
+//    instead of 40 --: at the floor a claimer's share (3 x 40 + 42 us) still ends with the publisher's (4 - 5 x 40 us), and a
+//    segment of 8 iterations (320 us alone) is done in ~200 us.  Below that the joint's hand-over and the commit's column
+//    copy (~10 us each) are no longer small against the share.
+// Which segment an idle pool workgroup goes for.  "The one with the most iterations left" is the same one for every idle
+// workgroup: one wins the lock, the others lose their look, and the pool takes segments one after the other (the full
+// mailbox dump of config 2: 30 - 60 workgroups waiting with a hundred claimable segments on display, 15 - 30 claims per
+// 100 us).  With spread s, segments whose iterations left agree in all bits above the lowest s are equals, and each
+// workgroup has its own order among equals: the late stragglers (twice the iterations of the crowd) still come first.
+#ifndef ALTRO_TWIN_SPREAD
+#define ALTRO_TWIN_SPREAD 3
+#endif
+constexpr int kTwinDefaultSpread = ALTRO_TWIN_SPREAD;
+constexpr int kTwinMaxSpread = 14;
+constexpr int kTwinSeeClaim = 3;
+constexpr int kTwinMinFloor = 3;
+constexpr int kTwinMinCeil = 1 << 14;  // (twice the value fits the scan's 15 bits of "iterations left")
+ALTRO_HD int tw_min_share(int asked) { return asked < kTwinMinFloor ? kTwinMinFloor : (asked > kTwinMinCeil ? kTwinMinCeil : asked); }
+static_assert(kTwinMinFloor + 1 > kTwinSeeClaim, "tw_keep() of the smallest claimable segment must let the publisher see the claim");
 // iterations of the primary's share that pay for the twin's start-up (claim seen, clone, one unspeculated iteration): the twin
 // takes the iterations from snapshot + (R + lag) / 2 + 1 on.  Round 6 (mailbox stamps of config 2, ALTRO_HIP_TWIN_DEBUG): with 3
 // the twins finished 15 - 140 us before their primaries handed over; with 1 the two sides end together (persistent launch 2.42 -
@@ -4048,9 +4092,10 @@ ALTRO_DEV int tw_remaining(const DevOpts& o, unsigned long long prog, int end_in
   return r1 < r2 ? r1 : r2;
 }
 // iterations the publisher keeps of the R it has left (halves, plus what pays for the claimer's start-up: kTwinLag); a
-// segment is worth splitting while both shares hold kTwinMinRemaining iterations
-ALTRO_DEV int tw_keep(int R, int lag) { return (R + lag) / 2 + 1; }
-ALTRO_DEV bool tw_claimable(int R, int lag) { return R >= 2 * kTwinMinRemaining && R - tw_keep(R, lag) >= kTwinMinRemaining; }
+// segment is worth splitting while both shares hold min_share iterations (TwinCtl::min_share).  Host-callable for
+// tests/test_tail_endgame_policy.py (altro_twin_policy); inlined into the kernels as before.
+ALTRO_HD int tw_keep(int R, int lag) { return (R + lag) / 2 + 1; }
+ALTRO_HD bool tw_claimable(int R, int lag, int min_share) { return R >= 2 * min_share && R - tw_keep(R, lag) >= min_share; }
 // A worker that refuses its successor, gives its own claim up or finishes the instance with a successor waiting: no further
 // claim on it (kTwFrozen), and every worker down the chain is told that its work is void.  Bounded; thread 0 only.
 ALTRO_DEV void tw_cancel_chain(const TwinCtl& tw, unsigned long long* box) {
@@ -4125,11 +4170,13 @@ ALTRO_DEV void fused_report(const TailCtx<T>& C, int b_real, const int* sync_wor
 
 // ---- pool workgroups: find work.  Wave 0 scans the mailboxes for the published segment with the most iterations left
 //      (late stragglers first, once CUs free up) and lane 0 tries to claim its second half. ----
-// One look at every mailbox -- the primaries', then the pool's.  Returns the wave's best candidate as (iterations left << 16 |
-// 0xffff - position in the scan), 0 for none; *waiting_out: workers that may still offer something -- alive (or not yet
-// dispatched), not full, long enough.
-ALTRO_DEV int tw_scan(const TwinCtl& tw, const DevOpts& o, int nsl, int nall, int self, int lane, int* waiting_out) {
-  int waiting = 0, key = 0;
+// One look at every mailbox -- the primaries', then the pool's.  Returns the wave's best candidate as ((iterations left >>
+// tw.spread) + 1) << 32 | this workgroup's own order among equals << 16 | position in the scan), 0 for none; *waiting_out:
+// workers that may still offer something -- alive (or not yet dispatched), not full, long enough by tw_claimable() with the
+// launch's min_share: the rule of tw_try_claim, so the pool (tw_find_work) stays exactly as long as a claim can still succeed.
+ALTRO_DEV unsigned long long tw_scan(const TwinCtl& tw, const DevOpts& o, int nsl, int nall, int self, int lane, int* waiting_out) {
+  int waiting = 0;
+  unsigned long long key = 0;
   for (int v0 = 0; v0 < nall; v0 += kBlock) {
     const int v = v0 + lane;
     bool open = false;
@@ -4140,9 +4187,13 @@ ALTRO_DEV int tw_scan(const TwinCtl& tw, const DevOpts& o, int nsl, int nall, in
       if (open && (st & kTwsSnap) != 0) {
         const unsigned long long* bx = tw.box + (size_t)id * kTwWords;
         const int R = tw_remaining(o, tw_load(bx + kTwProg), (int)tw_load(bx + kTwEnd));
-        open = tw_claimable(R, tw.lag);
+        open = tw_claimable(R, tw.lag, tw.min_share);
         if (open && (st & kTwsLocked) == 0) {
-          const int k2 = ((R < 0x7fff ? R : 0x7fff) << 16) | (0xffff - (v & 0xffff));
+          // (segments that are equals under tw.spread: each pool workgroup has an order of its own among them, so that
+          //  the idle ones do not all go for the same segment and lose against one winner, look after look)
+          const unsigned mix = tw.spread > 0 ? (((unsigned)v * 0x9E3779B1u) ^ ((unsigned)self * 0x85EBCA6Bu)) >> 16 : 0xffffu - (unsigned)v;
+          const unsigned long long k2 = ((unsigned long long)(((R < 0x7fff ? R : 0x7fff) >> tw.spread) + 1) << 32) |
+                                        ((unsigned long long)(mix & 0xffffu) << 16) | (unsigned long long)(v & 0xffff);
           key = k2 > key ? k2 : key;
         }
       }
@@ -4150,7 +4201,7 @@ ALTRO_DEV int tw_scan(const TwinCtl& tw, const DevOpts& o, int nsl, int nall, in
     waiting += __popcll(__ballot(open));
   }
   for (int d = 32; d > 0; d >>= 1) {
-    const int other = __shfl_xor(key, d);
+    const unsigned long long other = __shfl_xor(key, d);
     key = other > key ? other : key;
   }
   *waiting_out = waiting;
@@ -4182,7 +4233,7 @@ ALTRO_DEV int tw_try_claim(const TailCtx<T>& C, int v, int nsl, int self) {
     const int in0 = (int)(c0 >> 32), tot0 = (int)(c0 & 0xffffffffull), in1 = (int)(pr >> 32), tot1 = (int)(pr & 0xffffffffull);
     const int R = tw_remaining(o, pr, end_in);
     if (gen >= tw.depth) more = kTwsFull;
-    if (stable && more == 0 && (so & kTwFrozen) == 0 && inst != 0 && in1 >= in0 && in1 - in0 == tot1 - tot0 && tw_claimable(R, tw.lag)) {
+    if (stable && more == 0 && (so & kTwFrozen) == 0 && inst != 0 && in1 >= in0 && in1 - in0 == tot1 - tot0 && tw_claimable(R, tw.lag, tw.min_share)) {
       const int ahead = tw_keep(R, tw.lag);  // iterations the publisher keeps, counted from where it is
       // the regularisation entering iteration `start`: every iteration since the snapshot runs its backward pass
       // (DecreaseRegularization, ilqr.hpp:440) and rejects its line search (IncreaseRegularization, :550)
@@ -4237,9 +4288,9 @@ ALTRO_DEV void tw_find_work(const TailCtx<T>& C, int self, int lane) {
   int chosen = -1;
   for (int tries = 0; tries < kTwinIdlePolls && chosen < 0; ++tries) {
     int waiting = 0;
-    const int key = tw_scan(tw, C.o, nsl, nall, self, lane, &waiting);
+    const unsigned long long key = tw_scan(tw, C.o, nsl, nall, self, lane, &waiting);
     int got = 0;
-    if (key != 0 && lane == 0) got = tw_try_claim(C, 0xffff - (key & 0xffff), nsl, self);
+    if (key != 0 && lane == 0) got = tw_try_claim(C, (int)(key & 0xffffull), nsl, self);
     got = __shfl(got, 0);
     if (got > 0) chosen = got - 1;
     if (chosen < 0) {
@@ -4254,6 +4305,26 @@ ALTRO_DEV void tw_find_work(const TailCtx<T>& C, int self, int lane) {
     //  multipliers, or its clone of them -- may sit in another XCD's L2: its release is matched by this acquire)
     if (chosen >= 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
+}
+// Thread 0 of a worker: the snapshot of its streak goes on display -- once per streak: the counters `cnt` and the
+// regularisation ENTERING the worker's next iteration, which a claimer steps the rule from.  Whatever this workgroup has
+// stored in its column (the trajectory of the last accepted step, the multipliers, cost_prev = cost_cur; a pool workgroup:
+// its clone of them) leaves this XCD's L2 before a claimer is told that it may read it.
+ALTRO_DEV void tw_show(const TwinCtl& tw, TwinWorker& w, unsigned long long cnt, double rho, double drho, int b_real, int loops) {
+  ++w.ver;
+  unsigned long long* buf = w.box + kTwSnap + 3 * (w.ver & 1);
+  tw_store(buf, cnt);
+  tw_store(buf + 1, tw_bits(rho));
+  tw_store(buf + 2, tw_bits(drho));
+  tw_store(w.box + kTwInst, (unsigned long long)(unsigned)(b_real + 1));
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  tw_order();
+  tw_store(w.box + kTwSeq, w.ver);
+  tw_order();
+  __hip_atomic_fetch_or(tw.state + w.slot, kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  w.shown = true;
+  w.stamp(tw, kTsPSnap);
+  w.stamp(tw, kTsPLoopsAtSnap, loops);
 }
 // ---- pool workgroup with a claim: clone the instance into the shadow column and enter the state the claim names ----
 // All threads, behind the barrier that publishes tw_find_work's words.  Returns false if the workgroup has nothing to do: no
@@ -4300,6 +4371,22 @@ ALTRO_DEV bool tw_enter_clone(const TailCtx<T>& C, TwinWorker& w, int tslot, lon
   if (tid == 0) {  // (refused already -- the publisher broke its streak or finished)
     ff[kFfClaimOpen] = tw_load(w.box + kTwHand) == 0 ? 1.0 : 0.0;
     if (ff[kFfClaimOpen] == 0.0) w.close(tw);
+    // THE CLONE IS A PUBLISHER'S COLUMN: counters and regularisation entering this worker's first iteration are what its
+    // claim says, its column is in memory (the barrier above), its segment's end and successor stand in its mailbox (the
+    // claim wrote them).  So it shows its segment now instead of two rejected iterations (~150 us) from now, and the next
+    // level of the split starts a clone later.  Nobody has checked the claim's assumption yet -- nor has anybody when a
+    // streak is published the usual way by an unconfirmed worker: whoever claims from here stands behind this worker in
+    // the chain, and the joint that refuses this worker cancels them with it (tw_cancel_chain).  The meaning of the
+    // worker's words holds for a snapshot older than its first iteration: ver counts snapshots (this is the first),
+    // break_total is still -1 < the snapshot's it_total, so a claim derived from it passes the joint exactly if no
+    // iteration from the first on was anything but a rejection; `shown` makes tw_publish keep the progress word current
+    // from the first iteration on and hide the snapshot if that iteration breaks the streak.
+    // (its own successor word: nobody else writes it before the snapshot is on display)
+    else if ((int)((tw_load(w.box + kTwSucc) >> 16) & 0xffffull) < tw.depth) {
+      const unsigned long long cnt = ((unsigned long long)(unsigned)(int)ff[kFfClaimItInner] << 32) | (unsigned long long)(unsigned)(int)ff[kFfClaimItTotal];
+      tw_store(w.box + kTwProg, cnt);
+      tw_show(tw, w, cnt, ff[kFfClaimRho], ff[kFfClaimDrho], *b_real, 0);
+    }
   }
   __syncthreads();
   return ff[kFfClaimOpen] != 0.0;
@@ -4416,28 +4503,11 @@ ALTRO_DEV void tw_publish(const TailCtx<T>& C, TwinWorker& w, bool rc, int it_in
   const TwinCtl& tw = C.tw;
   const double* ff = C.ff;
   // (a column whose streak the batched sweeps have split into segments ends at its segment's end: not claimable)
-  if (rc && w.streak >= 2 && !w.full && (!SEG || !C.A.seg_end || C.A.seg_next[b] < 0)) {
+  // (w.shown below two rejections: a pool workgroup that showed its clone, tw_enter_clone)
+  if (rc && (w.streak >= 2 || w.shown) && !w.full && (!SEG || !C.A.seg_end || C.A.seg_next[b] < 0)) {
     const unsigned long long cnt = ((unsigned long long)(unsigned)it_in << 32) | (unsigned long long)(unsigned)it_tot;
     tw_store(w.box + kTwProg, cnt);  // (all an iteration of a published streak costs: one relaxed store, nothing waited for)
-    if (!w.shown) {
-      // once per streak: the state a claimer steps the regularisation rule from
-      ++w.ver;
-      unsigned long long* buf = w.box + kTwSnap + 3 * (w.ver & 1);
-      tw_store(buf, cnt);
-      tw_store(buf + 1, tw_bits(ff[kFfRho]));
-      tw_store(buf + 2, tw_bits(ff[kFfDrho]));
-      tw_store(w.box + kTwInst, (unsigned long long)(unsigned)(b_real + 1));
-      // whatever the last accepted step and the first rejected iteration stored (trajectory, multipliers, cost_prev =
-      // cost_cur; a pool workgroup: its clone of them) leaves this XCD's L2 before a claimer is told that it may read it
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      tw_order();
-      tw_store(w.box + kTwSeq, w.ver);
-      tw_order();
-      __hip_atomic_fetch_or(tw.state + w.slot, kTwsSnap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      w.shown = true;
-      w.stamp(tw, kTsPSnap);
-      w.stamp(tw, kTsPLoopsAtSnap, loops);
-    }
+    if (!w.shown) tw_show(tw, w, cnt, ff[kFfRho], ff[kFfDrho], b_real, loops);  // once per streak
   }
   // (a streak that broke: the snapshot on display describes a state that no longer exists -- a late claimer would
   //  claim on it and be refused; hide it until the next streak publishes)
@@ -4685,7 +4755,14 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   if (w.is_twin) {
     if (wave == 0) tw_find_work(C, tw.cap + tslot, lane);
     __syncthreads();
-    if (!tw_enter_clone<T, M, SEG>(C, w, tslot, tstart_clock, kThreads, &b, &b_real)) return;
+    if (!tw_enter_clone<T, M, SEG>(C, w, tslot, tstart_clock, kThreads, &b, &b_real)) {
+      if (tid == 0 && tw.debug) {  // (how long the pool held a CU for nothing: the mailbox dump's idle lines)
+        unsigned long long* own = tw.box + (size_t)(tw.cap + tslot) * kTwWords + kTwStamp;
+        tw_store(own + kTsTStart, (unsigned long long)tstart_clock);
+        tw_store(own + kTsTIdleEnd, (unsigned long long)wall_clock64());
+      }
+      return;
+    }
   }
   if (wave == 2 && lane == 0) {  // LDS mirrors of initial_cost / need_init_cost (read by this same lane: forward2_body)
     S.ff[kFfInitCost] = A.initial_cost[b];
@@ -4694,8 +4771,9 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
   for (;;) {
     const long long st_it = ALTRO_STAMP_T0();
     // (a claim on this worker's segment: the word is requested here and looked at in the bookkeeping step behind the forward
-    //  pass, so its round trip through the memory side runs beside the iteration -- a claim is seen one iteration late at the
-    //  worst, and it names an iteration at least kTwinMinRemaining ahead)
+    //  pass, so its round trip through the memory side runs beside the iteration -- a claim is seen entering the third
+    //  iteration behind the progress word it was derived from at the worst (kTwinSeeClaim), and it names an iteration at
+    //  least tw.min_share + 1 >= kTwinMinFloor + 1 = 4 ahead of that word)
     if (w.box && tid == 0 && !w.closed && !w.full && (w.is_twin || w.shown)) w.peek = tw_load(w.box + kTwSucc);
     // ---- S: X, U, lambda, rho, parameters -> LDS (all threads).  Only once: phases 2 and 3 of the
     //      forward pass keep the LDS copies current from then on ----

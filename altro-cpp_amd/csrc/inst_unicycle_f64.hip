@@ -3,3 +3,14 @@
 namespace altro_hip {
 EngineBase* MakeEngineUnicycleF64(const altro_desc& d, std::string* err) { return MakeEngineImpl<double, UnicycleM>(d, err); }
 }  // namespace altro_hip
+
+// The split policy of the persistent tail as the kernels inline it (TwinCtl, altro_kernels.hpp), on the host, for
+// tests/test_tail_endgame_policy.py (here because this translation unit sees the kernels' header; in no public header: not
+// part of the interface).  Returns the minimum share in use for `asked_min`.
+extern "C" int altro_twin_policy(int R, int lag, int asked_min, int* keep, int* claimable, int* see_claim) {
+  const int min_share = altro_hip::tw_min_share(asked_min);
+  if (keep) *keep = altro_hip::tw_keep(R, lag);
+  if (claimable) *claimable = altro_hip::tw_claimable(R, lag, min_share) ? 1 : 0;
+  if (see_claim) *see_claim = altro_hip::kTwinSeeClaim;
+  return min_share;
+}
