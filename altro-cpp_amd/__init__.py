@@ -616,20 +616,25 @@ class BatchSolver:
         """mpc_advance with fp64 arrays [B][n] in memory of this handle's device (either pointer may be 0)."""
         self._call("mpc_advance_device", C.c_int(shift), C.c_void_p(x0_ptr or None), C.c_void_p(w_ptr or None))
 
+    def _run_logs(self, cycles, shift, w, per_knot=False):
+        """What every mpc_run* shares: the checked disturbance ([cycles][B][n], per_knot [cycles][B][shift][n]), the dict of the
+        logs the C call fills, and their four pointers in the order of the C signatures."""
+        w = _f64(w)
+        shape = (cycles, self.batch, shift, self.n) if per_knot else (cycles, self.batch, self.n)
+        if w is not None and w.shape != shape:
+            raise ValueError("w must have shape (" + ", ".join(str(v) for v in shape) + ")")
+        L = max(cycles, 0) * max(shift, 0)
+        out = dict(X_cl=np.zeros((self.batch, L + 1, self.n)), U_cl=np.zeros((self.batch, L, self.m)),
+                   iterations=np.zeros((self.batch, max(cycles, 0)), dtype=np.int32),
+                   status=np.zeros((self.batch, max(cycles, 0)), dtype=np.int32))
+        return w, out, (_dp(out["X_cl"]), _dp(out["U_cl"]), self._ip(out["iterations"]), self._ip(out["status"]))
+
     def mpc_run(self, cycles, shift, w=None):
         """``cycles`` x (solve; mpc_advance(shift, w=w[c])) with the closed-loop log kept on the device.  Returns
         dict(X_cl [B][cycles*shift+1][n], U_cl [B][cycles*shift][m], iterations [B][cycles], status [B][cycles])."""
-        w = _f64(w)
-        if w is not None and w.shape != (cycles, self.batch, self.n):
-            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {self.n})")
-        L = max(cycles, 0) * max(shift, 0)
-        X = np.zeros((self.batch, L + 1, self.n))
-        U = np.zeros((self.batch, L, self.m))
-        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
-        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
-        self._call("mpc_run", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(X), _dp(U),
-                   it.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int)))
-        return dict(X_cl=X, U_cl=U, iterations=it, status=st)
+        w, out, logs = self._run_logs(cycles, shift, w)
+        self._call("mpc_run", C.c_int(cycles), C.c_int(shift), _dp(w), *logs)
+        return out
 
     def _track_bounds(self, u_lo, u_hi):
         u_lo, u_hi = _f64(u_lo), _f64(u_hi)
@@ -666,20 +671,12 @@ class BatchSolver:
         """``cycles`` x (solve; mpc_track(shift, 1, w=w[c]); mpc_advance(shift, x0=the tracked state)) with the log kept on
         the device; w [cycles][B][shift][n].  Returns dict(X_cl [B][cycles*shift+1][n], U_cl [B][cycles*shift][m] -- the
         TRACKED states and controls --, iterations [B][cycles], status [B][cycles], track [B][cycles] of TRACK_STATS_DTYPE)."""
-        w = _f64(w)
         u_lo, u_hi = self._track_bounds(u_lo, u_hi)
-        if w is not None and w.shape != (cycles, self.batch, shift, self.n):
-            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {shift}, {self.n})")
-        L = max(cycles, 0) * max(shift, 0)
-        X = np.zeros((self.batch, L + 1, self.n))
-        U = np.zeros((self.batch, L, self.m))
-        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
-        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
-        track = np.zeros((self.batch, max(cycles, 0)), dtype=TRACK_STATS_DTYPE)
-        self._call("mpc_run_tracked", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(u_lo), _dp(u_hi), _dp(X), _dp(U),
-                   it.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int)),
-                   track.ctypes.data_as(C.POINTER(TrackStats)))
-        return dict(X_cl=X, U_cl=U, iterations=it, status=st, track=track)
+        w, out, logs = self._run_logs(cycles, shift, w, per_knot=True)
+        out["track"] = np.zeros((self.batch, max(cycles, 0)), dtype=TRACK_STATS_DTYPE)
+        self._call("mpc_run_tracked", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(u_lo), _dp(u_hi), *logs,
+                   out["track"].ctypes.data_as(C.POINTER(TrackStats)))
+        return out
 
     def get_initial_state(self):
         """What the next solve starts from, [B][n]."""
@@ -757,19 +754,13 @@ class BatchSolver:
         """``cycles`` x (solve; multistart_spread; mpc_advance(shift, w=w[c]); multistart_perturb(dU) unless it is None) with
         nothing crossing to the host inside the loop.  Returns dict(X_cl, U_cl, iterations, status as mpc_run gives them,
         per instance, and winner [P][cycles])."""
-        w = _f64(w)
-        if w is not None and w.shape != (cycles, self.batch, self.n):
-            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {self.n})")
+        w, out, logs = self._run_logs(cycles, shift, w)
         dU, per_instance = self._perturbation(starts, dU)
-        L = max(cycles, 0) * max(shift, 0)
-        X = np.zeros((self.batch, L + 1, self.n))
-        U = np.zeros((self.batch, L, self.m))
-        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
-        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
         win = np.zeros((max(self._problems(starts), 1), max(cycles, 1)), dtype=np.int32)
         self._call("mpc_run_multistart", C.c_int(starts), C.c_int(cycles), C.c_int(shift), _dp(w), _dp(dU), C.c_int(per_instance),
-                   _dp(X), _dp(U), self._ip(it), self._ip(st), self._ip(win))
-        return dict(X_cl=X, U_cl=U, iterations=it, status=st, winner=win[:self._problems(starts), :max(cycles, 0)])
+                   *logs, self._ip(win))
+        out["winner"] = win[:self._problems(starts), :max(cycles, 0)]
+        return out
 
     # -- teams (include/altro_team.h) ---------------------------------------------------------------
     # A handle of batch = T * agents instances holds T teams; agent a of team t is instance t * agents + a.  ``index`` is the
@@ -815,18 +806,12 @@ class BatchSolver:
         crossing to the host inside the loop.  Returns dict(X_cl, U_cl, iterations, status as mpc_run gives them, and
         clear [T][cycles])."""
         radius, per = self._team_radius(agents, radius)
-        w = _f64(w)
-        if w is not None and w.shape != (cycles, self.batch, self.n):
-            raise ValueError(f"w must have shape ({cycles}, {self.batch}, {self.n})")
-        L = max(cycles, 0) * max(shift, 0)
-        X = np.zeros((self.batch, L + 1, self.n))
-        U = np.zeros((self.batch, L, self.m))
-        it = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
-        st = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        w, out, logs = self._run_logs(cycles, shift, w)
         clear = np.zeros((max(self._teams(agents), 1), max(cycles, 1)))
         self._call("mpc_run_team", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_int(mode), C.c_double(blend),
-                   C.c_int(rounds), C.c_int(cycles), C.c_int(shift), _dp(w), _dp(X), _dp(U), self._ip(it), self._ip(st), _dp(clear))
-        return dict(X_cl=X, U_cl=U, iterations=it, status=st, clear=clear[:self._teams(agents), :max(cycles, 0)])
+                   C.c_int(rounds), C.c_int(cycles), C.c_int(shift), _dp(w), *logs, _dp(clear))
+        out["clear"] = clear[:self._teams(agents), :max(cycles, 0)]
+        return out
 
     # -- device interop ---------------------------------------------------------------------------
     def pack_results_device(self, device_ptr):

@@ -1216,15 +1216,17 @@ altro_status MpcRowMapOf(altro_handle h, int shift, std::vector<int>* out) {
   *out = MpcRowMap(h->spec.desc.N, shift, kb, ke, p, eq);
   return ALTRO_OK;
 }
+// the penalty of a row that starts afresh behind an advance
+double ResetPenalty(altro_handle h) { return h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0; }
+// behind an advance the initial state lives on the device alone (altro_get_initial_state reads it): the recorded one is out of date
+void ForgetX0(altro_handle h) {
+  h->spec.x0.clear();
+  h->spec.x0_per_instance = 0;
+}
 // the advance behind both entry points; x0 is [B][n] here
 altro_status MpcAdvanceImpl(altro_handle h, int shift, const double* x0, const double* w, int on_device) {
-  const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
-  const altro_status st = Forward(h, [&](EngineBase& e) { return e.MpcAdvance(shift, x0, w, on_device, pen); });
-  if (st == ALTRO_OK) {
-    // the initial state now lives on the device alone (altro_get_initial_state reads it): the recorded one is out of date
-    h->spec.x0.clear();
-    h->spec.x0_per_instance = 0;
-  }
+  const altro_status st = Forward(h, [&](EngineBase& e) { return e.MpcAdvance(shift, x0, w, on_device, ResetPenalty(h)); });
+  if (st == ALTRO_OK) ForgetX0(h);
   return st;
 }
 
@@ -1279,6 +1281,51 @@ altro_status MpcTrackImpl(altro_handle h, int steps, int samples, const double* 
   return Forward(h, [&](EngineBase& e) { return e.MpcTrack(g, on_device); });
 }
 
+// One closed-loop run, the skeleton of every altro_mpc_run*: the checks every kind shares, LoopBegin, `cycles` x (solve;
+// LoopCycle; forget the recorded x0), and LoopEnd -- also after a failure, it frees the run's device blocks -- with the FIRST
+// error's text kept.  The entry points check their own arguments first and bring what differs: the LoopSpec, the cycle's
+// solve (altro_solve_al; the team's rounds) and where the logs go.  h is not null and not busy here.
+template <class Solve>
+altro_status RunClosedLoop(altro_handle h, const char* who, const LoopSpec& spec, Solve solve, const LoopOut& out) {
+  if (spec.cycles < 1) {
+    h->err = std::string(who) + ": at least one cycle";
+    return ALTRO_INVALID_ARG;
+  }
+  altro_status st = MpcCheck(h, spec.shift, who);
+  if (st != ALTRO_OK) return st;
+  // (a team run writes the track of its knot constraint itself, in its first fill)
+  if (spec.kind != kLoopTeam && ReferenceMissing(h)) return ALTRO_NOT_READY;
+  st = Forward(h, [&](EngineBase& e) { return e.LoopBegin(spec); });
+  for (int c = 0; c < spec.cycles && st == ALTRO_OK; ++c) {
+    st = solve();
+    if (st != ALTRO_OK) break;
+    const LoopStep step{ResetPenalty(h), h->ilqr_mode, TrackOpts(h)};
+    st = Forward(h, [&](EngineBase& e) { return e.LoopCycle(step); });
+    if (st == ALTRO_OK) ForgetX0(h);
+  }
+  if (h->uploaded) {
+    const std::string err = h->err;
+    const altro_status es = h->engine->LoopEnd(out);
+    if (st == ALTRO_OK && es != ALTRO_OK) {
+      h->err = h->engine->LastError();
+      st = es;
+    } else {
+      h->err = err;
+    }
+  }
+  return st;
+}
+// w: [cycles][B][n] -- or [cycles][B][shift][n] under tracking
+LoopSpec MakeLoopSpec(altro_handle h, LoopKind kind, int cycles, int shift, const double* w) {
+  LoopSpec s{};
+  s.kind = kind;
+  s.cycles = cycles;
+  s.shift = shift;
+  s.w = w;
+  s.w_stride = (size_t)h->spec.desc.batch * (size_t)h->spec.desc.n * (kind == kLoopTracked ? (size_t)std::max(shift, 0) : 1);
+  return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1325,30 +1372,8 @@ altro_status altro_mpc_run(altro_handle h, int cycles, int shift, const double* 
                            int* status) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  if (cycles < 1) {
-    h->err = "altro_mpc_run: at least one cycle";
-    return ALTRO_INVALID_ARG;
-  }
-  altro_status st = MpcCheck(h, shift, "altro_mpc_run");
-  if (st != ALTRO_OK) return st;
-  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
-  st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
-  const size_t per_cycle = (size_t)h->spec.desc.batch * h->spec.desc.n;
-  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
-    st = altro_solve_al(h);
-    if (st == ALTRO_OK) st = MpcAdvanceImpl(h, shift, nullptr, w ? w + (size_t)c * per_cycle : nullptr, 0);
-  }
-  if (h->uploaded) {
-    const std::string err = h->err;
-    const altro_status es = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);  // (also after a failure: it frees the log)
-    if (st == ALTRO_OK && es != ALTRO_OK) {
-      h->err = h->engine->LastError();
-      st = es;
-    } else {
-      h->err = err;
-    }
-  }
-  return st;
+  return RunClosedLoop(h, "altro_mpc_run", MakeLoopSpec(h, kLoopPlain, cycles, shift, w), [&] { return altro_solve_al(h); },
+                       LoopOut{X_cl, U_cl, iterations, status, nullptr, nullptr, nullptr});
 }
 altro_status altro_mpc_track(altro_handle h, int steps, int samples, const double* dx0, const double* w, const double* u_lo,
                              const double* u_hi, double* X_cl, double* U_cl, altro_track_stats* stats) {
@@ -1365,7 +1390,7 @@ altro_status altro_mpc_run_tracked(altro_handle h, int cycles, int shift, const 
                                    double* X_cl, double* U_cl, int* iterations, int* status, altro_track_stats* track) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  if (cycles < 1) {
+  if (cycles < 1) {  // (the driver's check, ahead of the bounds: a call with both wrong has always heard of the cycles)
     h->err = "altro_mpc_run_tracked: at least one cycle";
     return ALTRO_INVALID_ARG;
   }
@@ -1373,32 +1398,11 @@ altro_status altro_mpc_run_tracked(altro_handle h, int cycles, int shift, const 
     h->err = "altro_mpc_run_tracked: u_lo and u_hi come together (both or neither)";
     return ALTRO_INVALID_ARG;
   }
-  altro_status st = MpcCheck(h, shift, "altro_mpc_run_tracked");
-  if (st != ALTRO_OK) return st;
-  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
-  st = Forward(h, [&](EngineBase& e) { return e.MpcTrackedBegin(cycles, shift, u_lo, u_hi); });
-  const size_t per_cycle = (size_t)h->spec.desc.batch * (size_t)shift * (size_t)h->spec.desc.n;
-  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
-    st = altro_solve_al(h);
-    if (st != ALTRO_OK) break;
-    const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
-    st = Forward(h, [&](EngineBase& e) { return e.MpcTrackedCycle(w ? w + (size_t)c * per_cycle : nullptr, TrackOpts(h), pen); });
-    if (st == ALTRO_OK) {  // (as behind altro_mpc_advance: the initial state now lives on the device alone)
-      h->spec.x0.clear();
-      h->spec.x0_per_instance = 0;
-    }
-  }
-  if (h->uploaded) {
-    const std::string err = h->err;
-    const altro_status es = h->engine->MpcTrackedEnd(X_cl, U_cl, iterations, status, reinterpret_cast<TrackStats*>(track));
-    if (st == ALTRO_OK && es != ALTRO_OK) {
-      h->err = h->engine->LastError();
-      st = es;
-    } else {
-      h->err = err;
-    }
-  }
-  return st;
+  LoopSpec spec = MakeLoopSpec(h, kLoopTracked, cycles, shift, w);
+  spec.u_lo = u_lo;
+  spec.u_hi = u_hi;
+  return RunClosedLoop(h, "altro_mpc_run_tracked", spec, [&] { return altro_solve_al(h); },
+                       LoopOut{X_cl, U_cl, iterations, status, nullptr, nullptr, reinterpret_cast<TrackStats*>(track)});
 }
 altro_status altro_get_initial_state(altro_handle h, double* x0) {
   if (!x0) return ALTRO_INVALID_ARG;
@@ -1498,38 +1502,12 @@ altro_status altro_mpc_run_multistart(altro_handle h, int starts, int cycles, in
                                       int dU_per_instance, double* X_cl, double* U_cl, int* iterations, int* status, int* winner) {
   altro_status st = MsCheck(h, starts, false, "altro_mpc_run_multistart");
   if (st != ALTRO_OK) return st;
-  if (cycles < 1) {
-    h->err = "altro_mpc_run_multistart: at least one cycle";
-    return ALTRO_INVALID_ARG;
-  }
-  st = MpcCheck(h, shift, "altro_mpc_run_multistart");
-  if (st != ALTRO_OK) return st;
-  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
-  st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
-  if (st == ALTRO_OK) st = Forward(h, [&](EngineBase& e) { return e.MsRunBegin(starts, cycles, w, dU, dU_per_instance); });
-  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
-    st = altro_solve_al(h);
-    if (st != ALTRO_OK) break;
-    const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
-    st = Forward(h, [&](EngineBase& e) { return e.MsRunCycle(shift, pen, h->ilqr_mode); });
-    if (st == ALTRO_OK) {  // (as behind altro_mpc_advance: the initial state now lives on the device alone)
-      h->spec.x0.clear();
-      h->spec.x0_per_instance = 0;
-    }
-  }
-  if (h->uploaded) {
-    const std::string err = h->err;
-    altro_status es = h->engine->MsRunEnd(winner);  // (also after a failure: both free their device blocks)
-    const altro_status el = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);
-    if (es == ALTRO_OK) es = el;
-    if (st == ALTRO_OK && es != ALTRO_OK) {
-      h->err = h->engine->LastError();
-      st = es;
-    } else {
-      h->err = err;
-    }
-  }
-  return st;
+  LoopSpec spec = MakeLoopSpec(h, kLoopMultiStart, cycles, shift, w);
+  spec.G = starts;
+  spec.dU = dU;
+  spec.dU_per_instance = dU_per_instance;
+  return RunClosedLoop(h, "altro_mpc_run_multistart", spec, [&] { return altro_solve_al(h); },
+                       LoopOut{X_cl, U_cl, iterations, status, winner, nullptr, nullptr});
 }
 
 }  // extern "C"
@@ -1655,34 +1633,12 @@ altro_status altro_mpc_run_team(altro_handle h, int agents, int index, const dou
     h->err = "altro_mpc_run_team: at least one round and one cycle";
     return ALTRO_INVALID_ARG;
   }
-  st = MpcCheck(h, shift, "altro_mpc_run_team");
-  if (st != ALTRO_OK) return st;
-  st = Forward(h, [&](EngineBase& e) { return e.TeamRadius(rad.data()); });
-  if (st == ALTRO_OK) st = Forward(h, [&](EngineBase& e) { return e.MpcLogBegin(cycles, shift); });
-  if (st == ALTRO_OK) st = Forward(h, [&](EngineBase& e) { return e.TeamRunBegin(agents, cycles, w); });
-  for (int c = 0; c < cycles && st == ALTRO_OK; ++c) {
-    st = TeamRounds(h, agents, index, mode, blend, rounds);
-    if (st != ALTRO_OK) break;
-    const double pen = h->opts.initial_penalty > 0 ? h->opts.initial_penalty : 1.0;
-    st = Forward(h, [&](EngineBase& e) { return e.TeamRunCycle(agents, index, shift, pen); });
-    if (st == ALTRO_OK) {  // (as behind altro_mpc_advance: the initial state now lives on the device alone)
-      h->spec.x0.clear();
-      h->spec.x0_per_instance = 0;
-    }
-  }
-  if (h->uploaded) {
-    const std::string err = h->err;
-    altro_status es = h->engine->TeamRunEnd(clear);  // (also after a failure: both free their device blocks)
-    const altro_status el = h->engine->MpcLogEnd(X_cl, U_cl, iterations, status);
-    if (es == ALTRO_OK) es = el;
-    if (st == ALTRO_OK && es != ALTRO_OK) {
-      h->err = h->engine->LastError();
-      st = es;
-    } else {
-      h->err = err;
-    }
-  }
-  return st;
+  LoopSpec spec = MakeLoopSpec(h, kLoopTeam, cycles, shift, w);
+  spec.A = agents;
+  spec.index = index;
+  spec.radius = rad.data();
+  return RunClosedLoop(h, "altro_mpc_run_team", spec, [&] { return TeamRounds(h, agents, index, mode, blend, rounds); },
+                       LoopOut{X_cl, U_cl, iterations, status, nullptr, clear, nullptr});
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstddef>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -130,6 +132,68 @@ struct TrackArgs {
   TrackStats* stats;          // [B][S]
   int check_bounds;           // options.check_forwardpass_bounds, state_max, control_max
   double state_max, control_max;
+};
+
+// ---- blocks carved into parts ---------------------------------------------------------------------------------------
+// Element counts of the K parts of one block -> the element every part starts at; off[K] is the size of the block.
+template <int K>
+struct Parts {
+  size_t cnt[K], off[K + 1];
+  Parts(std::initializer_list<size_t> counts) : cnt{}, off{} {
+    int i = 0;
+    for (size_t c : counts) {
+      cnt[i] = c;
+      off[i + 1] = off[i] + c;
+      ++i;
+    }
+  }
+  size_t total() const { return off[K]; }
+};
+// the block Engine::MpcTrack stages for a host caller, in doubles: dx0 | w | u_lo, u_hi | X_cl | U_cl | stats.  L = B S lanes;
+// an array the caller leaves out takes no room.
+inline Parts<6> TrackStageParts(int n, int m, size_t L, size_t steps, bool dx0, bool w, bool bounds, bool X_cl, bool U_cl, bool stats) {
+  static_assert(sizeof(TrackStats) % sizeof(double) == 0, "the statistics are staged in a block of doubles");
+  return {dx0 ? L * n : 0,          w ? L * steps * n : 0,
+          bounds ? 2 * (size_t)m : 0, X_cl ? L * (steps + 1) * n : 0,
+          U_cl ? L * steps * m : 0, stats ? L * (sizeof(TrackStats) / sizeof(double)) : 0};
+}
+// the block of a tracked closed-loop run, in doubles: X log | U log | one cycle's X, U | its last state | its disturbance |
+// u_lo, u_hi | statistics [cycles][B]
+inline Parts<8> TrackedRunParts(int n, int m, size_t B, size_t cycles, size_t shift) {
+  const size_t Lk = cycles * shift;
+  return {B * (Lk + 1) * n, B * Lk * m, B * (shift + 1) * n, B * shift * m, B * n, B * shift * n, 2 * (size_t)m,
+          cycles * B * (sizeof(TrackStats) / sizeof(double))};
+}
+
+// ---- one closed-loop run (altro_mpc_run, altro_mpc_run_tracked, altro_mpc_run_multistart, altro_mpc_run_team) -----------
+// EngineBase::LoopBegin .. LoopEnd: between the two, every LoopCycle (behind the cycle's solve) logs what the loop applies
+// and moves the horizon by `shift`.  All pointers are host arrays of the one C call that drives the run; any may be null.
+enum LoopKind {
+  kLoopPlain = 0,   // advance under w[c]
+  kLoopTracked,     // track `shift` knots under the gains and w[c], advance from the tracked state
+  kLoopMultiStart,  // select and spread the best of G starts, advance under w[c], perturb by dU
+  kLoopTeam         // log the team's clearance, advance under w[c] (the C API runs the team's rounds as the cycle's solve)
+};
+struct LoopSpec {
+  int kind, cycles, shift;
+  const double* w;   // the disturbance of cycle c at w + c * w_stride: [B][n], tracked [B][shift][n]
+  size_t w_stride;
+  int G, dU_per_instance;       // multi-start: starts per problem; dU [G][N][m] or [B][N][m]
+  const double* dU;
+  int A, index;                 // team: agents per team, the team's knot circle constraint
+  const double* radius;         // team: one per instance
+  const double *u_lo, *u_hi;    // tracked: [m] each, both or neither
+};
+struct LoopStep {  // what a cycle takes from the handle at the moment it runs
+  double reset_pen;  // the penalty of a row that starts afresh
+  bool ilqr_mode;    // picks the status as GetStats does
+  TrackArgs track;   // the options of a tracking call (check_bounds, state_max, control_max)
+};
+struct LoopOut {  // [B][cycles shift + 1][n], [B][cycles shift][m], [B][cycles] each; winner [B / G][cycles], clear [B / A][cycles]
+  double *X_cl, *U_cl;
+  int *iterations, *status, *winner;
+  double* clear;
+  TrackStats* track;
 };
 
 // ---- knot constraints (include/altro_knot_params.h) ----------------------------------------------------
@@ -426,16 +490,14 @@ class EngineBase {
   // receding-horizon advance (include/altro_mpc.h).  x0, w: fp64 [B][n] or nullptr, host arrays or (on_device) memory of the
   // engine's device; reset_pen: the penalty of a row that starts afresh.
   virtual altro_status MpcAdvance(int shift, const double* x0, const double* w, int on_device, double reset_pen) = 0;
-  // closed-loop log of altro_mpc_run: every advance between Begin and End appends what the loop applied
-  virtual altro_status MpcLogBegin(int cycles, int shift) = 0;
-  virtual altro_status MpcLogEnd(double* X_cl, double* U_cl, int* iterations, int* status) = 0;
   // closed-loop tracking under the gains on the device (k_mpc_track); changes nothing on the engine
   virtual altro_status MpcTrack(const TrackArgs& call, int on_device) = 0;
-  // altro_mpc_run_tracked: between Begin and End every Cycle (behind a solve) records the solve's statistics, tracks `shift`
-  // knots with one sample under w ([B][shift][n], host, or nullptr), appends to the log and advances from the tracked state
-  virtual altro_status MpcTrackedBegin(int cycles, int shift, const double* u_lo, const double* u_hi) = 0;
-  virtual altro_status MpcTrackedCycle(const double* w, const TrackArgs& opts, double reset_pen) = 0;
-  virtual altro_status MpcTrackedEnd(double* X_cl, double* U_cl, int* iterations, int* status, TrackStats* track) = 0;
+  // one closed-loop run (LoopSpec above).  Begin copies to the device what the run keeps there (radii, dU, bounds, w of the
+  // multi-start and team kinds) and opens the logs, replacing whatever an earlier run left; End downloads the logs of a run
+  // that went through all its cycles and frees the run's blocks, also after a failure
+  virtual altro_status LoopBegin(const LoopSpec& spec) = 0;
+  virtual altro_status LoopCycle(const LoopStep& step) = 0;
+  virtual altro_status LoopEnd(const LoopOut& out) = 0;
   virtual altro_status GetInitialState(double* x0) = 0;
   virtual altro_status SetPenalties(const double* rho) = 0;
   // rows and cone (1: equality) of every registered constraint, in registration order
@@ -459,24 +521,12 @@ class EngineBase {
   virtual altro_status MsSpread(int G, int* winner, int on_device, bool ilqr_mode) = 0;
   virtual altro_status MsPerturb(int G, const double* dU, int per_instance, int on_device) = 0;
   virtual altro_status MsGetBest(int G, double* X, double* U, altro_stats* stats, int* winner, int on_device, bool ilqr_mode) = 0;
-  // altro_mpc_run_multistart: Begin copies w ([cycles][B][n]) and dU to the device once (either may be null) and opens the
-  // winner log; every Cycle (behind a solve) spreads, advances by `shift` under its w and perturbs; End downloads
-  // winner[P][cycles] (may be null) and frees the block
-  virtual altro_status MsRunBegin(int G, int cycles, const double* w, const double* dU, int dU_per_instance) = 0;
-  virtual altro_status MsRunCycle(int shift, double reset_pen, bool ilqr_mode) = 0;
-  virtual altro_status MsRunEnd(int* winner) = 0;
   // teams (include/altro_team.h): A adjacent columns are the agents of one team, `index` the registration index of the team's
   // knot circle constraint.  TeamRadius copies the radii (host, one per instance) to the device, where they stay for the
   // fills and clearances that follow; clear is [B / A], host or (on_device) memory of the engine's device.
   virtual altro_status TeamRadius(const double* radius_per_instance) = 0;
   virtual altro_status TeamFill(int A, int index, int mode, double blend) = 0;
   virtual altro_status TeamClearance(int A, int index, double* clear, int on_device) = 0;
-  // altro_mpc_run_team: Begin copies w ([cycles][B][n], may be null) to the device once and opens the clearance log; every
-  // Cycle (behind the team solve) logs the clearance and advances by `shift` under its w; End downloads clear[B / A][cycles]
-  // (may be null) and frees the block
-  virtual altro_status TeamRunBegin(int A, int cycles, const double* w) = 0;
-  virtual altro_status TeamRunCycle(int A, int index, int shift, double reset_pen) = 0;
-  virtual altro_status TeamRunEnd(double* clear) = 0;
   virtual const char* LastError() = 0;
 };
 

@@ -45,6 +45,45 @@ namespace altro_hip {
     if (st_ != ALTRO_OK) return st_;     \
   } while (0)
 
+// One hipMalloc block, freed when its owner goes: one pointer, one size, no pooling.  Move-only.  Whoever lets a block go
+// while a copy on the engine's stream may still touch it synchronises that stream first.
+template <class U>
+class DevBlock {
+ public:
+  DevBlock() = default;
+  DevBlock(DevBlock&& o) noexcept : p_(o.p_), count_(o.count_) { o.p_ = nullptr, o.count_ = 0; }
+  DevBlock& operator=(DevBlock&& o) noexcept {
+    std::swap(p_, o.p_);
+    std::swap(count_, o.count_);
+    return *this;
+  }
+  ~DevBlock() { reset(); }
+  // `count` elements (at least one is asked for), in place of whatever the block held
+  hipError_t alloc(size_t count) {
+    reset();
+    const hipError_t e = hipMalloc((void**)&p_, std::max<size_t>(count, 1) * sizeof(U));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      p_ = nullptr;
+    } else {
+      count_ = count;
+    }
+    return e;
+  }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+    count_ = 0;
+  }
+  U* get() const { return p_; }
+  size_t count() const { return count_; }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  U* p_ = nullptr;
+  size_t count_ = 0;
+};
+
 // The ALTRO_HIP_* switches of an engine, all read in one place: once, when the engine is constructed
 // (the C API creates the engine at the first upload of a handle).
 constexpr int kSpecAuto = -1;  // speculation mode of the persistent kernel chosen per problem (see Switches::spec_mode)
@@ -707,15 +746,13 @@ class Engine final : public EngineBase {
   // kernels read (DevArrays::kpar).
   struct KnotCon {
     int index, k_begin, k_end, np, off, kind;  // registration index; knots; parameters; element in the record; kind
-    double* d_track = nullptr;
-    size_t cap = 0;
+    DevBlock<double> track;  // (count(): its capacity; rows x cols x np of it are the track)
     int rows = 0, cols = 0;
     // a track written by altro_team_fill_tracks (include/altro_team.h): row 0 belongs to window offset `base` (0 for every
     // track a caller set), `team` marks it, and the fill writes into the spare buffer and swaps
     int base = 0;
     bool team = false;
-    double* d_spare = nullptr;
-    size_t spare_cap = 0;
+    DevBlock<double> spare;
   };
   KnotCon* FindKnotCon(int index, const char* who) {
     for (KnotCon& c : kcons_)
@@ -735,15 +772,11 @@ class Engine final : public EngineBase {
     ctg_replayable_ = false;  // (as SetTrajectory: what a replayed backward pass would read belongs to the old parameters)
     const int cols = per_instance ? B_ : 1;
     const size_t need = (size_t)rows * cols * c->np;
-    if (need > c->cap) {
-      if (c->d_track) ALTRO_HIP_CHECK(hipFree(c->d_track));
-      c->d_track = nullptr;
-      c->cap = 0;
+    if (need > c->track.count()) {
       c->rows = 0;
-      ALTRO_HIP_CHECK(hipMalloc((void**)&c->d_track, need * sizeof(double)));
-      c->cap = need;
+      ALTRO_HIP_CHECK(c->track.alloc(need));
     }
-    ALTRO_HIP_CHECK(hipMemcpyAsync(c->d_track, P, need * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    ALTRO_HIP_CHECK(hipMemcpyAsync(c->track.get(), P, need * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
     c->rows = rows;
     c->cols = cols;
     c->base = 0;
@@ -777,15 +810,11 @@ class Engine final : public EngineBase {
     g.offset = track_offset_;
     for (int j = 0; j < g.ncon; ++j) {
       const KnotCon& c = kcons_[j];
-      g.c[j] = KnotTrack{c.rows > 0 ? c.d_track : nullptr, c.k_begin, c.k_end, c.np, c.off, c.rows, c.cols, c.base};
+      g.c[j] = KnotTrack{c.rows > 0 ? c.track.get() : nullptr, c.k_begin, c.k_end, c.np, c.off, c.rows, c.cols, c.base};
     }
     hipLaunchKernelGGL((k_knot_params<0>), GridBK(), dim3(kBlock), 0, stream_, g, d_kpar_, B_, Bp_);
   }
   void DropKnotCons() {
-    for (KnotCon& c : kcons_) {
-      if (c.d_track) hipFree(c.d_track);
-      if (c.d_spare) hipFree(c.d_spare);
-    }
     kcons_.clear();
     d_kpar_ = nullptr;
     track_offset_ = 0;
@@ -796,6 +825,15 @@ class Engine final : public EngineBase {
   // Model-independent: the kernel never calls the dynamics.  Expansions, knot costs, stored constraint values and cost-to-go
   // records stay where they are -- the next solve recomputes them -- so what a cost-to-go replay would read is gone.
   altro_status MpcAdvance(int shift, const double* x0, const double* w, int on_device, double reset_pen) override {
+    return Advance(shift, x0, w, on_device, reset_pen, nullptr);
+  }
+  // where the advance of one cycle of a closed-loop run logs what the loop applied (LoopRun); a plain advance has none
+  struct LogSlot {
+    double *X, *U;
+    int *it, *st;
+    int cycle, cycles;
+  };
+  altro_status Advance(int shift, const double* x0, const double* w, int on_device, double reset_pen, const LogSlot* log) {
     if (shift < 1 || shift > N_ - 1) {
       err_ = "altro_mpc_advance: the shift must lie in [1, N - 1]";
       return ALTRO_INVALID_ARG;
@@ -836,13 +874,13 @@ class Engine final : public EngineBase {
       g.x0 = x0;
       g.w = w;
     }
-    if (mpc_log_X_ && shift == mpc_log_shift_ && mpc_log_cycle_ < mpc_log_cycles_) {
-      g.Xlog = mpc_log_X_;
-      g.Ulog = mpc_log_U_;
-      g.itlog = mpc_log_it_;
-      g.stlog = mpc_log_it_ + (size_t)B_ * mpc_log_cycles_;
-      g.cycle = mpc_log_cycle_++;
-      g.cycles = mpc_log_cycles_;
+    if (log) {
+      g.Xlog = log->X;
+      g.Ulog = log->U;
+      g.itlog = log->it;
+      g.stlog = log->st;
+      g.cycle = log->cycle;
+      g.cycles = log->cycles;
     }
     hipLaunchKernelGGL(k_mpc_advance<T>, dim3((B_ + g.tile - 1) / g.tile, 5), dim3(kMpcThreads), 0, stream_, A_, g);
     if (A_.ref) {  // the window of a tracking cost's reference moves with the horizon (the end of the path is held)
@@ -855,46 +893,16 @@ class Engine final : public EngineBase {
     }
     return Sync();
   }
-  altro_status MpcLogBegin(int cycles, int shift) override {
-    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    MpcLogDrop();
-    const size_t nx = (size_t)B_ * ((size_t)cycles * shift + 1) * n, nu = (size_t)B_ * cycles * shift * m;
-    ALTRO_HIP_CHECK(hipMalloc((void**)&mpc_log_X_, (nx + nu) * sizeof(double)));
-    mpc_log_U_ = mpc_log_X_ + nx;
-    if (hipMalloc((void**)&mpc_log_it_, 2 * (size_t)B_ * cycles * sizeof(int)) != hipSuccess) {
-      MpcLogDrop();
-      err_ = "altro_mpc_run: out of device memory for the closed-loop log";
-      return ALTRO_HIP_ERROR;
-    }
-    mpc_log_cycles_ = cycles;
-    mpc_log_shift_ = shift;
-    mpc_log_cycle_ = 0;
-    return ALTRO_OK;
-  }
-  altro_status MpcLogEnd(double* X_cl, double* U_cl, int* iterations, int* status) override {
-    hipError_t e = hipSetDevice(desc_.device_id);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    if (mpc_log_X_ && mpc_log_cycle_ == mpc_log_cycles_) {
-      const size_t L = (size_t)mpc_log_cycles_ * mpc_log_shift_, bc = (size_t)B_ * mpc_log_cycles_;
-      if (e == hipSuccess && X_cl) e = CopySync(X_cl, mpc_log_X_, (size_t)B_ * (L + 1) * n * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && U_cl) e = CopySync(U_cl, mpc_log_U_, (size_t)B_ * L * m * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && iterations) e = CopySync(iterations, mpc_log_it_, bc * sizeof(int), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && status) e = CopySync(status, mpc_log_it_ + bc, bc * sizeof(int), hipMemcpyDeviceToHost);
-    }
-    MpcLogDrop();
-    ALTRO_HIP_CHECK(e);
-    return ALTRO_OK;
-  }
   // ---- multi-start (include/altro_multistart.h) -----------------------------------------------------
   // G adjacent columns are the starts of one problem.  Everything runs on the engine's stream; the winners live in a device
-  // array of the engine (d_ms_win_) unless the caller brings device memory for them.  The C API has checked G against the batch.
+  // array of the engine (ms_win_) unless the caller brings device memory for them.  The C API has checked G against the batch.
   altro_status MsCheck(int G) {
     if (G < 1 || B_ % G != 0) {
       err_ = "multi-start: starts must be at least 1 and divide the batch";
       return ALTRO_INVALID_ARG;
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (!d_ms_win_) ALTRO_HIP_CHECK(hipMalloc((void**)&d_ms_win_, (size_t)B_ * sizeof(int)));
+    if (!ms_win_) ALTRO_HIP_CHECK(ms_win_.alloc((size_t)B_));
     return ALTRO_OK;
   }
   // k_ms_select into `win` (device, [P]); log: one more copy at log[p * stride + off]
@@ -904,10 +912,10 @@ class Engine final : public EngineBase {
                        stride, off);
   }
   // where the winners of this call go on the device, and their way back to a host caller
-  int* MsWinDev(int* winner, int on_device) { return winner && on_device ? winner : d_ms_win_; }
+  int* MsWinDev(int* winner, int on_device) { return winner && on_device ? winner : ms_win_.get(); }
   altro_status MsWinOut(int G, int* winner, int on_device) {
     ALTRO_TRY(Sync());
-    if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, d_ms_win_, (size_t)(B_ / G) * sizeof(int), hipMemcpyDeviceToHost));
+    if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, ms_win_.get(), (size_t)(B_ / G) * sizeof(int), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   }
   altro_status MsSelect(int G, int* winner, int on_device, bool ilqr_mode) override {
@@ -1001,64 +1009,6 @@ class Engine final : public EngineBase {
     }
     return ALTRO_OK;
   }
-  // altro_mpc_run_multistart: w and dU go to the device once, the winners of every cycle stay there until the end
-  struct MsRun {
-    double *blk = nullptr, *w = nullptr, *dU = nullptr;
-    int* win = nullptr;  // [P][cycles]
-    int G = 0, cycles = 0, cycle = 0, per_instance = 0;
-  };
-  void MsRunDrop() {
-    if (ms_run_.blk) hipFree(ms_run_.blk);
-    if (ms_run_.win) hipFree(ms_run_.win);
-    ms_run_ = MsRun{};
-  }
-  altro_status MsRunBegin(int G, int cycles, const double* w, const double* dU, int dU_per_instance) override {
-    ALTRO_TRY(MsCheck(G));
-    MsRunDrop();
-    const size_t nw = w ? (size_t)cycles * B_ * n : 0, nd = dU ? (size_t)(dU_per_instance ? B_ : G) * N_ * m : 0;
-    if (nw + nd > 0) {
-      ALTRO_HIP_CHECK(hipMalloc((void**)&ms_run_.blk, (nw + nd) * sizeof(double)));
-      if (w) {
-        ms_run_.w = ms_run_.blk;
-        ALTRO_HIP_CHECK(CopySync(ms_run_.w, w, nw * sizeof(double), hipMemcpyHostToDevice));
-      }
-      if (dU) {
-        ms_run_.dU = ms_run_.blk + nw;
-        ALTRO_HIP_CHECK(CopySync(ms_run_.dU, dU, nd * sizeof(double), hipMemcpyHostToDevice));
-      }
-    }
-    ALTRO_HIP_CHECK(hipMalloc((void**)&ms_run_.win, (size_t)(B_ / G) * cycles * sizeof(int)));
-    ms_run_.G = G;
-    ms_run_.cycles = cycles;
-    ms_run_.per_instance = dU_per_instance;
-    return ALTRO_OK;
-  }
-  altro_status MsRunCycle(int shift, double reset_pen, bool ilqr_mode) override {
-    if (!ms_run_.win || ms_run_.cycle >= ms_run_.cycles) {
-      err_ = "altro_mpc_run_multistart: no cycle left";
-      return ALTRO_INVALID_ARG;
-    }
-    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    const int G = ms_run_.G, c = ms_run_.cycle++;
-    ctg_replayable_ = false;
-    LaunchMsSelect(G, ilqr_mode, d_ms_win_, ms_run_.win, ms_run_.cycles, c);
-    if (G > 1) LaunchMsSpread(G, d_ms_win_);
-    ALTRO_TRY(MpcAdvance(shift, nullptr, ms_run_.w ? ms_run_.w + (size_t)c * B_ * n : nullptr, 1, reset_pen));
-    if (ms_run_.dU) {
-      LaunchMsPerturb(G, ms_run_.dU, ms_run_.per_instance);
-      return Sync();
-    }
-    return ALTRO_OK;
-  }
-  altro_status MsRunEnd(int* winner) override {
-    hipError_t e = hipSetDevice(desc_.device_id);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    if (e == hipSuccess && winner && ms_run_.win && ms_run_.cycle == ms_run_.cycles)
-      e = CopySync(winner, ms_run_.win, (size_t)(B_ / ms_run_.G) * ms_run_.cycles * sizeof(int), hipMemcpyDeviceToHost);
-    MsRunDrop();
-    ALTRO_HIP_CHECK(e);
-    return ALTRO_OK;
-  }
 
   // ---- teams (include/altro_team.h) -----------------------------------------------------------------
   // A adjacent columns are the agents of one team; the team's knot circle constraint gets its per-instance track from the
@@ -1079,14 +1029,14 @@ class Engine final : public EngineBase {
   }
   altro_status TeamRadius(const double* radius) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (!d_team_rad_) ALTRO_HIP_CHECK(hipMalloc((void**)&d_team_rad_, 2 * (size_t)B_ * sizeof(double)));  // radii | clearances
-    ALTRO_HIP_CHECK(CopySync(d_team_rad_, radius, (size_t)B_ * sizeof(double), hipMemcpyHostToDevice));
+    if (!team_rad_) ALTRO_HIP_CHECK(team_rad_.alloc(2 * (size_t)B_));  // radii | clearances
+    ALTRO_HIP_CHECK(CopySync(team_rad_.get(), radius, (size_t)B_ * sizeof(double), hipMemcpyHostToDevice));
     return ALTRO_OK;
   }
   altro_status TeamFill(int A, int index, int mode, double blend) override {
     KnotCon* c = TeamCheck(A, index, "altro_team_fill_tracks");
     if (!c) return ALTRO_INVALID_ARG;
-    if (!d_team_rad_) {
+    if (!team_rad_) {
       err_ = "altro_team_fill_tracks: no radii on the device yet";
       return ALTRO_NOT_READY;
     }
@@ -1095,18 +1045,12 @@ class Engine final : public EngineBase {
     ctg_replayable_ = false;  // (as SetConstraintTrack)
     const int rows = N_ + 1;
     const size_t need = (size_t)B_ * rows * c->np;
-    if (need > c->spare_cap) {
-      if (c->d_spare) ALTRO_HIP_CHECK(hipFree(c->d_spare));
-      c->d_spare = nullptr;
-      c->spare_cap = 0;
-      ALTRO_HIP_CHECK(hipMalloc((void**)&c->d_spare, need * sizeof(double)));
-      c->spare_cap = need;
-    }
+    if (need > c->spare.count()) ALTRO_HIP_CHECK(c->spare.alloc(need));
     TeamFillArgs g{};
-    g.out = c->d_spare;
+    g.out = c->spare.get();
     // a track last written by a team fill has this very shape; any other is replaced, not blended
-    g.old = c->team && c->rows == rows && c->cols == B_ && blend != 1.0 ? c->d_track : nullptr;
-    g.radius = d_team_rad_;
+    g.old = c->team && c->rows == rows && c->cols == B_ && blend != 1.0 ? c->track.get() : nullptr;
+    g.radius = team_rad_.get();
     g.A = A;
     g.B = B_;
     g.rows = rows;
@@ -1116,8 +1060,7 @@ class Engine final : public EngineBase {
     const size_t total = (size_t)B_ * rows * (A - 1);
     hipLaunchKernelGGL(k_team_tracks<T>, dim3((unsigned)((total + kTeamThreads - 1) / kTeamThreads)), dim3(kTeamThreads), 0, stream_,
                        (const T*)A_.X, R::nP, Bp_, g);
-    std::swap(c->d_track, c->d_spare);
-    std::swap(c->cap, c->spare_cap);
+    std::swap(c->track, c->spare);
     c->rows = rows;
     c->cols = B_;
     c->base = track_offset_;
@@ -1128,64 +1071,16 @@ class Engine final : public EngineBase {
   void LaunchTeamClearance(int A, const KnotCon& c, double* clear, int stride, int off) {
     const int teams = B_ / A, per_block = kTeamThreads / 64;
     hipLaunchKernelGGL(k_team_clearance<T>, dim3((teams + per_block - 1) / per_block), dim3(kTeamThreads), 0, stream_, (const T*)A_.X,
-                       R::nP, Bp_, (const double*)d_team_rad_, A, teams, c.k_begin, c.k_end, clear, stride, off);
+                       R::nP, Bp_, (const double*)team_rad_.get(), A, teams, c.k_begin, c.k_end, clear, stride, off);
   }
   altro_status TeamClearance(int A, int index, double* clear, int on_device) override {
     KnotCon* c = TeamCheck(A, index, "altro_team_clearance");
-    if (!c || !d_team_rad_ || !clear) return ALTRO_INVALID_ARG;
+    if (!c || !team_rad_ || !clear) return ALTRO_INVALID_ARG;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    double* dst = on_device ? clear : d_team_rad_ + B_;
+    double* dst = on_device ? clear : team_rad_.get() + B_;
     LaunchTeamClearance(A, *c, dst, 1, 0);
     ALTRO_TRY(Sync());
     if (!on_device) ALTRO_HIP_CHECK(CopySync(clear, dst, (size_t)(B_ / A) * sizeof(double), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
-  }
-  // altro_mpc_run_team: w goes to the device once, the clearances of every cycle stay there until the end
-  struct TeamRun {
-    double *blk = nullptr, *w = nullptr, *clear = nullptr;  // clear: [B / A][cycles]
-    int A = 0, cycles = 0, cycle = 0;
-  };
-  void TeamRunDrop() {
-    if (team_run_.blk) hipFree(team_run_.blk);
-    team_run_ = TeamRun{};
-  }
-  altro_status TeamRunBegin(int A, int cycles, const double* w) override {
-    if (A < 2 || B_ % A != 0 || cycles < 1) {
-      err_ = "altro_mpc_run_team: agents must be at least 2 and divide the batch, and there is at least one cycle";
-      return ALTRO_INVALID_ARG;
-    }
-    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    TeamRunDrop();
-    const size_t nw = w ? (size_t)cycles * B_ * n : 0, nc = (size_t)(B_ / A) * cycles;
-    ALTRO_HIP_CHECK(hipMalloc((void**)&team_run_.blk, (nw + nc) * sizeof(double)));
-    team_run_.clear = team_run_.blk;
-    if (w) {
-      team_run_.w = team_run_.blk + nc;
-      ALTRO_HIP_CHECK(CopySync(team_run_.w, w, nw * sizeof(double), hipMemcpyHostToDevice));
-    }
-    team_run_.A = A;
-    team_run_.cycles = cycles;
-    return ALTRO_OK;
-  }
-  altro_status TeamRunCycle(int A, int index, int shift, double reset_pen) override {
-    KnotCon* c = TeamCheck(A, index, "altro_mpc_run_team");
-    if (!c || !d_team_rad_) return ALTRO_INVALID_ARG;
-    if (!team_run_.blk || A != team_run_.A || team_run_.cycle >= team_run_.cycles) {
-      err_ = "altro_mpc_run_team: no cycle left";
-      return ALTRO_INVALID_ARG;
-    }
-    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    const int cy = team_run_.cycle++;
-    LaunchTeamClearance(A, *c, team_run_.clear, team_run_.cycles, cy);
-    return MpcAdvance(shift, nullptr, team_run_.w ? team_run_.w + (size_t)cy * B_ * n : nullptr, 1, reset_pen);
-  }
-  altro_status TeamRunEnd(double* clear) override {
-    hipError_t e = hipSetDevice(desc_.device_id);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    if (e == hipSuccess && clear && team_run_.blk && team_run_.cycle == team_run_.cycles)
-      e = CopySync(clear, team_run_.clear, (size_t)(B_ / team_run_.A) * team_run_.cycles * sizeof(double), hipMemcpyDeviceToHost);
-    TeamRunDrop();
-    ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
   }
 
@@ -1203,20 +1098,16 @@ class Engine final : public EngineBase {
       ALTRO_TRY(LaunchTrack(call));
       return Sync();
     }
-    // the staged block, in doubles: dx0 | w | u_lo, u_hi | X_cl | U_cl | stats
-    const size_t L = (size_t)B_ * (size_t)call.S, steps = (size_t)call.steps;
-    static_assert(sizeof(TrackStats) % sizeof(double) == 0, "the statistics are staged in a block of doubles");
-    const size_t cnt[6] = {call.dx0 ? L * n : 0,           call.w ? L * steps * n : 0,     call.u_lo ? 2 * (size_t)m : 0,
-                           call.X_cl ? L * (steps + 1) * n : 0, call.U_cl ? L * steps * m : 0,
-                           call.stats ? L * (sizeof(TrackStats) / sizeof(double)) : 0};
-    size_t off[7] = {0};
-    for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + cnt[i];
-    double* blk = nullptr;
-    if (hipMalloc((void**)&blk, std::max<size_t>(off[6], 1) * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      err_ = "altro_mpc_track: out of device memory for " + std::to_string(off[6] * sizeof(double)) + " bytes of staged inputs and logs";
+    // the staged block (TrackStageParts); it goes when this call returns, behind the synchronisation below
+    const Parts<6> p = TrackStageParts(n, m, (size_t)B_ * (size_t)call.S, (size_t)call.steps, call.dx0, call.w, call.u_lo, call.X_cl,
+                                       call.U_cl, call.stats);
+    DevBlock<double> stage;
+    if (stage.alloc(p.total()) != hipSuccess) {
+      err_ = "altro_mpc_track: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged inputs and logs";
       return ALTRO_HIP_ERROR;
     }
+    double* const blk = stage.get();
+    const size_t *cnt = p.cnt, *off = p.off;
     TrackArgs g = call;
     hipError_t e = hipSuccess;
     auto up = [&](const double* src, int i) {
@@ -1241,103 +1132,177 @@ class Engine final : public EngineBase {
       if (e == hipSuccess && call.stats) e = hipMemcpyAsync(call.stats, g.stats, cnt[5] * sizeof(double), hipMemcpyDeviceToHost, stream_);
     }
     const hipError_t es = hipStreamSynchronize(stream_);  // (also after a failure: the block must not go under a copy in flight)
-    hipFree(blk);
     ALTRO_TRY(st);
     ALTRO_HIP_CHECK(e);
     ALTRO_HIP_CHECK(es);
     return ALTRO_OK;
   }
-  altro_status MpcTrackedBegin(int cycles, int shift, const double* u_lo, const double* u_hi) override {
+
+  // ---- one closed-loop run (LoopSpec, altro_common.hpp) ----------------------------------------------
+  // What lives on the device between LoopBegin and LoopEnd: one block of doubles, one of ints, one cycle counter.  The plain,
+  // multi-start and team kinds log through k_mpc_advance (LogSlot): rows of X, U per instance, iterations and statuses
+  // [B][cycles].  The closed-loop states of the tracked kind are the TRACKED ones, so it does not use that log: k_mpc_track
+  // writes one cycle's rows, two strided copies append them, and iterations, statuses and TrackStats are recorded cycle-major
+  // [cycles][B] (one contiguous row per cycle) and transposed on the host in LoopEnd.  One layout for both takes a kernel
+  // change.
+  struct LoopRun {
+    LoopSpec spec{};  // (its host pointers belong to the C call that drives the run)
+    int cycle = 0;    // cycles that went through
+    DevBlock<double> d;
+    DevBlock<int> i;
+    double *Xlog = nullptr, *Ulog = nullptr;  // [B][cycles shift + 1][n], [B][cycles shift][m]
+    int *it = nullptr, *win = nullptr;        // iterations | statuses; multi-start: winners [B / G][cycles]
+    double *w = nullptr, *dU = nullptr, *clear = nullptr;  // multi-start, team: w and dU on the device; team: [B / A][cycles]
+    double *Xc = nullptr, *Uc = nullptr, *xend = nullptr, *wc = nullptr, *ulo = nullptr, *uhi = nullptr;  // tracked: one cycle's
+    TrackStats* stats = nullptr;                                                                          // arrays; [cycles][B]
+  };
+  altro_status LoopBegin(const LoopSpec& s) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    TrackedDrop();
-    TrackedLog& t = tracked_;
-    const size_t B = (size_t)B_, Lk = (size_t)cycles * shift, sd = sizeof(TrackStats) / sizeof(double);
-    // in doubles: X log | U log | one cycle's X, U | its last state | its disturbance | bounds | statistics [cycles][B]
-    const size_t cnt[8] = {B * (Lk + 1) * n, B * Lk * m, B * ((size_t)shift + 1) * n, B * shift * m, B * n, B * shift * n, 2 * (size_t)m,
-                           (size_t)cycles * B * sd};
-    size_t off[9] = {0};
-    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + cnt[i];
-    if (hipMalloc((void**)&t.blk, off[8] * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&t.it, 2 * (size_t)cycles * B * sizeof(int)) != hipSuccess) {
-      (void)hipGetLastError();
-      TrackedDrop();
-      err_ = "altro_mpc_run_tracked: out of device memory for the closed-loop log";
+    run_ = LoopRun{};
+    const bool ms = s.kind == kLoopMultiStart, team = s.kind == kLoopTeam;
+    if (ms) ALTRO_TRY(MsCheck(s.G));
+    if (team) {
+      if (s.A < 2 || B_ % s.A != 0 || !s.radius) {
+        err_ = "altro_mpc_run_team: agents must be at least 2 and divide the batch, with one radius per instance";
+        return ALTRO_INVALID_ARG;
+      }
+      ALTRO_TRY(TeamRadius(s.radius));
+    }
+    LoopRun r;
+    r.spec = s;
+    const size_t B = (size_t)B_, cycles = (size_t)s.cycles, Lk = cycles * s.shift;
+    const size_t nw = s.w && (ms || team) ? cycles * B * n : 0, nd = ms && s.dU ? (size_t)(s.dU_per_instance ? B_ : s.G) * N_ * m : 0;
+    hipError_t e;
+    if (s.kind == kLoopTracked) {
+      const Parts<8> p = TrackedRunParts(n, m, B, cycles, (size_t)s.shift);
+      e = r.d.alloc(p.total());
+      double* const b = r.d.get();
+      r.Xlog = b + p.off[0];
+      r.Ulog = b + p.off[1];
+      r.Xc = b + p.off[2];
+      r.Uc = b + p.off[3];
+      r.xend = b + p.off[4];
+      r.wc = b + p.off[5];
+      r.ulo = s.u_lo ? b + p.off[6] : nullptr;
+      r.uhi = s.u_hi ? b + p.off[6] + m : nullptr;
+      r.stats = reinterpret_cast<TrackStats*>(b + p.off[7]);
+    } else {  // X log | U log | w | dU | clearances
+      const Parts<5> p{B * (Lk + 1) * n, B * Lk * m, nw, nd, team ? (size_t)(B_ / s.A) * cycles : 0};
+      e = r.d.alloc(p.total());
+      double* const b = r.d.get();
+      r.Xlog = b + p.off[0];
+      r.Ulog = b + p.off[1];
+      r.w = nw ? b + p.off[2] : nullptr;
+      r.dU = nd ? b + p.off[3] : nullptr;
+      r.clear = b + p.off[4];
+    }
+    if (e == hipSuccess) e = r.i.alloc(2 * B * cycles + (ms ? (size_t)(B_ / s.G) * cycles : 0));
+    if (e != hipSuccess) {
+      err_ = "closed-loop run: out of device memory for the logs";
       return ALTRO_HIP_ERROR;
     }
-    t.Xlog = t.blk + off[0];
-    t.Ulog = t.blk + off[1];
-    t.Xc = t.blk + off[2];
-    t.Uc = t.blk + off[3];
-    t.xend = t.blk + off[4];
-    t.w = t.blk + off[5];
-    t.ulo = u_lo ? t.blk + off[6] : nullptr;
-    t.uhi = u_hi ? t.blk + off[6] + m : nullptr;
-    t.stats = reinterpret_cast<TrackStats*>(t.blk + off[7]);
-    t.cycles = cycles;
-    t.shift = shift;
-    t.cycle = 0;
-    if (u_lo) ALTRO_HIP_CHECK(CopySync(t.blk + off[6], u_lo, m * sizeof(double), hipMemcpyHostToDevice));
-    if (u_hi) ALTRO_HIP_CHECK(CopySync(t.blk + off[6] + m, u_hi, m * sizeof(double), hipMemcpyHostToDevice));
+    r.it = r.i.get();
+    r.win = r.it + 2 * B * cycles;
+    // (every copy is waited for: a block that goes on a failure has none in flight)
+    if (r.ulo) ALTRO_HIP_CHECK(CopySync(r.ulo, s.u_lo, m * sizeof(double), hipMemcpyHostToDevice));
+    if (r.uhi) ALTRO_HIP_CHECK(CopySync(r.uhi, s.u_hi, m * sizeof(double), hipMemcpyHostToDevice));
+    if (r.w) ALTRO_HIP_CHECK(CopySync(r.w, s.w, nw * sizeof(double), hipMemcpyHostToDevice));
+    if (r.dU) ALTRO_HIP_CHECK(CopySync(r.dU, s.dU, nd * sizeof(double), hipMemcpyHostToDevice));
+    run_ = std::move(r);
     return ALTRO_OK;
   }
-  altro_status MpcTrackedCycle(const double* w, const TrackArgs& opts, double reset_pen) override {
-    TrackedLog& t = tracked_;
-    if (!t.blk || t.cycle >= t.cycles) {
-      err_ = "altro_mpc_run_tracked: no log is open";
+  altro_status LoopCycle(const LoopStep& step) override {
+    LoopRun& r = run_;
+    const LoopSpec& s = r.spec;
+    if (!r.i || r.cycle >= s.cycles) {
+      err_ = "closed-loop run: no cycle left";
       return ALTRO_NOT_READY;
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    const size_t B = (size_t)B_, s = (size_t)t.shift, Lk = (size_t)t.cycles * s, c = (size_t)t.cycle, cb = (size_t)t.cycles * B;
-    // the statistics of the solve behind this cycle
-    ALTRO_HIP_CHECK(hipMemcpyAsync(t.it + c * B, A_.it_total, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
-    ALTRO_HIP_CHECK(hipMemcpyAsync(t.it + cb + c * B, A_.status_al, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
-    if (w) ALTRO_HIP_CHECK(hipMemcpyAsync(t.w, w, B * s * n * sizeof(double), hipMemcpyHostToDevice, stream_));
-    TrackArgs g = opts;
-    g.steps = t.shift;
-    g.S = 1;
-    g.dx0 = nullptr;
-    g.w = w ? t.w : nullptr;
-    g.u_lo = t.ulo;
-    g.u_hi = t.uhi;
-    g.X_cl = t.Xc;
-    g.U_cl = t.Uc;
-    g.x_end = t.xend;
-    g.stats = t.stats + c * B;
-    ALTRO_TRY(LaunchTrack(g));
-    // rows c s .. c s + s of every instance's log (the last of them is the next cycle's first, and the log's last row)
-    ALTRO_HIP_CHECK(hipMemcpy2DAsync(t.Xlog + c * s * n, (Lk + 1) * n * sizeof(double), t.Xc, (s + 1) * n * sizeof(double),
-                                     (s + 1) * n * sizeof(double), B, hipMemcpyDeviceToDevice, stream_));
-    ALTRO_HIP_CHECK(hipMemcpy2DAsync(t.Ulog + c * s * m, Lk * m * sizeof(double), t.Uc, s * m * sizeof(double), s * m * sizeof(double), B,
-                                     hipMemcpyDeviceToDevice, stream_));
-    ++t.cycle;
-    return MpcAdvance(t.shift, t.xend, nullptr, 1, reset_pen);
+    const size_t B = (size_t)B_, c = (size_t)r.cycle, cb = (size_t)s.cycles * B;
+    // this cycle's disturbance: the run's device copy, or the caller's array (the plain advance and the tracking stage it)
+    const double* const w = s.w ? (r.w ? r.w : s.w) + c * s.w_stride : nullptr;
+    const LogSlot log{r.Xlog, r.Ulog, r.it, r.it + cb, r.cycle, s.cycles};
+    if (s.kind == kLoopPlain) {
+      ALTRO_TRY(Advance(s.shift, nullptr, w, 0, step.reset_pen, &log));
+    } else if (s.kind == kLoopTracked) {
+      const size_t sh = (size_t)s.shift, Lk = (size_t)s.cycles * sh;
+      // the statistics of the solve behind this cycle
+      ALTRO_HIP_CHECK(hipMemcpyAsync(r.it + c * B, A_.it_total, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+      ALTRO_HIP_CHECK(hipMemcpyAsync(r.it + cb + c * B, A_.status_al, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+      if (w) ALTRO_HIP_CHECK(hipMemcpyAsync(r.wc, w, B * sh * n * sizeof(double), hipMemcpyHostToDevice, stream_));
+      TrackArgs g = step.track;
+      g.steps = s.shift;
+      g.S = 1;
+      g.dx0 = nullptr;
+      g.w = w ? r.wc : nullptr;
+      g.u_lo = r.ulo;
+      g.u_hi = r.uhi;
+      g.X_cl = r.Xc;
+      g.U_cl = r.Uc;
+      g.x_end = r.xend;
+      g.stats = r.stats + c * B;
+      ALTRO_TRY(LaunchTrack(g));
+      // rows c s .. c s + s of every instance's log (the last of them is the next cycle's first, and the log's last row)
+      ALTRO_HIP_CHECK(hipMemcpy2DAsync(r.Xlog + c * sh * n, (Lk + 1) * n * sizeof(double), r.Xc, (sh + 1) * n * sizeof(double),
+                                       (sh + 1) * n * sizeof(double), B, hipMemcpyDeviceToDevice, stream_));
+      ALTRO_HIP_CHECK(hipMemcpy2DAsync(r.Ulog + c * sh * m, Lk * m * sizeof(double), r.Uc, sh * m * sizeof(double), sh * m * sizeof(double), B,
+                                       hipMemcpyDeviceToDevice, stream_));
+      ALTRO_TRY(Advance(s.shift, r.xend, nullptr, 1, step.reset_pen, nullptr));
+    } else if (s.kind == kLoopMultiStart) {
+      ctg_replayable_ = false;
+      LaunchMsSelect(s.G, step.ilqr_mode, ms_win_.get(), r.win, s.cycles, r.cycle);
+      if (s.G > 1) LaunchMsSpread(s.G, ms_win_.get());
+      ALTRO_TRY(Advance(s.shift, nullptr, w, 1, step.reset_pen, &log));
+      if (r.dU) {
+        LaunchMsPerturb(s.G, r.dU, s.dU_per_instance);
+        ALTRO_TRY(Sync());
+      }
+    } else {
+      KnotCon* kc = TeamCheck(s.A, s.index, "altro_mpc_run_team");
+      if (!kc || !team_rad_) return ALTRO_INVALID_ARG;
+      LaunchTeamClearance(s.A, *kc, r.clear, s.cycles, r.cycle);
+      ALTRO_TRY(Advance(s.shift, nullptr, w, 1, step.reset_pen, &log));
+    }
+    ++r.cycle;
+    return ALTRO_OK;
   }
-  altro_status MpcTrackedEnd(double* X_cl, double* U_cl, int* iterations, int* status, TrackStats* track) override {
-    TrackedLog& t = tracked_;
+  altro_status LoopEnd(const LoopOut& o) override {
+    LoopRun r;  // the run goes with this call, whatever happens: behind the synchronisation no copy touches its blocks
+    std::swap(r, run_);
+    const LoopSpec& s = r.spec;
     hipError_t e = hipSetDevice(desc_.device_id);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    if (t.blk && t.cycle == t.cycles) {
-      const size_t B = (size_t)B_, Lk = (size_t)t.cycles * t.shift, cb = (size_t)t.cycles * B;
-      if (e == hipSuccess && X_cl) e = CopySync(X_cl, t.Xlog, B * (Lk + 1) * n * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && U_cl) e = CopySync(U_cl, t.Ulog, B * Lk * m * sizeof(double), hipMemcpyDeviceToHost);
-      // recorded [cycles][B] (one contiguous row per cycle), handed out [B][cycles]
-      if (e == hipSuccess && (iterations || status)) {
-        std::vector<int> h(2 * cb);
-        e = CopySync(h.data(), t.it, h.size() * sizeof(int), hipMemcpyDeviceToHost);
-        for (size_t c = 0; c < (size_t)t.cycles && e == hipSuccess; ++c)
-          for (size_t b = 0; b < B; ++b) {
-            if (iterations) iterations[b * t.cycles + c] = h[c * B + b];
-            if (status) status[b * t.cycles + c] = h[cb + c * B + b];
-          }
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      if (e == hipSuccess && dst) e = CopySync(dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    if (r.i && r.cycle == s.cycles) {
+      const size_t B = (size_t)B_, cycles = (size_t)s.cycles, Lk = cycles * s.shift, cb = cycles * B;
+      down(o.X_cl, r.Xlog, B * (Lk + 1) * n * sizeof(double));
+      down(o.U_cl, r.Ulog, B * Lk * m * sizeof(double));
+      if (s.kind != kLoopTracked) {
+        down(o.iterations, r.it, cb * sizeof(int));
+        down(o.status, r.it + cb, cb * sizeof(int));
+      } else {  // recorded [cycles][B], handed out [B][cycles]
+        if (o.iterations || o.status) {
+          std::vector<int> h(2 * cb);
+          down(h.data(), r.it, h.size() * sizeof(int));
+          for (size_t c = 0; c < cycles && e == hipSuccess; ++c)
+            for (size_t b = 0; b < B; ++b) {
+              if (o.iterations) o.iterations[b * cycles + c] = h[c * B + b];
+              if (o.status) o.status[b * cycles + c] = h[cb + c * B + b];
+            }
+        }
+        if (o.track) {
+          std::vector<TrackStats> h(cb);
+          down(h.data(), r.stats, h.size() * sizeof(TrackStats));
+          for (size_t c = 0; c < cycles && e == hipSuccess; ++c)
+            for (size_t b = 0; b < B; ++b) o.track[b * cycles + c] = h[c * B + b];
+        }
       }
-      if (e == hipSuccess && track) {
-        std::vector<TrackStats> h(cb);
-        e = CopySync(h.data(), t.stats, h.size() * sizeof(TrackStats), hipMemcpyDeviceToHost);
-        for (size_t c = 0; c < (size_t)t.cycles && e == hipSuccess; ++c)
-          for (size_t b = 0; b < B; ++b) track[b * t.cycles + c] = h[c * B + b];
-      }
+      if (s.kind == kLoopMultiStart) down(o.winner, r.win, (size_t)(B_ / s.G) * cycles * sizeof(int));
+      if (s.kind == kLoopTeam) down(o.clear, r.clear, (size_t)(B_ / s.A) * cycles * sizeof(double));
     }
-    TrackedDrop();
     ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
   }
@@ -1391,26 +1356,6 @@ class Engine final : public EngineBase {
     else
       hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
     return ALTRO_OK;
-  }
-  // closed-loop log of altro_mpc_run_tracked (MpcTrackedBegin .. MpcTrackedEnd): one block of doubles, one of ints
-  struct TrackedLog {
-    double *blk = nullptr, *Xlog = nullptr, *Ulog = nullptr, *Xc = nullptr, *Uc = nullptr, *xend = nullptr, *w = nullptr, *ulo = nullptr,
-           *uhi = nullptr;
-    TrackStats* stats = nullptr;
-    int* it = nullptr;  // iterations [cycles][B], then statuses [cycles][B]
-    int cycles = 0, shift = 0, cycle = 0;
-  };
-  void TrackedDrop() {
-    if (tracked_.blk) hipFree(tracked_.blk);
-    if (tracked_.it) hipFree(tracked_.it);
-    tracked_ = TrackedLog{};
-  }
-  void MpcLogDrop() {
-    if (mpc_log_X_) hipFree(mpc_log_X_);
-    if (mpc_log_it_) hipFree(mpc_log_it_);
-    mpc_log_X_ = mpc_log_U_ = nullptr;
-    mpc_log_it_ = nullptr;
-    mpc_log_cycles_ = mpc_log_shift_ = mpc_log_cycle_ = 0;
   }
   // ---- helpers ----------------------------------------------------------------------------------
   dim3 GridB() const { return dim3((B_ + kBlock - 1) / kBlock); }
@@ -1607,14 +1552,6 @@ class Engine final : public EngineBase {
     allocs_.clear();
     if (A_.hist) hipFree(A_.hist);
     if (A_.hist_len) hipFree(A_.hist_len);
-    MpcLogDrop();
-    TrackedDrop();
-    MsRunDrop();
-    if (d_ms_win_) hipFree(d_ms_win_);
-    d_ms_win_ = nullptr;
-    TeamRunDrop();
-    if (d_team_rad_) hipFree(d_team_rad_);
-    d_team_rad_ = nullptr;
     if (d_stage_) hipFree(d_stage_);
     d_stage_ = nullptr;
     stage_cap_ = 0;
@@ -2219,10 +2156,6 @@ class Engine final : public EngineBase {
       ref_offset_ = s.ref_offset;
     }
     // the knot constraints, and whatever altro_set_constraint_track / altro_set_track_offset recorded before the upload
-    for (KnotCon& c : kcons_) {
-      if (c.d_track) hipFree(c.d_track);
-      if (c.d_spare) hipFree(c.d_spare);
-    }
     kcons_.clear();
     for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i) {
       if (con_knot_off_[i] < 0) continue;
@@ -2233,7 +2166,7 @@ class Engine final : public EngineBase {
       c.np = s.cons[i].nparams;
       c.off = con_knot_off_[i];
       c.kind = s.cons[i].kind;
-      kcons_.push_back(c);
+      kcons_.push_back(std::move(c));
     }
     if (st == ALTRO_OK) track_offset_ = s.track_offset;
     for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i)
@@ -3081,14 +3014,9 @@ class Engine final : public EngineBase {
   std::vector<int> knot_class_, knot_rowbase_;
   std::vector<int> con_kb_, con_ke_, con_p_, con_eq_;  // knots, rows and cone of every registered constraint
   std::map<int, int*> mpc_maps_;                       // shift -> device row map of the advance (owned through allocs_)
-  double *mpc_log_X_ = nullptr, *mpc_log_U_ = nullptr;  // closed-loop log of altro_mpc_run (MpcLogBegin .. MpcLogEnd)
-  int* mpc_log_it_ = nullptr;                           // iterations [B][cycles], then statuses [B][cycles]
-  int mpc_log_cycles_ = 0, mpc_log_shift_ = 0, mpc_log_cycle_ = 0;
-  TrackedLog tracked_;                                  // closed-loop log of altro_mpc_run_tracked
-  int* d_ms_win_ = nullptr;                             // winners of the last multi-start call, [B] (MsCheck)
-  MsRun ms_run_;                                        // altro_mpc_run_multistart (MsRunBegin .. MsRunEnd)
-  double* d_team_rad_ = nullptr;                        // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
-  TeamRun team_run_;                                    // altro_mpc_run_team (TeamRunBegin .. TeamRunEnd)
+  LoopRun run_;                 // the closed-loop run in progress (LoopBegin .. LoopEnd)
+  DevBlock<int> ms_win_;        // winners of the last multi-start call, [B] (MsCheck)
+  DevBlock<double> team_rad_;   // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
   std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;
   volatile int* h_counter_ = nullptr;  // pinned + mapped: one word per sweep
