@@ -28,6 +28,7 @@ F64, F32 = 0, 1
 MODEL_UNICYCLE, MODEL_TRIPLE_INTEGRATOR, MODEL_QUADROTOR12 = 1, 2, 3
 CON_GOAL, CON_CONTROL_BOUND, CON_CIRCLE, CON_USER = 1, 2, 3, 4
 TEAM_ALL, TEAM_PRIORITY = 0, 1  # include/altro_team.h
+COV_W_PER_INSTANCE, COV_W_PER_KNOT = 1, 2  # include/altro_covariance.h: w_mode bits
 # altro::SolverStatus, altro/common/solver_stats.hpp:20-31
 (SOLVED, UNSOLVED, STATE_LIMIT, CONTROL_LIMIT, COST_INCREASE, MAX_ITERATIONS, MAX_OUTER_ITERATIONS,
  MAX_INNER_ITERATIONS, MAX_PENALTY, BACKWARD_PASS_REGULARIZATION_FAILED) = range(10)
@@ -812,6 +813,61 @@ class BatchSolver:
                    C.c_int(rounds), C.c_int(cycles), C.c_int(shift), _dp(w), *logs, _dp(clear))
         out["clear"] = clear[:self._teams(agents), :max(cycles, 0)]
         return out
+
+    # -- closed-loop covariance (include/altro_covariance.h) -----------------------------------------
+    def _cov_inputs(self, steps, Sigma0, W):
+        n, B, K = self.n, self.batch, max(int(steps), 0)
+        Sigma0, W = _f64(Sigma0), _f64(W)
+        if Sigma0 is not None and Sigma0.shape not in ((n, n), (B, n, n)):
+            raise ValueError(f"Sigma0 must have shape ({n}, {n}) or ({B}, {n}, {n})")
+        w_mode = 0
+        if W is not None:
+            # (batch == steps: a 3-d W is read per instance; pass [B][steps][n][n] for the other meaning)
+            shapes = {(n, n): 0, (B, n, n): COV_W_PER_INSTANCE, (K, n, n): COV_W_PER_KNOT,
+                      (B, K, n, n): COV_W_PER_INSTANCE | COV_W_PER_KNOT}
+            if W.shape not in shapes:
+                raise ValueError(f"W must have shape ({n}, {n}), ({B}, {n}, {n}), ({K}, {n}, {n}) or ({B}, {K}, {n}, {n})")
+            w_mode = COV_W_PER_INSTANCE if W.shape == (B, n, n) else shapes[W.shape]
+        return Sigma0, 1 if Sigma0 is not None and Sigma0.ndim == 3 else 0, W, w_mode
+
+    def cov_propagate(self, steps, Sigma0=None, W=None, want=("Sigma", "sx", "su", "rpos")):
+        """The closed-loop covariance along the plan under the gains on the device (altro_cov_propagate):
+        Sigma_{k+1} = F_k Sigma_k F_k^T + W_k, F_k = A_k + B_k K_k, from ``Sigma0`` ([n][n] or [B][n][n]; None: zero) and
+        ``W`` ([n][n], [B][n][n], [steps][n][n] or [B][steps][n][n]; None: zero), of which only the lower triangles are
+        read.  Changes nothing on the handle.  Returns a dict of the arrays named in ``want``: Sigma [B][steps+1][n][n],
+        sx [B][steps+1][n], su [B][steps][m], rpos [B][steps+1]."""
+        K = max(int(steps), 0)
+        Sigma0, per, W, w_mode = self._cov_inputs(steps, Sigma0, W)
+        shapes = dict(Sigma=(self.batch, K + 1, self.n, self.n), sx=(self.batch, K + 1, self.n), su=(self.batch, K, self.m),
+                      rpos=(self.batch, K + 1))
+        unknown = [k for k in want if k not in shapes]
+        if unknown:
+            raise ValueError(f"want names Sigma, sx, su, rpos; got {unknown}")
+        out = {k: np.zeros(shapes[k]) for k in want}
+        self._call("cov_propagate", C.c_int(steps), _dp(Sigma0), C.c_int(per), _dp(W), C.c_int(w_mode),
+                   *(_dp(out.get(k)) for k in ("Sigma", "sx", "su", "rpos")))
+        return out
+
+    def cov_propagate_device(self, steps, Sigma0_ptr=0, sigma0_per_instance=False, W_ptr=0, w_mode=0, Sigma_ptr=0, sx_ptr=0,
+                             su_ptr=0, rpos_ptr=0):
+        """cov_propagate with every array in fp64 memory of this handle's device (any pointer may be 0, not all outputs)."""
+        self._call("cov_propagate_device", C.c_int(steps), C.c_void_p(Sigma0_ptr or None), C.c_int(1 if sigma0_per_instance else 0),
+                   C.c_void_p(W_ptr or None), C.c_int(w_mode), *(C.c_void_p(p or None) for p in (Sigma_ptr, sx_ptr, su_ptr, rpos_ptr)))
+
+    def cov_inflate_circles(self, index, base, kappa, rpos):
+        """Write the track of knot circle constraint ``index`` on the device, per instance: the centres of ``base``
+        ([rows][3 nobs] or [B][rows][3 nobs]) and the radii rad + kappa * rpos[b][min(max(r - offset, 0), N)]; ``rpos``
+        [B][N+1] as cov_propagate(N) returns it.  The window offset stays."""
+        base, rpos = _f64(base), _f64(rpos)
+        rows, per = self._track_shape(index, base)
+        if rpos.shape != (self.batch, self.N + 1):
+            raise ValueError(f"rpos must have shape ({self.batch}, {self.N + 1})")
+        self._call("cov_inflate_circles", C.c_int(index), _dp(base), C.c_int(rows), C.c_int(per), C.c_double(kappa), _dp(rpos))
+
+    def cov_inflate_circles_device(self, index, base_ptr, rows, per_instance, kappa, rpos_ptr):
+        """cov_inflate_circles with ``base`` and ``rpos`` in fp64 memory of this handle's device."""
+        self._call("cov_inflate_circles_device", C.c_int(index), C.c_void_p(base_ptr or None), C.c_int(rows),
+                   C.c_int(1 if per_instance else 0), C.c_double(kappa), C.c_void_p(rpos_ptr or None))
 
     # -- device interop ---------------------------------------------------------------------------
     def pack_results_device(self, device_ptr):

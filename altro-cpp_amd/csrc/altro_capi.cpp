@@ -38,12 +38,13 @@
 #include "../../include/altro_knot_params.h"
 #include "../../include/altro_multistart.h"
 #include "../../include/altro_team.h"
+#include "../../include/altro_covariance.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 13  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 14  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -1639,6 +1640,102 @@ altro_status altro_mpc_run_team(altro_handle h, int agents, int index, const dou
   spec.radius = rad.data();
   return RunClosedLoop(h, "altro_mpc_run_team", spec, [&] { return TeamRounds(h, agents, index, mode, blend, rounds); },
                        LoopOut{X_cl, U_cl, iterations, status, nullptr, clear, nullptr});
+}
+
+}  // extern "C"
+
+// ---- closed-loop covariance (include/altro_covariance.h) ----------------------------------------------------------------
+namespace {
+
+// both propagation entry points: everything that can be refused without a device first
+altro_status CovPropagateImpl(altro_handle h, int steps, const double* Sigma0, int sigma0_per_instance, const double* W, int w_mode,
+                              double* Sigma, double* sx, double* su, double* rpos, int on_device, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const int N = h->spec.desc.N;
+  if (steps < 1 || steps > N) {
+    h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
+    return ALTRO_INVALID_ARG;
+  }
+  if (!Sigma && !sx && !su && !rpos) {
+    h->err = std::string(who) + ": at least one of Sigma, sx, su and rpos is required";
+    return ALTRO_INVALID_ARG;
+  }
+  if (w_mode < 0 || w_mode > (ALTRO_COV_W_PER_INSTANCE | ALTRO_COV_W_PER_KNOT)) {
+    h->err = std::string(who) + ": w_mode is a combination of ALTRO_COV_W_PER_INSTANCE and ALTRO_COV_W_PER_KNOT, got " + std::to_string(w_mode);
+    return ALTRO_INVALID_ARG;
+  }
+  if (rpos && h->spec.desc.n < 2) {
+    h->err = std::string(who) + ": rpos is the spread of the position (x[0], x[1]) and needs at least two states";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!h->has_gains) {
+    h->err = std::string(who) + ": no backward pass has produced gains on this handle yet (altro_solve_al, altro_solve_ilqr, "
+             "altro_backward_pass)";
+    return ALTRO_NOT_READY;
+  }
+  CovArgs g{};
+  g.steps = steps;
+  g.sigma0_per_instance = sigma0_per_instance ? 1 : 0;
+  g.w_mode = w_mode;
+  g.Sigma0 = Sigma0;
+  g.W = W;
+  g.Sigma = Sigma;
+  g.sx = sx;
+  g.su = su;
+  g.rpos = rpos;
+  return Forward(h, [&](EngineBase& e) { return e.CovPropagate(g, on_device); });
+}
+altro_status CovInflateImpl(altro_handle h, int index, const double* base, int rows, int per_instance, double kappa, const double* rpos,
+                            int on_device, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
+    h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
+    return ALTRO_INVALID_ARG;
+  }
+  if (h->spec.cons[index].kind != ALTRO_CON_CIRCLE || h->spec.cons[index].nparams % 3 != 0) {
+    h->err = std::string(who) + ": constraint " + std::to_string(index) + " must be an ALTRO_CON_CIRCLE";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!base || !rpos) {
+    h->err = std::string(who) + ": base and rpos are required";
+    return ALTRO_INVALID_ARG;
+  }
+  if (rows < 1) {
+    h->err = std::string(who) + ": the base track needs at least one row, got " + std::to_string(rows);
+    return ALTRO_INVALID_ARG;
+  }
+  if (!(kappa >= 0.0) || !(kappa < std::numeric_limits<double>::infinity())) {  // (a NaN fails the first)
+    h->err = std::string(who) + ": kappa must be finite and not negative";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.CovInflate(index, base, rows, per_instance ? 1 : 0, kappa, rpos, on_device); });
+}
+
+}  // namespace
+
+extern "C" {
+
+altro_status altro_cov_propagate(altro_handle h, int steps, const double* Sigma0, int sigma0_per_instance, const double* W, int w_mode,
+                                 double* Sigma, double* sx, double* su, double* rpos) {
+  return CovPropagateImpl(h, steps, Sigma0, sigma0_per_instance, W, w_mode, Sigma, sx, su, rpos, 0, "altro_cov_propagate");
+}
+altro_status altro_cov_propagate_device(altro_handle h, int steps, const void* Sigma0_device, int sigma0_per_instance,
+                                        const void* W_device, int w_mode, void* Sigma_device, void* sx_device, void* su_device,
+                                        void* rpos_device) {
+  return CovPropagateImpl(h, steps, (const double*)Sigma0_device, sigma0_per_instance, (const double*)W_device, w_mode,
+                          (double*)Sigma_device, (double*)sx_device, (double*)su_device, (double*)rpos_device, 1,
+                          "altro_cov_propagate_device");
+}
+altro_status altro_cov_inflate_circles(altro_handle h, int index, const double* base, int rows, int per_instance, double kappa,
+                                       const double* rpos) {
+  return CovInflateImpl(h, index, base, rows, per_instance, kappa, rpos, 0, "altro_cov_inflate_circles");
+}
+altro_status altro_cov_inflate_circles_device(altro_handle h, int index, const void* base_device, int rows, int per_instance,
+                                              double kappa, const void* rpos_device) {
+  return CovInflateImpl(h, index, (const double*)base_device, rows, per_instance, kappa, (const double*)rpos_device, 1,
+                        "altro_cov_inflate_circles_device");
 }
 
 }  // extern "C"

@@ -134,6 +134,14 @@ struct TrackArgs {
   double state_max, control_max;
 };
 
+// One call of Engine::CovPropagate / one launch of k_cov_recur (include/altro_covariance.h).  Every pointer may be null; host
+// or device memory as the call says.
+struct CovArgs {
+  int steps, sigma0_per_instance, w_mode;  // w_mode: bit 0 per instance, bit 1 per knot
+  const double *Sigma0, *W;                // [n][n] | [B][n][n];  [n][n] | [B][n][n] | [steps][n][n] | [B][steps][n][n]
+  double *Sigma, *sx, *su, *rpos;          // [B][steps + 1][n][n], [B][steps + 1][n], [B][steps][m], [B][steps + 1]
+};
+
 // ---- blocks carved into parts ---------------------------------------------------------------------------------------
 // Element counts of the K parts of one block -> the element every part starts at; off[K] is the size of the block.
 template <int K>
@@ -527,6 +535,12 @@ class EngineBase {
   virtual altro_status TeamRadius(const double* radius_per_instance) = 0;
   virtual altro_status TeamFill(int A, int index, int mode, double blend) = 0;
   virtual altro_status TeamClearance(int A, int index, double* clear, int on_device) = 0;
+  // closed-loop covariance (include/altro_covariance.h): CovPropagate changes nothing on the engine; CovInflate writes the
+  // per-instance track of knot circle constraint `index` (base [rows][np] or [B][rows][np], rpos [B][N + 1]) and leaves the
+  // window offset alone.  Host arrays, or (on_device) memory of the engine's device.
+  virtual altro_status CovPropagate(const CovArgs& call, int on_device) = 0;
+  virtual altro_status CovInflate(int index, const double* base, int rows, int per_instance, double kappa, const double* rpos,
+                                  int on_device) = 0;
   virtual const char* LastError() = 0;
 };
 

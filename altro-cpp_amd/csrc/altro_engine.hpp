@@ -1084,6 +1084,121 @@ class Engine final : public EngineBase {
     return ALTRO_OK;
   }
 
+  // ---- closed-loop covariance (include/altro_covariance.h) ------------------------------------------
+  // k_cov_linearise over (instance, knot) into the engine's scratch F | Kw ([steps][n n][Bp], [steps][m n][Bp]), then
+  // k_cov_recur along the knots.  Host arrays are staged through ONE device block that lives for the call, as MpcTrack does;
+  // device arrays are used where they are.  Reads the engine's arrays only: no flag of the engine changes.
+  altro_status LaunchCov(const CovArgs& g) {
+    const size_t nf = (size_t)g.steps * n * n * Bp_, nk = (size_t)g.steps * m * n * Bp_;
+    if (nf + nk > cov_f_.count() && cov_f_.alloc(nf + nk) != hipSuccess) {
+      err_ = "altro_cov_propagate: out of device memory for " + std::to_string((nf + nk) * sizeof(double)) + " bytes of linearisations";
+      return ALTRO_HIP_ERROR;
+    }
+    double *F = cov_f_.get(), *Kw = F + nf;
+    hipLaunchKernelGGL((k_cov_linearise<T, M>), dim3((B_ + kBlock - 1) / kBlock, g.steps), dim3(kBlock), 0, stream_, A_, d_pd_, F, Kw);
+    constexpr int per_block = n <= kCovMaxN ? kBlock / cov_group(n <= kCovMaxN ? n : 1) : 1;
+    hipLaunchKernelGGL((k_cov_recur<n, m>), dim3((B_ + per_block - 1) / per_block), dim3(kBlock), 0, stream_, g, (const double*)F,
+                       (const double*)Kw, B_, (unsigned)Bp_);
+    return ALTRO_OK;
+  }
+  altro_status CovPropagate(const CovArgs& call, int on_device) override {
+    if (call.steps < 1 || call.steps > N_ || (call.w_mode & ~3) || (!call.Sigma && !call.sx && !call.su && !call.rpos) ||
+        (call.rpos && n < 2)) {
+      err_ = "altro_cov_propagate: steps must lie in [1, N], w_mode in 0..3, an output is required, and rpos needs two states";
+      return ALTRO_INVALID_ARG;
+    }
+    if (n > kCovMaxN) {
+      err_ = "altro_cov_propagate: models of more than " + std::to_string(kCovMaxN) + " states are not supported";
+      return ALTRO_UNSUPPORTED;
+    }
+    if (!StepOk()) return ALTRO_NOT_READY;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    if (on_device) {
+      ALTRO_TRY(LaunchCov(call));
+      return Sync();
+    }
+    const size_t B = (size_t)B_, st = (size_t)call.steps, nn = (size_t)n * n;
+    const Parts<6> p{call.Sigma0 ? (call.sigma0_per_instance ? B : 1) * nn : 0,
+                     call.W ? ((call.w_mode & 1) ? B : 1) * ((call.w_mode & 2) ? st : 1) * nn : 0,
+                     call.Sigma ? B * (st + 1) * nn : 0,
+                     call.sx ? B * (st + 1) * n : 0,
+                     call.su ? B * st * m : 0,
+                     call.rpos ? B * (st + 1) : 0};
+    DevBlock<double> stage;
+    if (stage.alloc(p.total()) != hipSuccess) {
+      err_ = "altro_cov_propagate: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
+      return ALTRO_HIP_ERROR;
+    }
+    double* const blk = stage.get();
+    const size_t *cnt = p.cnt, *off = p.off;
+    CovArgs g = call;
+    hipError_t e = hipSuccess;
+    auto up = [&](const double* src, int i) {
+      if (src && e == hipSuccess) e = hipMemcpyAsync(blk + off[i], src, cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream_);
+      return src ? blk + off[i] : nullptr;
+    };
+    g.Sigma0 = up(call.Sigma0, 0);
+    g.W = up(call.W, 1);
+    g.Sigma = call.Sigma ? blk + off[2] : nullptr;
+    g.sx = call.sx ? blk + off[3] : nullptr;
+    g.su = call.su ? blk + off[4] : nullptr;
+    g.rpos = call.rpos ? blk + off[5] : nullptr;
+    altro_status s = ALTRO_OK;
+    if (e == hipSuccess) s = LaunchCov(g);
+    if (s == ALTRO_OK) {
+      if (e == hipSuccess) e = hipGetLastError();
+      auto down = [&](double* dst, const double* src, int i) {
+        if (dst && cnt[i] && e == hipSuccess) e = hipMemcpyAsync(dst, src, cnt[i] * sizeof(double), hipMemcpyDeviceToHost, stream_);
+      };
+      down(call.Sigma, g.Sigma, 2);
+      down(call.sx, g.sx, 3);
+      down(call.su, g.su, 4);
+      down(call.rpos, g.rpos, 5);
+    }
+    const hipError_t es = hipStreamSynchronize(stream_);  // (also after a failure: the block must not go under a copy in flight)
+    ALTRO_TRY(s);
+    ALTRO_HIP_CHECK(e);
+    ALTRO_HIP_CHECK(es);
+    return ALTRO_OK;
+  }
+  // the routine of TeamFill: write the constraint's spare buffer, then swap; the track is an ordinary one afterwards (base 0)
+  altro_status CovInflate(int index, const double* base, int rows, int per_instance, double kappa, const double* rpos,
+                          int on_device) override {
+    KnotCon* c = FindKnotCon(index, "altro_cov_inflate_circles");
+    if (!c) return ALTRO_INVALID_ARG;
+    if (c->kind != ALTRO_CON_CIRCLE || c->np % 3 != 0 || !base || !rpos || rows < 1 || !(kappa >= 0.0) || !std::isfinite(kappa)) {
+      err_ = "altro_cov_inflate_circles: a knot circle constraint, a base track of at least one row, rpos and a finite kappa >= 0";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(Sync());
+    const size_t nb = (size_t)(per_instance ? B_ : 1) * rows * c->np, nr = (size_t)B_ * (N_ + 1), need = (size_t)B_ * rows * c->np;
+    DevBlock<double> stage;  // (goes behind the synchronisation at the end)
+    if (!on_device) {
+      if (stage.alloc(nb + nr) != hipSuccess) {
+        err_ = "altro_cov_inflate_circles: out of device memory for " + std::to_string((nb + nr) * sizeof(double)) + " bytes of staged arrays";
+        return ALTRO_HIP_ERROR;
+      }
+      ALTRO_HIP_CHECK(CopySync(stage.get(), base, nb * sizeof(double), hipMemcpyHostToDevice));
+      ALTRO_HIP_CHECK(CopySync(stage.get() + nb, rpos, nr * sizeof(double), hipMemcpyHostToDevice));
+      base = stage.get();
+      rpos = stage.get() + nb;
+    }
+    if (need > c->spare.count()) ALTRO_HIP_CHECK(c->spare.alloc(need));
+    ctg_replayable_ = false;  // (as SetConstraintTrack)
+    const int nobs = c->np / 3;
+    const size_t total = (size_t)B_ * rows * nobs;
+    hipLaunchKernelGGL((k_cov_inflate<0>), dim3((unsigned)((total + kTeamThreads - 1) / kTeamThreads)), dim3(kTeamThreads), 0, stream_,
+                       c->spare.get(), base, rpos, B_, rows, nobs, per_instance ? B_ : 1, track_offset_, N_, kappa);
+    std::swap(c->track, c->spare);
+    c->rows = rows;
+    c->cols = B_;
+    c->base = 0;
+    c->team = false;
+    LaunchKnotParams();
+    return Sync();
+  }
+
   // ---- closed-loop tracking (include/altro_mpc.h) ---------------------------------------------------
   // One launch of k_mpc_track, one lane per (instance, sample).  Host arrays are staged through ONE device block that lives
   // for the call; device arrays are used where they are.  Reads the engine's arrays only: no flag of the engine changes.
@@ -3016,6 +3131,7 @@ class Engine final : public EngineBase {
   std::map<int, int*> mpc_maps_;                       // shift -> device row map of the advance (owned through allocs_)
   LoopRun run_;                 // the closed-loop run in progress (LoopBegin .. LoopEnd)
   DevBlock<int> ms_win_;        // winners of the last multi-start call, [B] (MsCheck)
+  DevBlock<double> cov_f_;      // covariance: F | Kw of the last propagation, [steps][n n + m n][Bp] (LaunchCov)
   DevBlock<double> team_rad_;   // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
   std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;

@@ -5858,4 +5858,204 @@ ALTRO_DEV void mpc_track_kernel(const DevArrays<T>& A, const ProblemDesc* __rest
   g.stats[lane] = st;
 }
 
+// -------------------------------------------------------------------------------------------------
+// Closed-loop covariance (include/altro_covariance.h): Sigma_{k+1} = F_k Sigma_k F_k^T + W_k with F_k = A_k + B_k K_k along
+// the plan and the gains the handle holds, and the circle tracks inflated by the position spread.  Everything in fp64; the
+// kernels read the handle's arrays and write only the engine's scratch, the caller's arrays and a constraint's spare track.
+//
+// k_cov_linearise  ONE LANE PER (instance, knot), knot = blockIdx.y < steps: loads Xbar_k, Ubar_k and the gain record (an
+//                  fp32 record widened, as k_mpc_track reads it), evaluates the very discrete_jacobian of expansion_body with
+//                  step_of / time_of / model_of, forms F = A + B K and stores it ROW-MAJOR with the INSTANCE FASTEST:
+//                  F[(k * n * n + i * n + j) * Bp + b], so the 64 lanes of a wave store 512 contiguous bytes per element.
+//                  Where m > 0 the widened gains go beside it the same way, Kw[(k * m * n + c * n + j) * Bp + b] (what su
+//                  needs).  No serial dependence; this is where the arithmetic is.
+// k_cov_recur      serial over the knots.  An instance is spread over a GROUP of G = 2^ceil(log2 n) adjacent lanes of one
+//                  wave (64 / G instances per one-wave workgroup), lane i holding ROW i of Sigma in registers -- by symmetry
+//                  also column i.  Per knot: y = row i of Sigma F^T (F from LDS, the same address for the lanes of a group);
+//                  the rows go to LDS and come back as columns c = (Sigma F^T)[:, i]; v[j] = sum_l F[j][l] c[l] + W[j][i] is
+//                  COLUMN i of the new Sigma; the columns go to LDS, and lane i takes element (i, l) from the lane that
+//                  owns the LOWER-triangle entry (row >= column), which makes the result symmetric bit for bit.  F of the
+//                  NEXT knot is requested from memory at the top of the step (n * n / G elements per lane) and moved to the
+//                  other half of a double LDS buffer at its end, as k_mpc_track does with its records.  Only the lower
+//                  triangles of Sigma0 and W are read.  Every register array is indexed by unrolled constants only (a
+//                  lane's own index selects through compares or through an LDS / memory address): no scratch.
+//                  Lanes of a group beyond n and groups beyond B run along with clamped indices and store nothing.
+// k_cov_inflate    one lane per (instance, row, circle) of the track, in the order of `out`.
+// -------------------------------------------------------------------------------------------------
+constexpr int kCovMaxN = 32;  // a group is at most half a wave, and the double F buffer stays within 32 KiB of LDS
+constexpr int cov_group(int n) {
+  int G = 1;
+  while (G < n) G *= 2;
+  return G;
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_cov_linearise(DevArrays<T> A, const ProblemDesc* __restrict__ pd, double* __restrict__ F,
+                                                          double* __restrict__ Kw) {
+  constexpr int n = M::n, m = M::m;
+  using R = Rec<T, n, m>;
+  using RS = rec_scalar_t<T, M>;
+  using RR = Rec<RS, n, m>;
+  const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
+  if (b >= A.B) return;
+  const unsigned Bp = A.Bp;
+  T x[R::nP], u[R::mP];
+  RS kd[RR::KP];
+  load_rec<T, R::nP>(RECP(A.X, k, R::nP), x);
+  load_rec<T, R::mP>(RECP(A.U, k, R::mP), u);
+  load_rec<RS, RR::KP>(RECP((const RS*)A.KD, k, RR::KP), kd);
+  T J[n * (n + m)];
+#pragma unroll
+  for (int e = 0; e < n * (n + m); ++e) J[e] = T(0);
+  discrete_jacobian<T, M>(x, u, step_of(A, pd, k), J, time_of(A, k), model_of(A, k));
+  double* const Fk = F + (size_t)k * (size_t)(n * n) * Bp + (unsigned)b;
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double f = (double)J[i + j * n];
+#pragma unroll
+      for (int c = 0; c < m; ++c) f += (double)J[n * n + i + c * n] * (double)kd[RR::oK + c + j * m];
+      Fk[(size_t)(i * n + j) * Bp] = f;
+    }
+  if constexpr (m > 0) {
+    double* const Kk = Kw + (size_t)k * (size_t)(m * n) * Bp + (unsigned)b;
+#pragma unroll
+    for (int c = 0; c < m; ++c)
+#pragma unroll
+      for (int j = 0; j < n; ++j) Kk[(size_t)(c * n + j) * Bp] = (double)kd[RR::oK + c + j * m];
+  }
+}
+
+template <int n, int m>
+__global__ __launch_bounds__(kBlock) void k_cov_recur(CovArgs g, const double* __restrict__ F, const double* __restrict__ Kw, int B,
+                                                      unsigned Bp) {
+  if constexpr (n <= kCovMaxN) {
+    constexpr int G = cov_group(n), IPB = kBlock / G, NS = n | 1, FE = (n * n + G - 1) / G;
+    __shared__ double sF[2][IPB][n * n];
+    __shared__ double sX[IPB][G][NS];
+    const int grp = threadIdx.x / G, i_raw = threadIdx.x % G, b_raw = blockIdx.x * IPB + grp;
+    const bool live = b_raw < B && i_raw < n;
+    const int b = b_raw < B ? b_raw : B - 1, i = i_raw < n ? i_raw : n - 1;
+    const int steps = g.steps;
+    const size_t row0 = (size_t)b * (size_t)(steps + 1);
+    const double* const Fb = F + (unsigned)b;
+    double fn[FE], s[n];
+#pragma unroll
+    for (int t = 0; t < FE; ++t) {
+      const int e = i_raw + G * t;
+      if (e < n * n) sF[0][grp][e] = Fb[(size_t)e * Bp];
+    }
+#pragma unroll
+    for (int l = 0; l < n; ++l) {
+      const int r = i > l ? i : l, c = i > l ? l : i;
+      s[l] = g.Sigma0 ? g.Sigma0[(g.sigma0_per_instance ? (size_t)b * (n * n) : 0) + (size_t)(r * n + c)] : 0.0;
+    }
+    const double* const Wb = g.W ? g.W + ((g.w_mode & 1) ? (size_t)b * (size_t)((g.w_mode & 2) ? steps : 1) * (n * n) : 0) : nullptr;
+    __syncthreads();
+    int cur = 0;
+    for (int k = 0;; ++k) {
+      const bool prefetch = k + 1 < steps;
+      if (prefetch) {
+#pragma unroll
+        for (int t = 0; t < FE; ++t) {
+          const int e = i_raw + G * t;
+          fn[t] = e < n * n ? Fb[((size_t)(k + 1) * (n * n) + (size_t)e) * Bp] : 0.0;
+        }
+      }
+      // what knot k hands out
+      if (live && g.Sigma) {
+        double* const dst = g.Sigma + ((row0 + k) * n + i) * n;
+#pragma unroll
+        for (int l = 0; l < n; ++l) dst[l] = s[l];
+      }
+      if (g.sx) {
+        double d = s[0];
+#pragma unroll
+        for (int l = 1; l < n; ++l) d = l == i ? s[l] : d;
+        if (live) g.sx[(row0 + k) * n + i] = d < 0.0 ? 0.0 : __builtin_sqrt(d);
+      }
+      if constexpr (n >= 2) {
+        if (g.rpos) {  // the larger eigenvalue of [a bb; bb c], on the group's first lane (its row 0 holds a and bb)
+          const double c = __shfl(s[1], grp * G + 1);
+          const double a = s[0], bb = s[1], hm = (a + c) / 2, hd = (a - c) / 2, lam = hm + __builtin_sqrt(hd * hd + bb * bb);
+          if (live && i_raw == 0) g.rpos[row0 + k] = lam < 0.0 ? 0.0 : __builtin_sqrt(lam);
+        }
+      }
+      if (k >= steps) break;
+      if constexpr (m > 0) {
+        if (g.su) {  // diag(K Sigma K^T): lane i adds K[c][i] (Sigma K^T)[i][c], summed over the group
+          const double* const Kk = Kw + (size_t)k * (size_t)(m * n) * Bp + (unsigned)b;
+#pragma unroll
+          for (int c = 0; c < m; ++c) {
+            double t = 0.0;
+#pragma unroll
+            for (int l = 0; l < n; ++l) t += s[l] * Kk[(size_t)(c * n + l) * Bp];
+            double p = i_raw < n ? Kk[(size_t)(c * n + i) * Bp] * t : 0.0;
+#pragma unroll
+            for (int sh = G / 2; sh >= 1; sh >>= 1) p += __shfl_xor(p, sh);
+            if (live && i_raw == 0) g.su[((size_t)b * steps + k) * m + c] = p < 0.0 ? 0.0 : __builtin_sqrt(p);
+          }
+        }
+      }
+      // row i of Sigma F^T, handed over as column i
+      const double* const Fc = sF[cur][grp];
+      double col[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; ++l) acc += s[l] * Fc[j * n + l];
+        sX[grp][i_raw][j] = acc;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int l = 0; l < n; ++l) col[l] = sX[grp][l][i];
+      __syncthreads();
+      // column i of F (Sigma F^T) + W; W by its lower triangle
+      const double* const Wk = Wb ? Wb + ((g.w_mode & 2) ? (size_t)k * (n * n) : 0) : nullptr;
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; ++l) acc += Fc[j * n + l] * col[l];
+        const int r = i > j ? i : j, c = i > j ? j : i;
+        if (Wk) acc += Wk[r * n + c];
+        sX[grp][i_raw][j] = acc;
+      }
+      if (prefetch) {
+#pragma unroll
+        for (int t = 0; t < FE; ++t) {
+          const int e = i_raw + G * t;
+          if (e < n * n) sF[cur ^ 1][grp][e] = fn[t];
+        }
+      }
+      __syncthreads();
+      // element (i, l) from the lane that owns its lower-triangle twin
+#pragma unroll
+      for (int l = 0; l < n; ++l) s[l] = l <= i ? sX[grp][l][i] : sX[grp][i][l];
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+}
+
+// out[(b * rows + r) * np + 3 i + (cx | cy | radius)]: centre from `base` ([rows][np], or [B][rows][np] with cols > 1), radius
+// = base radius + kappa * rpos[b][min(max(r - offset, 0), N)].  (A template, as k_knot_params: one definition per program.)
+template <int>
+__global__ __launch_bounds__(kTeamThreads) void k_cov_inflate(double* __restrict__ out, const double* __restrict__ base,
+                                                              const double* __restrict__ rpos, int B, int rows, int nobs, int cols,
+                                                              int offset, int N, double kappa) {
+  const size_t per_col = (size_t)rows * (size_t)nobs, total = (size_t)B * per_col;
+  const size_t i = (size_t)blockIdx.x * kTeamThreads + threadIdx.x;
+  if (i >= total) return;
+  const size_t b = i / per_col, rem = i - b * per_col;
+  const int r = (int)(rem / (size_t)nobs);
+  const int at = r - offset < 0 ? 0 : (r - offset > N ? N : r - offset);
+  const double* src = base + 3 * (cols > 1 ? i : rem);
+  double* dst = out + 3 * i;
+  dst[0] = src[0];
+  dst[1] = src[1];
+  dst[2] = src[2] + kappa * rpos[b * (size_t)(N + 1) + (size_t)at];
+}
+
 }  // namespace altro_hip

@@ -40,6 +40,7 @@
 #include "../altro_knot_params.h"
 #include "../altro_multistart.h"
 #include "../altro_team.h"
+#include "../altro_covariance.h"
 
 namespace altro {
 
@@ -1541,6 +1542,24 @@ class AugmentedLagrangianiLQR {
                        double* X_cl, double* U_cl, altro_track_stats* stats = nullptr) {
     ilqr_solver_.PushOptions();
     detail::Check(Handle(), altro_mpc_track(Handle(), steps, samples, dx0, w, u_lo, u_hi, X_cl, U_cl, stats), "altro_mpc_track");
+  }
+  // The closed-loop covariance of the solved plan under its gains (include/altro_covariance.h), ON THE DEVICE: what a caller
+  // of the reference composes on the host from GetFeedbackGain() and the knots' dynamics Jacobians,
+  // Sigma_{k+1} = (A_k + B_k K_k) Sigma_k (A_k + B_k K_k)^T + W_k.  Sigma0 [n][n] or [B][n][n], W as w_mode says
+  // (ALTRO_COV_W_PER_INSTANCE | ALTRO_COV_W_PER_KNOT), Sigma [B][steps+1][n][n], sx [B][steps+1][n], su [B][steps][m],
+  // rpos [B][steps+1]; each may be null, not all outputs.  Changes nothing on the solver.  A thin call giving the C call's bits.
+  void PropagateCovariance(int steps, const double* Sigma0, bool sigma0_per_instance, const double* W, int w_mode, double* Sigma,
+                           double* sx = nullptr, double* su = nullptr, double* rpos = nullptr) {
+    ilqr_solver_.PushOptions();
+    detail::Check(Handle(), altro_cov_propagate(Handle(), steps, Sigma0, sigma0_per_instance ? 1 : 0, W, w_mode, Sigma, sx, su, rpos),
+                  "altro_cov_propagate");
+  }
+  // ... and the track of knot circle constraint `index` written from it: the centres of `base` ([rows][3 nobs], or
+  // [B][rows][3 nobs]), the radii plus kappa * rpos of the knot the row stands for; rpos [B][N+1]
+  void InflateCircleTrack(int index, const double* base, int rows, bool per_instance, double kappa, const double* rpos) {
+    ilqr_solver_.Push();
+    detail::Check(Handle(), altro_cov_inflate_circles(Handle(), index, base, rows, per_instance ? 1 : 0, kappa, rpos),
+                  "altro_cov_inflate_circles");
   }
   // al_solver.hpp:287-302: duals and penalties reset as the options say, statistics reset, "viol" and "pen" logged
   void Init() {
