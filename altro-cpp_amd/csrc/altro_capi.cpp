@@ -397,8 +397,8 @@ altro_status altro_register_model_source(const char* name, const char* source, i
     inc = slash == std::string::npos ? "." : inc.substr(0, slash);
   }
   std::string hdrs;
-  for (const char* f : {"altro_common.hpp", "altro_problem.hpp", "altro_device.hpp", "altro_kernels.hpp", "altro_engine.hpp", "altro_user_model.hpp",
-                        "../../include/altro_hip.h"}) {
+  for (const char* f : {"altro_common.hpp", "altro_devmem.hpp", "altro_problem.hpp", "altro_device.hpp", "altro_kernels.hpp", "altro_engine.hpp",
+                        "altro_user_model.hpp", "../../include/altro_hip.h"}) {
     std::string txt;
     if (!ReadFile(inc + "/" + f, &txt)) {
       err = std::string("engine header ") + f + " not found in " + inc + " (set ALTRO_HIP_INCLUDE_DIR)";

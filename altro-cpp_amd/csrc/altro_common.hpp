@@ -172,6 +172,31 @@ inline Parts<8> TrackedRunParts(int n, int m, size_t B, size_t cycles, size_t sh
   return {B * (Lk + 1) * n, B * Lk * m, B * (shift + 1) * n, B * shift * m, B * n, B * shift * n, 2 * (size_t)m,
           cycles * B * (sizeof(TrackStats) / sizeof(double))};
 }
+// the block of every other closed-loop run: X log | U log | w [cycles][B][n] | dU (`nd` doubles) | clearances (`nclear`)
+inline Parts<5> PlainRunParts(int n, int m, size_t B, size_t cycles, size_t shift, bool w, size_t nd, size_t nclear) {
+  return {B * (cycles * shift + 1) * n, B * cycles * shift * m, w ? cycles * B * n : 0, nd, nclear};
+}
+// the blocks the other calls stage for a host caller, in doubles; an array the caller leaves out takes no room.
+// Engine::CovPropagate: Sigma0 | W | Sigma | sx | su | rpos
+inline Parts<6> CovStageParts(int n, int m, size_t B, const CovArgs& c) {
+  const size_t st = (size_t)c.steps, nn = (size_t)n * n;
+  return {c.Sigma0 ? (c.sigma0_per_instance ? B : 1) * nn : 0,
+          c.W ? ((c.w_mode & 1) ? B : 1) * ((c.w_mode & 2) ? st : 1) * nn : 0,
+          c.Sigma ? B * (st + 1) * nn : 0,
+          c.sx ? B * (st + 1) * n : 0,
+          c.su ? B * st * m : 0,
+          c.rpos ? B * (st + 1) : 0};
+}
+// Engine::CovInflate: the base track [cols][rows][np] | rpos [B][knots];  Engine::MsPerturb: dU [cols][N][m];
+// Engine::Advance: x0 [B][n] | w [B][n];  Engine::SetReference: Xref | Uref, `points` = rows x columns of the path
+inline Parts<2> InflateStageParts(size_t cols, size_t rows, size_t np, size_t B, size_t knots) { return {cols * rows * np, B * knots}; }
+// Engine::MsGetBest: X [P][N + 1][n] | U [P][N][m] | statistics [P] of `stats_doubles` doubles each
+inline Parts<3> MsBestStageParts(int n, int m, size_t P, size_t N, bool X, bool U, size_t stats_doubles) {
+  return {X ? P * (N + 1) * n : 0, U ? P * N * m : 0, P * stats_doubles};
+}
+inline Parts<1> PerturbStageParts(int m, size_t cols, size_t N) { return {cols * N * m}; }
+inline Parts<2> AdvanceStageParts(int n, size_t B, bool x0, bool w) { return {x0 ? B * n : 0, w ? B * n : 0}; }
+inline Parts<2> ReferenceStageParts(int n, int m, size_t points, bool U) { return {points * n, U ? points * m : 0}; }
 
 // ---- one closed-loop run (altro_mpc_run, altro_mpc_run_tracked, altro_mpc_run_multistart, altro_mpc_run_team) -----------
 // EngineBase::LoopBegin .. LoopEnd: between the two, every LoopCycle (behind the cycle's solve) logs what the loop applies

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "altro_devmem.hpp"
 #include "altro_kernels.hpp"
 #include "altro_problem.hpp"
 
@@ -44,45 +45,6 @@ namespace altro_hip {
     altro_status st_ = (expr);           \
     if (st_ != ALTRO_OK) return st_;     \
   } while (0)
-
-// One hipMalloc block, freed when its owner goes: one pointer, one size, no pooling.  Move-only.  Whoever lets a block go
-// while a copy on the engine's stream may still touch it synchronises that stream first.
-template <class U>
-class DevBlock {
- public:
-  DevBlock() = default;
-  DevBlock(DevBlock&& o) noexcept : p_(o.p_), count_(o.count_) { o.p_ = nullptr, o.count_ = 0; }
-  DevBlock& operator=(DevBlock&& o) noexcept {
-    std::swap(p_, o.p_);
-    std::swap(count_, o.count_);
-    return *this;
-  }
-  ~DevBlock() { reset(); }
-  // `count` elements (at least one is asked for), in place of whatever the block held
-  hipError_t alloc(size_t count) {
-    reset();
-    const hipError_t e = hipMalloc((void**)&p_, std::max<size_t>(count, 1) * sizeof(U));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p_ = nullptr;
-    } else {
-      count_ = count;
-    }
-    return e;
-  }
-  void reset() {
-    if (p_) (void)hipFree(p_);
-    p_ = nullptr;
-    count_ = 0;
-  }
-  U* get() const { return p_; }
-  size_t count() const { return count_; }
-  explicit operator bool() const { return p_ != nullptr; }
-
- private:
-  U* p_ = nullptr;
-  size_t count_ = 0;
-};
 
 // The ALTRO_HIP_* switches of an engine, all read in one place: once, when the engine is constructed
 // (the C API creates the engine at the first upload of a handle).
@@ -224,16 +186,11 @@ class Engine final : public EngineBase {
   // one counter per sweep (device: filled by the forward kernel's atomics; host: pinned + mapped,
   // written by the next sweep's first kernel), so no memset / copy sits between the sweeps
   altro_status ReserveCounters(int count) {
-    if (count <= counter_cap_) return ALTRO_OK;
-    if (d_counter_) hipFree(d_counter_);
-    if (h_counter_) hipHostFree((void*)h_counter_);
-    d_counter_ = nullptr;
-    h_counter_ = nullptr;
-    counter_cap_ = 0;
-    ALTRO_HIP_CHECK(hipHostMalloc((void**)&h_counter_, (size_t)count * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    ALTRO_HIP_CHECK(hipHostGetDevicePointer((void**)&h_counter_dev_, (void*)h_counter_, 0));
-    ALTRO_HIP_CHECK(hipMalloc((void**)&d_counter_, (size_t)count * sizeof(int)));
-    counter_cap_ = count;
+    if ((size_t)count <= hm_.d_counter.count()) return ALTRO_OK;
+    hm_.d_counter.reset();
+    ALTRO_HIP_CHECK(hm_.h_counter.alloc((size_t)count));
+    ALTRO_HIP_CHECK(hipHostGetDevicePointer((void**)&h_counter_dev_, (void*)hm_.h_counter.get(), 0));
+    ALTRO_HIP_CHECK(hm_.d_counter.alloc((size_t)count));
     return ALTRO_OK;
   }
 
@@ -272,7 +229,7 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     ALTRO_TRY(Sync());
     pd_.hstep = hstep;
-    ALTRO_HIP_CHECK(CopySync(d_pd_, &pd_, sizeof(pd_), hipMemcpyHostToDevice));
+    ALTRO_HIP_CHECK(CopySync(up_.d_pd, &pd_, sizeof(pd_), hipMemcpyHostToDevice));
     return ALTRO_OK;
   }
   // Trajectory::SetStep(k, h) / SetTime(k, t) (trajectory.hpp:119-120) and time-varying user models
@@ -309,21 +266,21 @@ class Engine final : public EngineBase {
         err_ = "the integration step of knot " + std::to_string(k) + " is not set (Trajectory::SetStep / SetUniformStep)";
         return ALTRO_NOT_READY;
       }
-    if (!d_hk_) {
-      ALTRO_TRY(Alloc(&d_hk_, (size_t)N_ + 1));
-      ALTRO_TRY(Alloc(&d_tk_, (size_t)N_ + 1));
+    if (!up_.d_hk) {
+      ALTRO_TRY(Alloc(&up_.d_hk, (size_t)N_ + 1));
+      ALTRO_TRY(Alloc(&up_.d_tk, (size_t)N_ + 1));
     }
-    ALTRO_HIP_CHECK(CopySync(d_hk_, hk.data(), hk.size() * sizeof(float), hipMemcpyHostToDevice));
-    ALTRO_HIP_CHECK(CopySync(d_tk_, tk.data(), tk.size() * sizeof(float), hipMemcpyHostToDevice));
-    A_.hk = d_hk_;
-    A_.tk = d_tk_;
+    ALTRO_HIP_CHECK(CopySync(up_.d_hk, hk.data(), hk.size() * sizeof(float), hipMemcpyHostToDevice));
+    ALTRO_HIP_CHECK(CopySync(up_.d_tk, tk.data(), tk.size() * sizeof(float), hipMemcpyHostToDevice));
+    A_.hk = up_.d_hk;
+    A_.tk = up_.d_tk;
     return ALTRO_OK;
   }
   altro_status ResetTrajectory() override {
     ctg_replayable_ = false;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    ALTRO_HIP_CHECK(hipMemcpyAsync(A_.X, X_init_, (size_t)(N_ + 1) * R::nP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
-    ALTRO_HIP_CHECK(hipMemcpyAsync(A_.U, U_init_, (size_t)N_ * R::mP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
+    ALTRO_HIP_CHECK(hipMemcpyAsync(A_.X, up_.X_init, (size_t)(N_ + 1) * R::nP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
+    ALTRO_HIP_CHECK(hipMemcpyAsync(A_.U, up_.U_init, (size_t)N_ * R::mP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
     return ALTRO_OK;
   }
   altro_status ResetStats() override {
@@ -333,13 +290,13 @@ class Engine final : public EngineBase {
   }
   altro_status SetPenalty(double rho) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL(k_set_rows<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_, 0, 1, T(rho));
+    hipLaunchKernelGGL(k_set_rows<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 0, 1, T(rho));
     return Sync();
   }
   altro_status SetPenaltyScaling(double phi) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     std::vector<double> v(kMaxClasses * kMaxConPerKnot, phi);
-    ALTRO_HIP_CHECK(CopySync(d_phi_, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    ALTRO_HIP_CHECK(CopySync(up_.d_phi, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
     return ALTRO_OK;
   }
 
@@ -351,9 +308,9 @@ class Engine final : public EngineBase {
     if (!RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     const DevOpts d = ToDevOpts(o);
-    hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, d_pd_, d);
+    hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, up_.d_pd, d);
     LaunchKnotCosts();
-    hipLaunchKernelGGL(k_log_viol_pen<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_);
+    hipLaunchKernelGGL(k_log_viol_pen<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd);
     return Sync();
   }
   altro_status SolveSetup(const altro_options& o) override {
@@ -364,16 +321,16 @@ class Engine final : public EngineBase {
   altro_status Rollout(const altro_options&) override {
     if (!StepOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL((k_rollout<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, d_pd_, 1);
+    hipLaunchKernelGGL((k_rollout<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1);
     return Sync();
   }
   altro_status Cost(const altro_options&, double* J) override {
     if (!RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     LaunchKnotCosts();
-    hipLaunchKernelGGL(k_sum_costs<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_tmp_);
+    hipLaunchKernelGGL(k_sum_costs<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_tmp);
     ALTRO_TRY(Sync());
-    if (J) return DownloadVec(d_tmp_, J);
+    if (J) return DownloadVec(up_.d_tmp, J);
     return ALTRO_OK;
   }
   altro_status UpdateExpansions(const altro_options&) override {
@@ -381,9 +338,9 @@ class Engine final : public EngineBase {
     if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     if (KnotRouted(A_))
-      hipLaunchKernelGGL((k_expansions_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
+      hipLaunchKernelGGL((k_expansions_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1, (int*)nullptr, (int*)nullptr);
     else
-      hipLaunchKernelGGL((k_expansions<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, 1, (int*)nullptr, (int*)nullptr);
+      hipLaunchKernelGGL((k_expansions<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1, (int*)nullptr, (int*)nullptr);
     return Sync();
   }
   altro_status BackwardPass(const altro_options& o) override {
@@ -398,17 +355,17 @@ class Engine final : public EngineBase {
   altro_status ReplayCtg() {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     ALTRO_TRY(Sync());
-    double* tmpT = nullptr;
-    int* tmpI = nullptr;
+    // the per-instance scalars as the solve left them (both blocks go behind the synchronisation below)
+    DevBlock<double> tmpT;
+    DevBlock<int> tmpI;
     const size_t nT = (size_t)kNumScalarT * Bp_ * sizeof(double), nI = (size_t)kNumScalarI * Bp_ * sizeof(int);
-    ALTRO_HIP_CHECK(hipMalloc((void**)&tmpT, nT));
-    if (hipMalloc((void**)&tmpI, nI) != hipSuccess) {
-      hipFree(tmpT);
+    ALTRO_HIP_CHECK(tmpT.alloc((size_t)kNumScalarT * Bp_));
+    if (tmpI.alloc((size_t)kNumScalarI * Bp_) != hipSuccess) {
       err_ = "ReplayCtg: out of device memory";
       return ALTRO_HIP_ERROR;
     }
-    hipError_t e = hipMemcpyAsync(tmpT, d_scalarT_, nT, hipMemcpyDeviceToDevice, stream_);
-    if (e == hipSuccess) e = hipMemcpyAsync(tmpI, d_scalarI_, nI, hipMemcpyDeviceToDevice, stream_);
+    hipError_t e = hipMemcpyAsync(tmpT.get(), up_.d_scalarT, nT, hipMemcpyDeviceToDevice, stream_);
+    if (e == hipSuccess) e = hipMemcpyAsync(tmpI.get(), up_.d_scalarI, nI, hipMemcpyDeviceToDevice, stream_);
     // the regularisation the last backward pass used (stats_.Log("reg", rho_)) is what this one starts from
     if (e == hipSuccess) e = hipMemcpyAsync(A_.rho_reg, A_.reg_log, (size_t)Bp_ * sizeof(double), hipMemcpyDeviceToDevice, stream_);
     if (e == hipSuccess) {
@@ -418,12 +375,11 @@ class Engine final : public EngineBase {
       LaunchBackward(A, last_opts_, 1, B_);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(d_scalarT_, tmpT, nT, hipMemcpyDeviceToDevice, stream_);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_scalarI_, tmpI, nI, hipMemcpyDeviceToDevice, stream_);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    hipFree(tmpT);
-    hipFree(tmpI);
+    if (e == hipSuccess) e = hipMemcpyAsync(up_.d_scalarT, tmpT.get(), nT, hipMemcpyDeviceToDevice, stream_);
+    if (e == hipSuccess) e = hipMemcpyAsync(up_.d_scalarI, tmpI.get(), nI, hipMemcpyDeviceToDevice, stream_);
+    const hipError_t es = hipStreamSynchronize(stream_);  // (also after a failure: the blocks must not go under a copy in flight)
     ALTRO_HIP_CHECK(e);
+    ALTRO_HIP_CHECK(es);
     ctg_fresh_ = true;
     return ALTRO_OK;
   }
@@ -437,26 +393,26 @@ class Engine final : public EngineBase {
   }
   altro_status UpdateConvergenceStatistics(const altro_options& o) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL((k_conv_stats<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, d_pd_, ToDevOpts(o));
+    hipLaunchKernelGGL((k_conv_stats<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, ToDevOpts(o));
     return Sync();
   }
   altro_status UpdateDuals(const altro_options&) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL(k_update_duals<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_);
+    hipLaunchKernelGGL(k_update_duals<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd);
     return Sync();
   }
   altro_status UpdatePenalties(const altro_options&) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL(k_update_penalties<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_);
+    hipLaunchKernelGGL(k_update_penalties<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd);
     return Sync();
   }
-  altro_status GetMaxViolation(double* out) override { return MaxViolPen(d_tmp_, nullptr, out); }
-  altro_status GetMaxPenalty(double* out) override { return MaxViolPen(nullptr, d_tmp_, out); }
-  altro_status MaxViolPen(double* viol, double* pen, double* out) {  // (one of the two is d_tmp_, the other null)
+  altro_status GetMaxViolation(double* out) override { return MaxViolPen(up_.d_tmp, nullptr, out); }
+  altro_status GetMaxPenalty(double* out) override { return MaxViolPen(nullptr, up_.d_tmp, out); }
+  altro_status MaxViolPen(double* viol, double* pen, double* out) {  // (one of the two is up_.d_tmp, the other null)
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    hipLaunchKernelGGL(k_max_viol_pen<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_, viol, pen);
+    hipLaunchKernelGGL(k_max_viol_pen<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, viol, pen);
     ALTRO_TRY(Sync());
-    return DownloadVec(d_tmp_, out);
+    return DownloadVec(up_.d_tmp, out);
   }
 
   // ---- results ----------------------------------------------------------------------------------
@@ -537,10 +493,10 @@ class Engine final : public EngineBase {
     ALTRO_TRY(Sync());
     std::vector<double> f((size_t)kNumScalarT * Bp_);
     std::vector<int> iv((size_t)kNumScalarI * Bp_);
-    ALTRO_HIP_CHECK(CopySync(f.data(), d_scalarT_, f.size() * sizeof(double), hipMemcpyDeviceToHost));
-    ALTRO_HIP_CHECK(CopySync(iv.data(), d_scalarI_, iv.size() * sizeof(int), hipMemcpyDeviceToHost));
-    auto F = [&](double* p, int b) { return f[(size_t)(p - d_scalarT_) + b]; };
-    auto I = [&](int* p, int b) { return iv[(size_t)(p - d_scalarI_) + b]; };
+    ALTRO_HIP_CHECK(CopySync(f.data(), up_.d_scalarT, f.size() * sizeof(double), hipMemcpyDeviceToHost));
+    ALTRO_HIP_CHECK(CopySync(iv.data(), up_.d_scalarI, iv.size() * sizeof(int), hipMemcpyDeviceToHost));
+    auto F = [&](double* p, int b) { return f[(size_t)(p - up_.d_scalarT) + b]; };
+    auto I = [&](int* p, int b) { return iv[(size_t)(p - up_.d_scalarI) + b]; };
     for (int b = 0; b < B_; ++b) {
       altro_stats& s = st[b];
       s.status_ilqr = I(A_.status, b);
@@ -576,17 +532,17 @@ class Engine final : public EngineBase {
   }
   altro_status SetRecordHistory(int capacity) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (A_.hist) {
-      hipFree(A_.hist);
-      hipFree(A_.hist_len);
-      A_.hist = nullptr;
-      A_.hist_len = nullptr;
-    }
+    hm_.hist.reset();
+    hm_.hist_len.reset();
+    A_.hist = nullptr;
+    A_.hist_len = nullptr;
     A_.hist_cap = 0;
     if (capacity > 0) {
-      ALTRO_HIP_CHECK(hipMalloc((void**)&A_.hist, (size_t)kHistFields * capacity * Bp_ * sizeof(double)));
-      ALTRO_HIP_CHECK(hipMalloc((void**)&A_.hist_len, (size_t)Bp_ * sizeof(int)));
-      ALTRO_HIP_CHECK(ZeroSync(A_.hist_len, 0, (size_t)Bp_ * sizeof(int)));
+      ALTRO_HIP_CHECK(hm_.hist.alloc((size_t)kHistFields * capacity * Bp_));
+      ALTRO_HIP_CHECK(hm_.hist_len.alloc((size_t)Bp_));
+      ALTRO_HIP_CHECK(ZeroSync(hm_.hist_len.get(), 0, (size_t)Bp_ * sizeof(int)));
+      A_.hist = hm_.hist.get();
+      A_.hist_len = hm_.hist_len.get();
       A_.hist_cap = capacity;
     }
     return ALTRO_OK;
@@ -651,7 +607,7 @@ class Engine final : public EngineBase {
   }
 
   // ---- the reference path of the tracking costs (include/altro_tracking.h: altro_set_reference) ---------------------
-  // The path lives on the device (d_refpath_, one column or B of them); every change of path or window ends in ONE launch
+  // The path lives on the device (Uploaded::refpath, one column or B of them); every change of path or window ends in ONE launch
   // of k_ref_terms on the engine's stream, which rewrites the term records the cost kernels read (DevArrays::ref).  A handle
   // without a tracking cost keeps the path and the offset it is given and launches nothing.
   altro_status SetReference(const double* Xref, const double* Uref, int rows, int per_instance, int on_device) override {
@@ -664,28 +620,19 @@ class Engine final : public EngineBase {
     ctg_replayable_ = false;  // (as SetTrajectory: what a replayed backward pass would read belongs to the old reference)
     const int cols = per_instance ? B_ : 1;
     const size_t need = (size_t)rows * cols * kRefPT;
-    if (need > refpath_cap_) {
-      if (d_refpath_) ALTRO_HIP_CHECK(hipFree(d_refpath_));
-      d_refpath_ = nullptr;
-      refpath_cap_ = 0;
-      ALTRO_HIP_CHECK(hipMalloc((void**)&d_refpath_, need * sizeof(double)));
-      refpath_cap_ = need;
-    }
-    const double *Xd = Xref, *Ud = Uref;
-    if (!on_device) {
-      const size_t nx = (size_t)rows * cols * n, nu = Uref ? (size_t)rows * cols * m : 0;
-      ALTRO_TRY(EnsureStage(nx + nu));
-      ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, Xref, nx * sizeof(double), hipMemcpyHostToDevice, stream_));
-      if (Uref) ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_ + nx, Uref, nu * sizeof(double), hipMemcpyHostToDevice, stream_));
-      Xd = d_stage_;
-      Ud = Uref ? d_stage_ + nx : nullptr;
-    }
-    hipLaunchKernelGGL((k_ref_pack<n, m>), dim3((cols + kBlock - 1) / kBlock, rows), dim3(kBlock), 0, stream_, Xd, Ud, d_refpath_, rows, cols);
-    ref_rows_ = rows;
-    ref_cols_ = cols;
-    ref_offset_ = 0;
+    if (need > up_.refpath.count()) ALTRO_HIP_CHECK(up_.refpath.alloc(need));
+    const Parts<2> p = ReferenceStageParts(n, m, (size_t)rows * cols, Uref != nullptr);
+    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
+    Staged<2> sg(on_device != 0, hm_.stage.get(), p, stream_);
+    const double *Xd = sg.in(0, Xref), *Ud = sg.in(1, Uref);
+    hipLaunchKernelGGL((k_ref_pack<n, m>), dim3((cols + kBlock - 1) / kBlock, rows), dim3(kBlock), 0, stream_, Xd, Ud, up_.refpath.get(), rows,
+                       cols);
+    up_.ref_rows = rows;
+    up_.ref_cols = cols;
+    up_.ref_offset = 0;
     LaunchRefTerms();
-    return Sync();
+    ALTRO_HIP_CHECK(sg.finish());
+    return ALTRO_OK;
   }
   altro_status SetReferenceOffset(int offset) override {
     if (offset < 0) {
@@ -694,11 +641,11 @@ class Engine final : public EngineBase {
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     ctg_replayable_ = false;
-    ref_offset_ = offset;
+    up_.ref_offset = offset;
     LaunchRefTerms();
     return Sync();
   }
-  int GetReferenceOffset() override { return ref_offset_; }
+  int GetReferenceOffset() override { return up_.ref_offset; }
   altro_status GetReferenceTerms(double* q, double* r, double* c) override {
     if (!A_.ref) {  // no tracking cost: every knot reads zero
       const size_t BK = (size_t)B_ * (N_ + 1);
@@ -715,24 +662,24 @@ class Engine final : public EngineBase {
   // the per-knot costs of the step-level calls (k_knot_costs; its twin on a handle with a tracking cost)
   void LaunchKnotCosts() {
     if (KnotRouted(A_))
-      hipLaunchKernelGGL((k_knot_costs_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
+      hipLaunchKernelGGL((k_knot_costs_trk<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, up_.d_pd);
     else
-      hipLaunchKernelGGL((k_knot_costs<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_);
+      hipLaunchKernelGGL((k_knot_costs<T, M>), GridBK(), dim3(kBlock), 0, stream_, A_, up_.d_pd);
   }
   // the term records of the current path and window (nothing to do without a tracking cost or without a path)
   void LaunchRefTerms() {
-    if (!A_.ref || ref_rows_ < 1) return;
-    hipLaunchKernelGGL((k_ref_terms<T, n, m>), GridBK(), dim3(kBlock), 0, stream_, A_, d_pd_, (const double*)d_refpath_, d_ref_, ref_rows_,
-                       ref_cols_, ref_offset_);
+    if (!A_.ref || up_.ref_rows < 1) return;
+    hipLaunchKernelGGL((k_ref_terms<T, n, m>), GridBK(), dim3(kBlock), 0, stream_, A_, up_.d_pd, (const double*)up_.refpath.get(), up_.d_ref, up_.ref_rows,
+                       up_.ref_cols, up_.ref_offset);
   }
   // a cost evaluation on a handle with a tracking cost needs the path
   bool RefOk() {
-    for (const KnotCon& c : kcons_)
+    for (const KnotCon& c : up_.kcons)
       if (c.rows < 1) {
         err_ = "constraint " + std::to_string(c.index) + " is a knot constraint but has no parameter track (altro_set_constraint_track)";
         return false;
       }
-    if (!A_.ref || ref_rows_ > 0) return true;
+    if (!A_.ref || up_.ref_rows > 0) return true;
     err_ = "a knot has a tracking cost but no reference path is set (altro_set_reference)";
     return false;
   }
@@ -755,7 +702,7 @@ class Engine final : public EngineBase {
     DevBlock<double> spare;
   };
   KnotCon* FindKnotCon(int index, const char* who) {
-    for (KnotCon& c : kcons_)
+    for (KnotCon& c : up_.kcons)
       if (c.index == index) return &c;
     err_ = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
     return nullptr;
@@ -791,11 +738,11 @@ class Engine final : public EngineBase {
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     ctg_replayable_ = false;
-    track_offset_ = offset;
+    up_.track_offset = offset;
     LaunchKnotParams();
     return Sync();
   }
-  int GetTrackOffset() override { return track_offset_; }
+  int GetTrackOffset() override { return up_.track_offset; }
   altro_status GetKnotParams(int index, double* out) override {
     KnotCon* c = FindKnotCon(index, "altro_get_knot_params");
     if (!c || !out) return ALTRO_INVALID_ARG;
@@ -805,19 +752,14 @@ class Engine final : public EngineBase {
   void LaunchKnotParams() {
     if (!A_.kpar) return;
     KnotParArgs g{};
-    g.ncon = (int)kcons_.size();
+    g.ncon = (int)up_.kcons.size();
     g.kt = A_.kpar_kt;
-    g.offset = track_offset_;
+    g.offset = up_.track_offset;
     for (int j = 0; j < g.ncon; ++j) {
-      const KnotCon& c = kcons_[j];
+      const KnotCon& c = up_.kcons[j];
       g.c[j] = KnotTrack{c.rows > 0 ? c.track.get() : nullptr, c.k_begin, c.k_end, c.np, c.off, c.rows, c.cols, c.base};
     }
-    hipLaunchKernelGGL((k_knot_params<0>), GridBK(), dim3(kBlock), 0, stream_, g, d_kpar_, B_, Bp_);
-  }
-  void DropKnotCons() {
-    kcons_.clear();
-    d_kpar_ = nullptr;
-    track_offset_ = 0;
+    hipLaunchKernelGGL((k_knot_params<0>), GridBK(), dim3(kBlock), 0, stream_, g, up_.d_kpar, B_, Bp_);
   }
 
   // ---- receding-horizon advance (include/altro_mpc.h) ----------------------------------------------
@@ -863,17 +805,11 @@ class Engine final : public EngineBase {
     g.rows = pd_.total_rows;
     g.row_src = map;
     g.reset_pen = reset_pen;
-    if ((x0 || w) && !on_device) {
-      const size_t cnt = (size_t)B_ * n;
-      ALTRO_TRY(EnsureStage(2 * cnt));
-      if (x0) ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, x0, cnt * sizeof(double), hipMemcpyHostToDevice, stream_));
-      if (w) ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_ + cnt, w, cnt * sizeof(double), hipMemcpyHostToDevice, stream_));
-      g.x0 = x0 ? d_stage_ : nullptr;
-      g.w = w ? d_stage_ + cnt : nullptr;
-    } else {
-      g.x0 = x0;
-      g.w = w;
-    }
+    const Parts<2> p = AdvanceStageParts(n, (size_t)B_, x0 != nullptr, w != nullptr);
+    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
+    Staged<2> sg(on_device != 0, hm_.stage.get(), p, stream_);
+    g.x0 = sg.in(0, x0);
+    g.w = sg.in(1, w);
     if (log) {
       g.Xlog = log->X;
       g.Ulog = log->U;
@@ -884,25 +820,26 @@ class Engine final : public EngineBase {
     }
     hipLaunchKernelGGL(k_mpc_advance<T>, dim3((B_ + g.tile - 1) / g.tile, 5), dim3(kMpcThreads), 0, stream_, A_, g);
     if (A_.ref) {  // the window of a tracking cost's reference moves with the horizon (the end of the path is held)
-      ref_offset_ = (int)std::min<long long>((long long)ref_offset_ + shift, 0x7fffffffLL);
+      up_.ref_offset = (int)std::min<long long>((long long)up_.ref_offset + shift, 0x7fffffffLL);
       LaunchRefTerms();
     }
     if (A_.kpar) {  // ... and so does the window of the knot constraints' tracks (the last row is held)
-      track_offset_ = (int)std::min<long long>((long long)track_offset_ + shift, 0x7fffffffLL);
+      up_.track_offset = (int)std::min<long long>((long long)up_.track_offset + shift, 0x7fffffffLL);
       LaunchKnotParams();
     }
-    return Sync();
+    ALTRO_HIP_CHECK(sg.finish());
+    return ALTRO_OK;
   }
   // ---- multi-start (include/altro_multistart.h) -----------------------------------------------------
   // G adjacent columns are the starts of one problem.  Everything runs on the engine's stream; the winners live in a device
-  // array of the engine (ms_win_) unless the caller brings device memory for them.  The C API has checked G against the batch.
+  // array of the engine (hm_.ms_win) unless the caller brings device memory for them.  The C API has checked G against the batch.
   altro_status MsCheck(int G) {
     if (G < 1 || B_ % G != 0) {
       err_ = "multi-start: starts must be at least 1 and divide the batch";
       return ALTRO_INVALID_ARG;
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (!ms_win_) ALTRO_HIP_CHECK(ms_win_.alloc((size_t)B_));
+    if (!hm_.ms_win) ALTRO_HIP_CHECK(hm_.ms_win.alloc((size_t)B_));
     return ALTRO_OK;
   }
   // k_ms_select into `win` (device, [P]); log: one more copy at log[p * stride + off]
@@ -912,10 +849,10 @@ class Engine final : public EngineBase {
                        stride, off);
   }
   // where the winners of this call go on the device, and their way back to a host caller
-  int* MsWinDev(int* winner, int on_device) { return winner && on_device ? winner : ms_win_.get(); }
+  int* MsWinDev(int* winner, int on_device) { return winner && on_device ? winner : hm_.ms_win.get(); }
   altro_status MsWinOut(int G, int* winner, int on_device) {
     ALTRO_TRY(Sync());
-    if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, ms_win_.get(), (size_t)(B_ / G) * sizeof(int), hipMemcpyDeviceToHost));
+    if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, hm_.ms_win.get(), (size_t)(B_ / G) * sizeof(int), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   }
   altro_status MsSelect(int G, int* winner, int on_device, bool ilqr_mode) override {
@@ -967,30 +904,25 @@ class Engine final : public EngineBase {
       return ALTRO_INVALID_ARG;
     }
     ctg_replayable_ = false;
-    if (!on_device) {
-      const size_t cnt = (size_t)(per_instance ? B_ : G) * N_ * m;
-      ALTRO_TRY(EnsureStage(cnt));
-      ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, dU, cnt * sizeof(double), hipMemcpyHostToDevice, stream_));
-      dU = d_stage_;
-    }
-    LaunchMsPerturb(G, dU, per_instance);
-    return Sync();
+    const Parts<1> p = PerturbStageParts(m, (size_t)(per_instance ? B_ : G), (size_t)N_);
+    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
+    Staged<1> sg(on_device != 0, hm_.stage.get(), p, stream_);
+    LaunchMsPerturb(G, sg.in(0, dU), per_instance);
+    ALTRO_HIP_CHECK(sg.finish());
+    return ALTRO_OK;
   }
   // The winners' trajectories through k_rec_to_rows with the winner as the source column, their statistics through k_ms_stats.
   // A host caller's arrays are staged in ONE device block (X | U | stats) and come back with one copy each.
   altro_status MsGetBest(int G, double* X, double* U, altro_stats* stats, int* winner, int on_device, bool ilqr_mode) override {
     ALTRO_TRY(MsCheck(G));
     const int P = B_ / G;
-    const size_t nx = (size_t)P * (N_ + 1) * n, nu = (size_t)P * N_ * m, ns = (size_t)P * sizeof(altro_stats) / sizeof(double);
     static_assert(sizeof(altro_stats) % sizeof(double) == 0, "altro_stats is a whole number of doubles");
-    double *dX = X, *dU = U;
-    altro_stats* dS = stats;
-    if (!on_device) {
-      ALTRO_TRY(EnsureStage(nx + nu + ns));
-      dX = d_stage_;
-      dU = d_stage_ + nx;
-      dS = reinterpret_cast<altro_stats*>(d_stage_ + nx + nu);
-    }
+    const Parts<3> p = MsBestStageParts(n, m, (size_t)P, (size_t)N_, X != nullptr, U != nullptr,
+                                         stats ? sizeof(altro_stats) / sizeof(double) : 0);
+    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
+    Staged<3> sg(on_device != 0, hm_.stage.get(), p, stream_);
+    double *dX = sg.out(0, X), *dU = sg.out(1, U);
+    altro_stats* dS = sg.out(2, stats);
     int* win = MsWinDev(winner, on_device);
     LaunchMsSelect(G, ilqr_mode, win, nullptr, 0, 0);
     const dim3 gp((P + kBlock - 1) / kBlock);
@@ -1001,12 +933,8 @@ class Engine final : public EngineBase {
       hipLaunchKernelGGL((k_rec_to_rows<T>), dim3(gp.x, N_), dim3(kBlock), 0, stream_, (const T*)A_.U, dU, N_, R::mP, 0, m, P, Bp_,
                          (const int*)win, G);
     if (stats) hipLaunchKernelGGL(k_ms_stats<T>, gp, dim3(kBlock), 0, stream_, A_, (const int*)win, G, P, ilqr_mode ? 1 : 0, dS);
-    ALTRO_TRY(MsWinOut(G, winner, on_device));
-    if (!on_device) {
-      if (X) ALTRO_HIP_CHECK(CopySync(X, dX, nx * sizeof(double), hipMemcpyDeviceToHost));
-      if (U) ALTRO_HIP_CHECK(CopySync(U, dU, nu * sizeof(double), hipMemcpyDeviceToHost));
-      if (stats) ALTRO_HIP_CHECK(CopySync(stats, dS, (size_t)P * sizeof(altro_stats), hipMemcpyDeviceToHost));
-    }
+    ALTRO_HIP_CHECK(sg.finish());  // (the one wait that MsWinOut would start with)
+    if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, hm_.ms_win.get(), (size_t)P * sizeof(int), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   }
 
@@ -1029,14 +957,14 @@ class Engine final : public EngineBase {
   }
   altro_status TeamRadius(const double* radius) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (!team_rad_) ALTRO_HIP_CHECK(team_rad_.alloc(2 * (size_t)B_));  // radii | clearances
-    ALTRO_HIP_CHECK(CopySync(team_rad_.get(), radius, (size_t)B_ * sizeof(double), hipMemcpyHostToDevice));
+    if (!hm_.team_rad) ALTRO_HIP_CHECK(hm_.team_rad.alloc(2 * (size_t)B_));  // radii | clearances
+    ALTRO_HIP_CHECK(CopySync(hm_.team_rad.get(), radius, (size_t)B_ * sizeof(double), hipMemcpyHostToDevice));
     return ALTRO_OK;
   }
   altro_status TeamFill(int A, int index, int mode, double blend) override {
     KnotCon* c = TeamCheck(A, index, "altro_team_fill_tracks");
     if (!c) return ALTRO_INVALID_ARG;
-    if (!team_rad_) {
+    if (!hm_.team_rad) {
       err_ = "altro_team_fill_tracks: no radii on the device yet";
       return ALTRO_NOT_READY;
     }
@@ -1050,34 +978,29 @@ class Engine final : public EngineBase {
     g.out = c->spare.get();
     // a track last written by a team fill has this very shape; any other is replaced, not blended
     g.old = c->team && c->rows == rows && c->cols == B_ && blend != 1.0 ? c->track.get() : nullptr;
-    g.radius = team_rad_.get();
+    g.radius = hm_.team_rad.get();
     g.A = A;
     g.B = B_;
     g.rows = rows;
     g.priority = mode == 1 ? 1 : 0;
-    g.ahead = track_offset_ > c->base ? track_offset_ - c->base : 0;
+    g.ahead = up_.track_offset > c->base ? up_.track_offset - c->base : 0;
     g.blend = blend;
     const size_t total = (size_t)B_ * rows * (A - 1);
     hipLaunchKernelGGL(k_team_tracks<T>, dim3((unsigned)((total + kTeamThreads - 1) / kTeamThreads)), dim3(kTeamThreads), 0, stream_,
                        (const T*)A_.X, R::nP, Bp_, g);
-    std::swap(c->track, c->spare);
-    c->rows = rows;
-    c->cols = B_;
-    c->base = track_offset_;
-    c->team = true;
-    LaunchKnotParams();
+    AdoptSpare(c, rows, up_.track_offset, true);
     return Sync();
   }
   void LaunchTeamClearance(int A, const KnotCon& c, double* clear, int stride, int off) {
     const int teams = B_ / A, per_block = kTeamThreads / 64;
     hipLaunchKernelGGL(k_team_clearance<T>, dim3((teams + per_block - 1) / per_block), dim3(kTeamThreads), 0, stream_, (const T*)A_.X,
-                       R::nP, Bp_, (const double*)team_rad_.get(), A, teams, c.k_begin, c.k_end, clear, stride, off);
+                       R::nP, Bp_, (const double*)hm_.team_rad.get(), A, teams, c.k_begin, c.k_end, clear, stride, off);
   }
   altro_status TeamClearance(int A, int index, double* clear, int on_device) override {
     KnotCon* c = TeamCheck(A, index, "altro_team_clearance");
-    if (!c || !team_rad_ || !clear) return ALTRO_INVALID_ARG;
+    if (!c || !hm_.team_rad || !clear) return ALTRO_INVALID_ARG;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    double* dst = on_device ? clear : team_rad_.get() + B_;
+    double* dst = on_device ? clear : hm_.team_rad.get() + B_;
     LaunchTeamClearance(A, *c, dst, 1, 0);
     ALTRO_TRY(Sync());
     if (!on_device) ALTRO_HIP_CHECK(CopySync(clear, dst, (size_t)(B_ / A) * sizeof(double), hipMemcpyDeviceToHost));
@@ -1090,12 +1013,12 @@ class Engine final : public EngineBase {
   // device arrays are used where they are.  Reads the engine's arrays only: no flag of the engine changes.
   altro_status LaunchCov(const CovArgs& g) {
     const size_t nf = (size_t)g.steps * n * n * Bp_, nk = (size_t)g.steps * m * n * Bp_;
-    if (nf + nk > cov_f_.count() && cov_f_.alloc(nf + nk) != hipSuccess) {
+    if (nf + nk > hm_.cov_f.count() && hm_.cov_f.alloc(nf + nk) != hipSuccess) {
       err_ = "altro_cov_propagate: out of device memory for " + std::to_string((nf + nk) * sizeof(double)) + " bytes of linearisations";
       return ALTRO_HIP_ERROR;
     }
-    double *F = cov_f_.get(), *Kw = F + nf;
-    hipLaunchKernelGGL((k_cov_linearise<T, M>), dim3((B_ + kBlock - 1) / kBlock, g.steps), dim3(kBlock), 0, stream_, A_, d_pd_, F, Kw);
+    double *F = hm_.cov_f.get(), *Kw = F + nf;
+    hipLaunchKernelGGL((k_cov_linearise<T, M>), dim3((B_ + kBlock - 1) / kBlock, g.steps), dim3(kBlock), 0, stream_, A_, up_.d_pd, F, Kw);
     constexpr int per_block = n <= kCovMaxN ? kBlock / cov_group(n <= kCovMaxN ? n : 1) : 1;
     hipLaunchKernelGGL((k_cov_recur<n, m>), dim3((B_ + per_block - 1) / per_block), dim3(kBlock), 0, stream_, g, (const double*)F,
                        (const double*)Kw, B_, (unsigned)Bp_);
@@ -1113,53 +1036,32 @@ class Engine final : public EngineBase {
     }
     if (!StepOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (on_device) {
-      ALTRO_TRY(LaunchCov(call));
-      return Sync();
-    }
-    const size_t B = (size_t)B_, st = (size_t)call.steps, nn = (size_t)n * n;
-    const Parts<6> p{call.Sigma0 ? (call.sigma0_per_instance ? B : 1) * nn : 0,
-                     call.W ? ((call.w_mode & 1) ? B : 1) * ((call.w_mode & 2) ? st : 1) * nn : 0,
-                     call.Sigma ? B * (st + 1) * nn : 0,
-                     call.sx ? B * (st + 1) * n : 0,
-                     call.su ? B * st * m : 0,
-                     call.rpos ? B * (st + 1) : 0};
+    // the staged block of a host caller (CovStageParts); it goes when this call returns, behind the wait of finish()
+    const Parts<6> p = CovStageParts(n, m, (size_t)B_, call);
     DevBlock<double> stage;
-    if (stage.alloc(p.total()) != hipSuccess) {
+    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
       err_ = "altro_cov_propagate: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
       return ALTRO_HIP_ERROR;
     }
-    double* const blk = stage.get();
-    const size_t *cnt = p.cnt, *off = p.off;
+    Staged<6> sg(on_device != 0, stage.get(), p, stream_);
     CovArgs g = call;
-    hipError_t e = hipSuccess;
-    auto up = [&](const double* src, int i) {
-      if (src && e == hipSuccess) e = hipMemcpyAsync(blk + off[i], src, cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream_);
-      return src ? blk + off[i] : nullptr;
-    };
-    g.Sigma0 = up(call.Sigma0, 0);
-    g.W = up(call.W, 1);
-    g.Sigma = call.Sigma ? blk + off[2] : nullptr;
-    g.sx = call.sx ? blk + off[3] : nullptr;
-    g.su = call.su ? blk + off[4] : nullptr;
-    g.rpos = call.rpos ? blk + off[5] : nullptr;
-    altro_status s = ALTRO_OK;
-    if (e == hipSuccess) s = LaunchCov(g);
-    if (s == ALTRO_OK) {
-      if (e == hipSuccess) e = hipGetLastError();
-      auto down = [&](double* dst, const double* src, int i) {
-        if (dst && cnt[i] && e == hipSuccess) e = hipMemcpyAsync(dst, src, cnt[i] * sizeof(double), hipMemcpyDeviceToHost, stream_);
-      };
-      down(call.Sigma, g.Sigma, 2);
-      down(call.sx, g.sx, 3);
-      down(call.su, g.su, 4);
-      down(call.rpos, g.rpos, 5);
-    }
-    const hipError_t es = hipStreamSynchronize(stream_);  // (also after a failure: the block must not go under a copy in flight)
+    g.Sigma0 = sg.in(0, call.Sigma0);
+    g.W = sg.in(1, call.W);
+    g.Sigma = sg.out(2, call.Sigma);
+    g.sx = sg.out(3, call.sx);
+    g.su = sg.out(4, call.su);
+    g.rpos = sg.out(5, call.rpos);
+    const altro_status s = sg.ok() ? LaunchCov(g) : ALTRO_OK;
+    const hipError_t e = sg.finish(s == ALTRO_OK);
     ALTRO_TRY(s);
     ALTRO_HIP_CHECK(e);
-    ALTRO_HIP_CHECK(es);
     return ALTRO_OK;
+  }
+  // the spare buffer a kernel has just been launched to write becomes the constraint's track, one column per instance
+  void AdoptSpare(KnotCon* c, int rows, int base, bool team) {
+    std::swap(c->track, c->spare);
+    c->rows = rows, c->cols = B_, c->base = base, c->team = team;
+    LaunchKnotParams();
   }
   // the routine of TeamFill: write the constraint's spare buffer, then swap; the track is an ordinary one afterwards (base 0)
   altro_status CovInflate(int index, const double* base, int rows, int per_instance, double kappa, const double* rpos,
@@ -1172,31 +1074,25 @@ class Engine final : public EngineBase {
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     ALTRO_TRY(Sync());
-    const size_t nb = (size_t)(per_instance ? B_ : 1) * rows * c->np, nr = (size_t)B_ * (N_ + 1), need = (size_t)B_ * rows * c->np;
-    DevBlock<double> stage;  // (goes behind the synchronisation at the end)
-    if (!on_device) {
-      if (stage.alloc(nb + nr) != hipSuccess) {
-        err_ = "altro_cov_inflate_circles: out of device memory for " + std::to_string((nb + nr) * sizeof(double)) + " bytes of staged arrays";
-        return ALTRO_HIP_ERROR;
-      }
-      ALTRO_HIP_CHECK(CopySync(stage.get(), base, nb * sizeof(double), hipMemcpyHostToDevice));
-      ALTRO_HIP_CHECK(CopySync(stage.get() + nb, rpos, nr * sizeof(double), hipMemcpyHostToDevice));
-      base = stage.get();
-      rpos = stage.get() + nb;
+    const size_t need = (size_t)B_ * rows * c->np;
+    const Parts<2> p = InflateStageParts((size_t)(per_instance ? B_ : 1), (size_t)rows, (size_t)c->np, (size_t)B_, (size_t)N_ + 1);
+    DevBlock<double> stage;  // (goes behind the wait of `sg`)
+    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
+      err_ = "altro_cov_inflate_circles: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
+      return ALTRO_HIP_ERROR;
     }
+    Staged<2> sg(on_device != 0, stage.get(), p, stream_);
+    base = sg.in(0, base);
+    rpos = sg.in(1, rpos);
     if (need > c->spare.count()) ALTRO_HIP_CHECK(c->spare.alloc(need));
     ctg_replayable_ = false;  // (as SetConstraintTrack)
     const int nobs = c->np / 3;
     const size_t total = (size_t)B_ * rows * nobs;
     hipLaunchKernelGGL((k_cov_inflate<0>), dim3((unsigned)((total + kTeamThreads - 1) / kTeamThreads)), dim3(kTeamThreads), 0, stream_,
-                       c->spare.get(), base, rpos, B_, rows, nobs, per_instance ? B_ : 1, track_offset_, N_, kappa);
-    std::swap(c->track, c->spare);
-    c->rows = rows;
-    c->cols = B_;
-    c->base = 0;
-    c->team = false;
-    LaunchKnotParams();
-    return Sync();
+                       c->spare.get(), base, rpos, B_, rows, nobs, per_instance ? B_ : 1, up_.track_offset, N_, kappa);
+    AdoptSpare(c, rows, 0, false);
+    ALTRO_HIP_CHECK(sg.finish());
+    return ALTRO_OK;
   }
 
   // ---- closed-loop tracking (include/altro_mpc.h) ---------------------------------------------------
@@ -1209,47 +1105,28 @@ class Engine final : public EngineBase {
     }
     if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    if (on_device) {
-      ALTRO_TRY(LaunchTrack(call));
-      return Sync();
-    }
-    // the staged block (TrackStageParts); it goes when this call returns, behind the synchronisation below
+    // the staged block of a host caller (TrackStageParts); it goes when this call returns, behind the wait of finish()
     const Parts<6> p = TrackStageParts(n, m, (size_t)B_ * (size_t)call.S, (size_t)call.steps, call.dx0, call.w, call.u_lo, call.X_cl,
                                        call.U_cl, call.stats);
     DevBlock<double> stage;
-    if (stage.alloc(p.total()) != hipSuccess) {
+    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
       err_ = "altro_mpc_track: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged inputs and logs";
       return ALTRO_HIP_ERROR;
     }
-    double* const blk = stage.get();
-    const size_t *cnt = p.cnt, *off = p.off;
+    Staged<6> sg(on_device != 0, stage.get(), p, stream_);
     TrackArgs g = call;
-    hipError_t e = hipSuccess;
-    auto up = [&](const double* src, int i) {
-      if (src && e == hipSuccess) e = hipMemcpyAsync(blk + off[i], src, cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream_);
-      return src ? blk + off[i] : nullptr;
-    };
-    g.dx0 = up(call.dx0, 0);
-    g.w = up(call.w, 1);
-    g.u_lo = up(call.u_lo, 2);
-    if (call.u_hi && e == hipSuccess) e = hipMemcpyAsync(blk + off[2] + m, call.u_hi, m * sizeof(double), hipMemcpyHostToDevice, stream_);
-    g.u_hi = call.u_hi ? blk + off[2] + m : nullptr;
-    g.X_cl = call.X_cl ? blk + off[3] : nullptr;
-    g.U_cl = call.U_cl ? blk + off[4] : nullptr;
-    g.stats = call.stats ? reinterpret_cast<TrackStats*>(blk + off[5]) : nullptr;
-    g.x_end = nullptr;
-    altro_status st = ALTRO_OK;
-    if (e == hipSuccess) st = LaunchTrack(g);
-    if (st == ALTRO_OK) {
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e == hipSuccess && call.X_cl) e = hipMemcpyAsync(call.X_cl, g.X_cl, cnt[3] * sizeof(double), hipMemcpyDeviceToHost, stream_);
-      if (e == hipSuccess && call.U_cl) e = hipMemcpyAsync(call.U_cl, g.U_cl, cnt[4] * sizeof(double), hipMemcpyDeviceToHost, stream_);
-      if (e == hipSuccess && call.stats) e = hipMemcpyAsync(call.stats, g.stats, cnt[5] * sizeof(double), hipMemcpyDeviceToHost, stream_);
-    }
-    const hipError_t es = hipStreamSynchronize(stream_);  // (also after a failure: the block must not go under a copy in flight)
+    g.dx0 = sg.in(0, call.dx0);
+    g.w = sg.in(1, call.w);
+    g.u_lo = sg.in(2, call.u_lo, 0, m);
+    g.u_hi = sg.in(2, call.u_hi, m, m);
+    g.X_cl = sg.out(3, call.X_cl);
+    g.U_cl = sg.out(4, call.U_cl);
+    g.stats = sg.out(5, call.stats);
+    if (!on_device) g.x_end = nullptr;  // (a device caller's only: what altro_mpc_run_tracked advances from)
+    const altro_status st = sg.ok() ? LaunchTrack(g) : ALTRO_OK;
+    const hipError_t e = sg.finish(st == ALTRO_OK);
     ALTRO_TRY(st);
     ALTRO_HIP_CHECK(e);
-    ALTRO_HIP_CHECK(es);
     return ALTRO_OK;
   }
 
@@ -1273,7 +1150,7 @@ class Engine final : public EngineBase {
   };
   altro_status LoopBegin(const LoopSpec& s) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    run_ = LoopRun{};
+    hm_.run = LoopRun{};
     const bool ms = s.kind == kLoopMultiStart, team = s.kind == kLoopTeam;
     if (ms) ALTRO_TRY(MsCheck(s.G));
     if (team) {
@@ -1285,49 +1162,46 @@ class Engine final : public EngineBase {
     }
     LoopRun r;
     r.spec = s;
-    const size_t B = (size_t)B_, cycles = (size_t)s.cycles, Lk = cycles * s.shift;
-    const size_t nw = s.w && (ms || team) ? cycles * B * n : 0, nd = ms && s.dU ? (size_t)(s.dU_per_instance ? B_ : s.G) * N_ * m : 0;
-    hipError_t e;
-    if (s.kind == kLoopTracked) {
-      const Parts<8> p = TrackedRunParts(n, m, B, cycles, (size_t)s.shift);
-      e = r.d.alloc(p.total());
-      double* const b = r.d.get();
-      r.Xlog = b + p.off[0];
-      r.Ulog = b + p.off[1];
-      r.Xc = b + p.off[2];
-      r.Uc = b + p.off[3];
-      r.xend = b + p.off[4];
-      r.wc = b + p.off[5];
-      r.ulo = s.u_lo ? b + p.off[6] : nullptr;
-      r.uhi = s.u_hi ? b + p.off[6] + m : nullptr;
-      r.stats = reinterpret_cast<TrackStats*>(b + p.off[7]);
-    } else {  // X log | U log | w | dU | clearances
-      const Parts<5> p{B * (Lk + 1) * n, B * Lk * m, nw, nd, team ? (size_t)(B_ / s.A) * cycles : 0};
-      e = r.d.alloc(p.total());
-      double* const b = r.d.get();
-      r.Xlog = b + p.off[0];
-      r.Ulog = b + p.off[1];
-      r.w = nw ? b + p.off[2] : nullptr;
-      r.dU = nd ? b + p.off[3] : nullptr;
-      r.clear = b + p.off[4];
-    }
-    if (e == hipSuccess) e = r.i.alloc(2 * B * cycles + (ms ? (size_t)(B_ / s.G) * cycles : 0));
-    if (e != hipSuccess) {
+    const size_t B = (size_t)B_, cycles = (size_t)s.cycles;
+    const bool tracked = s.kind == kLoopTracked;
+    const Parts<8> pt = TrackedRunParts(n, m, B, cycles, (size_t)s.shift);
+    const Parts<5> pp = PlainRunParts(n, m, B, cycles, (size_t)s.shift, s.w && (ms || team),
+                                      ms && s.dU ? (size_t)(s.dU_per_instance ? B_ : s.G) * N_ * m : 0, team ? (size_t)(B_ / s.A) * cycles : 0);
+    if (r.i.alloc(2 * B * cycles + (ms ? (size_t)(B_ / s.G) * cycles : 0)) != hipSuccess ||
+        r.d.alloc(tracked ? pt.total() : pp.total()) != hipSuccess) {
       err_ = "closed-loop run: out of device memory for the logs";
       return ALTRO_HIP_ERROR;
     }
     r.it = r.i.get();
     r.win = r.it + 2 * B * cycles;
-    // (every copy is waited for: a block that goes on a failure has none in flight)
-    if (r.ulo) ALTRO_HIP_CHECK(CopySync(r.ulo, s.u_lo, m * sizeof(double), hipMemcpyHostToDevice));
-    if (r.uhi) ALTRO_HIP_CHECK(CopySync(r.uhi, s.u_hi, m * sizeof(double), hipMemcpyHostToDevice));
-    if (r.w) ALTRO_HIP_CHECK(CopySync(r.w, s.w, nw * sizeof(double), hipMemcpyHostToDevice));
-    if (r.dU) ALTRO_HIP_CHECK(CopySync(r.dU, s.dU, nd * sizeof(double), hipMemcpyHostToDevice));
-    run_ = std::move(r);
+    // the run's host inputs go up with the block carved (one wait for all of them, none without any; a block that goes on
+    // a failure has no copy in flight)
+    if (tracked) {
+      Staged<8> sg(false, r.d.get(), pt, stream_);
+      r.Xlog = sg.part(0);
+      r.Ulog = sg.part(1);
+      r.Xc = sg.part(2);
+      r.Uc = sg.part(3);
+      r.xend = sg.part(4);
+      r.wc = sg.part(5);
+      r.ulo = const_cast<double*>(sg.in(6, s.u_lo, 0, m));
+      r.uhi = const_cast<double*>(sg.in(6, s.u_hi, m, m));
+      r.stats = reinterpret_cast<TrackStats*>(sg.part(7));
+      if (sg.copies() > 0) ALTRO_HIP_CHECK(sg.finish());
+    } else {
+      Staged<5> sg(false, r.d.get(), pp, stream_);
+      r.Xlog = sg.part(0);
+      r.Ulog = sg.part(1);
+      r.w = const_cast<double*>(sg.in(2, s.w));
+      r.dU = const_cast<double*>(sg.in(3, s.dU));
+      r.clear = sg.part(4);
+      if (sg.copies() > 0) ALTRO_HIP_CHECK(sg.finish());
+    }
+    hm_.run = std::move(r);
     return ALTRO_OK;
   }
   altro_status LoopCycle(const LoopStep& step) override {
-    LoopRun& r = run_;
+    LoopRun& r = hm_.run;
     const LoopSpec& s = r.spec;
     if (!r.i || r.cycle >= s.cycles) {
       err_ = "closed-loop run: no cycle left";
@@ -1366,8 +1240,8 @@ class Engine final : public EngineBase {
       ALTRO_TRY(Advance(s.shift, r.xend, nullptr, 1, step.reset_pen, nullptr));
     } else if (s.kind == kLoopMultiStart) {
       ctg_replayable_ = false;
-      LaunchMsSelect(s.G, step.ilqr_mode, ms_win_.get(), r.win, s.cycles, r.cycle);
-      if (s.G > 1) LaunchMsSpread(s.G, ms_win_.get());
+      LaunchMsSelect(s.G, step.ilqr_mode, hm_.ms_win.get(), r.win, s.cycles, r.cycle);
+      if (s.G > 1) LaunchMsSpread(s.G, hm_.ms_win.get());
       ALTRO_TRY(Advance(s.shift, nullptr, w, 1, step.reset_pen, &log));
       if (r.dU) {
         LaunchMsPerturb(s.G, r.dU, s.dU_per_instance);
@@ -1375,7 +1249,7 @@ class Engine final : public EngineBase {
       }
     } else {
       KnotCon* kc = TeamCheck(s.A, s.index, "altro_mpc_run_team");
-      if (!kc || !team_rad_) return ALTRO_INVALID_ARG;
+      if (!kc || !hm_.team_rad) return ALTRO_INVALID_ARG;
       LaunchTeamClearance(s.A, *kc, r.clear, s.cycles, r.cycle);
       ALTRO_TRY(Advance(s.shift, nullptr, w, 1, step.reset_pen, &log));
     }
@@ -1384,7 +1258,7 @@ class Engine final : public EngineBase {
   }
   altro_status LoopEnd(const LoopOut& o) override {
     LoopRun r;  // the run goes with this call, whatever happens: behind the synchronisation no copy touches its blocks
-    std::swap(r, run_);
+    std::swap(r, hm_.run);
     const LoopSpec& s = r.spec;
     hipError_t e = hipSetDevice(desc_.device_id);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
@@ -1431,8 +1305,8 @@ class Engine final : public EngineBase {
  private:
   // the device copy of MpcRowMap(shift), built at the first advance by that shift
   altro_status MpcMap(int shift, const int** out) {
-    auto it = mpc_maps_.find(shift);
-    if (it == mpc_maps_.end()) {
+    auto it = up_.mpc_maps.find(shift);
+    if (it == up_.mpc_maps.end()) {
       const std::vector<int> src = MpcRowMap(N_, shift, con_kb_, con_ke_, con_p_, con_eq_);
       if ((int)src.size() != pd_.total_rows) {
         err_ = "altro_mpc_advance: the row map does not match the rows on the device";
@@ -1441,7 +1315,7 @@ class Engine final : public EngineBase {
       int* d = nullptr;
       ALTRO_TRY(Alloc(&d, src.size()));
       if (!src.empty()) ALTRO_HIP_CHECK(CopySync(d, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice));
-      it = mpc_maps_.emplace(shift, d).first;
+      it = up_.mpc_maps.emplace(shift, d).first;
     }
     *out = it->second;
     return ALTRO_OK;
@@ -1467,9 +1341,9 @@ class Engine final : public EngineBase {
       return ALTRO_INVALID_ARG;
     }
     if (KnotRouted(A_))  // (a tracking cost or a knot constraint: the twin that reads the per-knot records, CtxTrackK)
-      hipLaunchKernelGGL((k_mpc_track_trk<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
+      hipLaunchKernelGGL((k_mpc_track_trk<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, up_.d_pd, g);
     else
-      hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, d_pd_, g);
+      hipLaunchKernelGGL((k_mpc_track<T, M>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, A_, up_.d_pd, g);
     return ALTRO_OK;
   }
   // ---- helpers ----------------------------------------------------------------------------------
@@ -1557,7 +1431,7 @@ class Engine final : public EngineBase {
       const size_t lds = fwd_shared_bytes_ + (size_t)per_wave * fwd_per_inst_bytes_;
       const dim3 grid2((ninst + per_wave - 1) / per_wave);
       WithForwardSrc([&](auto src) {
-        hipLaunchKernelGGL((k_forward2<T, M, decltype(src)::value>), grid2, dim3(kFwdWaves * kBlock), lds, cur_, A, d_pd_, pd_, d, mode,
+        hipLaunchKernelGGL((k_forward2<T, M, decltype(src)::value>), grid2, dim3(kFwdWaves * kBlock), lds, cur_, A, up_.d_pd, pd_, d, mode,
                            all, per_wave);
       });
       return;
@@ -1567,9 +1441,9 @@ class Engine final : public EngineBase {
       // fallback: single wave, reads from HBM (staged block larger than LDS, > 20 line-search trials, per-knot
       // steps / times: SetKnotTimes, or a tracking cost)
       if (KnotRouted(A))
-        hipLaunchKernelGGL((k_forward_trk<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
+        hipLaunchKernelGGL((k_forward_trk<T, M>), grid, dim3(kBlock), 0, cur_, A, up_.d_pd, d, mode, all, fwd_per_wave_);
       else
-        hipLaunchKernelGGL((k_forward<T, M>), grid, dim3(kBlock), 0, cur_, A, d_pd_, d, mode, all, fwd_per_wave_);
+        hipLaunchKernelGGL((k_forward<T, M>), grid, dim3(kBlock), 0, cur_, A, up_.d_pd, d, mode, all, fwd_per_wave_);
     }
   }
   static void CpuRelax() {  // one spin-wait hint, whatever the host CPU
@@ -1602,11 +1476,11 @@ class Engine final : public EngineBase {
     const hipError_t e = hipMemsetAsync(dst, value, bytes, stream_);
     return e != hipSuccess ? e : hipStreamSynchronize(stream_);
   }
+  // an upload-lifetime array (Uploaded::pool): at least one element, zero-filled on the engine's stream and waited for
   template <class U>
   altro_status Alloc(U** p, size_t count) {
-    ALTRO_HIP_CHECK(hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(U)));
+    ALTRO_HIP_CHECK(up_.pool.alloc(p, count));
     ALTRO_HIP_CHECK(ZeroSync(*p, 0, std::max<size_t>(count, 1) * sizeof(U)));
-    allocs_.push_back((void*)*p);
     return ALTRO_OK;
   }
   // back to one chain: the chains' streams, their events and the booking of this engine go
@@ -1621,60 +1495,29 @@ class Engine final : public EngineBase {
     }
     chains_ = 1;
   }
+  // A_ with nothing of an upload in it: what belongs to the handle -- the history buffers and the recording switches -- stays
+  DevArrays<T> HandleView() const {
+    DevArrays<T> A{};
+    A.hist = hm_.hist.get();
+    A.hist_len = hm_.hist_len.get();
+    A.hist_cap = A_.hist_cap;
+    A.record_ctg = A_.record_ctg;
+    return A;
+  }
   // undo a (partial) UploadImpl: device buffers, chain streams and the chain booking go; the engine's own stream stays
   void DropUpload() {
     uploaded_ = false;
     if (hipSetDevice(desc_.device_id) != hipSuccess) return;
     hipStreamSynchronize(stream_);
-    for (void* p : allocs_) hipFree(p);
-    allocs_.clear();
-    mpc_maps_.clear();
-    d_hk_ = d_tk_ = nullptr;
-    d_ref_ = nullptr;
-    if (d_refpath_) hipFree(d_refpath_);
-    d_refpath_ = nullptr;
-    refpath_cap_ = 0;
-    ref_rows_ = ref_cols_ = ref_offset_ = 0;
-    DropKnotCons();
+    up_ = Uploaded{};
+    A_ = HandleView();
     DropChains();
-    // (the history buffers and the recording switches belong to the handle, not to the upload)
-    double* const hist = A_.hist;
-    int* const hist_len = A_.hist_len;
-    const int hist_cap = A_.hist_cap, record_ctg = A_.record_ctg;
-    std::memset(&A_, 0, sizeof(A_));
-    A_.hist = hist;
-    A_.hist_len = hist_len;
-    A_.hist_cap = hist_cap;
-    A_.record_ctg = record_ctg;
-    d_tmp_ = nullptr;
-    d_twin_box_ = nullptr;
-    twin_cap_ = 0;
-    d_seg_cursor_ = nullptr;
-    seg_total_ = 0;
-    d_list_[0] = d_list_[1] = nullptr;
-    d_iota_ = d_merged_ = nullptr;
-    d_loop_win_ = d_loop_ctl_ = d_loop_tail_ = nullptr;
-    loop_groups_ = 0;
-    X_init_ = U_init_ = nullptr;
-    d_phi_ = nullptr;
-    d_pd_ = nullptr;
-    d_scalarT_ = nullptr;
-    d_scalarI_ = nullptr;
   }
+  // every block is freed HERE, with the engine's device current and before its stream goes (the members' destructors find nothing)
   void Release() {
     if (hipSetDevice(desc_.device_id) != hipSuccess) return;
-    for (void* p : allocs_) hipFree(p);
-    allocs_.clear();
-    if (A_.hist) hipFree(A_.hist);
-    if (A_.hist_len) hipFree(A_.hist_len);
-    if (d_stage_) hipFree(d_stage_);
-    d_stage_ = nullptr;
-    stage_cap_ = 0;
-    if (d_refpath_) hipFree(d_refpath_);
-    d_refpath_ = nullptr;
-    DropKnotCons();
-    if (d_counter_) hipFree(d_counter_);
-    if (h_counter_) hipHostFree((void*)h_counter_);
+    up_ = Uploaded{};
+    hm_ = HandleMem{};
     for (auto& e : prof_ev_) hipEventDestroy(e);
     DropChains();
     if (start_ev_) hipEventDestroy(start_ev_);
@@ -1687,12 +1530,7 @@ class Engine final : public EngineBase {
   }
   // Staging buffer of the host boundary: the caller's row layout on the device (see k_rec_to_rows / k_rows_to_rec).
   altro_status EnsureStage(size_t doubles) {
-    if (doubles <= stage_cap_) return ALTRO_OK;
-    if (d_stage_) ALTRO_HIP_CHECK(hipFree(d_stage_));
-    d_stage_ = nullptr;
-    stage_cap_ = 0;
-    ALTRO_HIP_CHECK(hipMalloc((void**)&d_stage_, doubles * sizeof(double)));
-    stage_cap_ = doubles;
+    if (doubles > hm_.stage.count()) ALTRO_HIP_CHECK(hm_.stage.alloc(doubles));
     return ALTRO_OK;
   }
   // device records [knots][Bp][EP] (fields at off..off+E) -> host [B][knots][E]: converted on the device, one contiguous
@@ -1702,10 +1540,10 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     const size_t count = (size_t)B_ * knots * E;
     ALTRO_TRY(EnsureStage(count));
-    hipLaunchKernelGGL((k_rec_to_rows<E_>), dim3((B_ + kBlock - 1) / kBlock, knots), dim3(kBlock), 0, stream_, dev, d_stage_, knots,
+    hipLaunchKernelGGL((k_rec_to_rows<E_>), dim3((B_ + kBlock - 1) / kBlock, knots), dim3(kBlock), 0, stream_, dev, hm_.stage.get(), knots,
                        EP, off, E, B_, Bp_);
     ALTRO_HIP_CHECK(hipGetLastError());
-    ALTRO_HIP_CHECK(CopySync(out, d_stage_, count * sizeof(double), hipMemcpyDeviceToHost));
+    ALTRO_HIP_CHECK(CopySync(out, hm_.stage.get(), count * sizeof(double), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   }
   // host [B][knots][E] (or shared [knots][E]; nullptr: zeros) -> device records [knots][Bp][EP] (padding zeroed)
@@ -1713,9 +1551,9 @@ class Engine final : public EngineBase {
     const size_t count = (size_t)(per_instance ? B_ : 1) * knots * E;
     if (src) {
       ALTRO_TRY(EnsureStage(count));
-      ALTRO_HIP_CHECK(hipMemcpyAsync(d_stage_, src, count * sizeof(double), hipMemcpyHostToDevice, stream_));
+      ALTRO_HIP_CHECK(hipMemcpyAsync(hm_.stage.get(), src, count * sizeof(double), hipMemcpyHostToDevice, stream_));
     }
-    hipLaunchKernelGGL((k_rows_to_rec<T>), dim3(Bp_ / kBlock, knots), dim3(kBlock), 0, stream_, src ? (const double*)d_stage_ : nullptr,
+    hipLaunchKernelGGL((k_rows_to_rec<T>), dim3(Bp_ / kBlock, knots), dim3(kBlock), 0, stream_, src ? (const double*)hm_.stage.get() : nullptr,
                        dev, knots, EP, E, B_, Bp_, per_instance ? 1 : 0);
     ALTRO_HIP_CHECK(hipGetLastError());
     return Sync();
@@ -1737,8 +1575,8 @@ class Engine final : public EngineBase {
     const double* Uh = !s.has_U ? nullptr : (s.U_view ? s.U_view : s.U.data());
     ALTRO_TRY(UploadRec(A_.X, N_ + 1, R::nP, n, Xh, s.traj_per_instance != 0));
     ALTRO_TRY(UploadRec(A_.U, N_, R::mP, m, Uh, s.traj_per_instance != 0));
-    ALTRO_HIP_CHECK(CopySync(X_init_, A_.X, (size_t)(N_ + 1) * R::nP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice));
-    ALTRO_HIP_CHECK(CopySync(U_init_, A_.U, (size_t)N_ * R::mP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice));
+    ALTRO_HIP_CHECK(CopySync(up_.X_init, A_.X, (size_t)(N_ + 1) * R::nP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice));
+    ALTRO_HIP_CHECK(CopySync(up_.U_init, A_.U, (size_t)N_ * R::mP * Bp_ * sizeof(T), hipMemcpyDeviceToDevice));
     return ALTRO_OK;
   }
 
@@ -1765,9 +1603,9 @@ class Engine final : public EngineBase {
     N_ = desc_.N;
     Bp_ = ((B_ + kBlock - 1) / kBlock) * kBlock;
     // Twin workgroups of the persistent kernel (TwinCtl, altro_kernels.hpp) clone an instance into a SHADOW COLUMN of the
-    // per-instance arrays: every array is allocated twin_cap_ instances wider (the stride of all of them is Bp_), one column
+    // per-instance arrays: every array is allocated up_.twin_cap instances wider (the stride of all of them is Bp_), one column
     // per slot of a persistent launch.  ALTRO_HIP_TWIN=0: no columns, no twins.
-    twin_cap_ = 0;
+    up_.twin_cap = 0;
     if constexpr (kMfmaBackward) {
       if (sw_.twin && !sw_.fast_forward && !sw_.no_fused) {
         // (a solve that has split rejection streaks hands over at 3/2 of persist_at_, see Solve)
@@ -1778,12 +1616,12 @@ class Engine final : public EngineBase {
         const int per_cu = ((num_cus_ + kBlock - 1) / kBlock) * kBlock;
         const int want = std::min({std::max(Bp_, per_cu), 16384, ((persist_at_ * 3 / 2 + 8 + kBlock - 1) / kBlock) * kBlock});
         // (only widen while the 32-bit byte offsets hold)
-        if (ExpBytes((size_t)(Bp_ + want)) < (size_t)0xffffffffu) twin_cap_ = want;
+        if (ExpBytes((size_t)(Bp_ + want)) < (size_t)0xffffffffu) up_.twin_cap = want;
       }
     }
-    // Segments of rejection streaks in the batched sweeps (DevArrays::seg_*): shadow columns [Bpad, Bpad + seg_total_),
+    // Segments of rejection streaks in the batched sweeps (DevArrays::seg_*): shadow columns [Bpad, Bpad + up_.seg_total),
     // one slice per chain of sweeps, then the twin columns.  Only for batches that run batched sweeps at all; ALTRO_HIP_SEGMENTS=0 switches it off.
-    seg_total_ = 0;
+    up_.seg_total = 0;
     seg_col0_ = Bp_;
     if constexpr (kMfmaBackward) {
       if (sw_.segments && !sw_.fast_forward && B_ > persist_at_) {
@@ -1792,11 +1630,11 @@ class Engine final : public EngineBase {
         //  with 2048 / 3520 / 4096 unused columns behind its 4672; config 3 is as fast with 2560 as with 4096;
         //  profiles/r05_experiments.txt #3)
         const int want = (Bp_ * 5 / 8) / kBlock * kBlock;
-        if (ExpBytes((size_t)(Bp_ + want + twin_cap_)) < (size_t)0xffffffffu) seg_total_ = want;
+        if (ExpBytes((size_t)(Bp_ + want + up_.twin_cap)) < (size_t)0xffffffffu) up_.seg_total = want;
       }
     }
     seg_parts_ = 4;
-    Bp_ += seg_total_ + twin_cap_;
+    Bp_ += up_.seg_total + up_.twin_cap;
   }
   // what the problem compiler needs to know of the model's user types (altro_device.hpp)
   static UserTypeTable UserTypes() {
@@ -1833,13 +1671,13 @@ class Engine final : public EngineBase {
     };
     // (the shadow columns widen every array; a batch that fits 32-bit indexing without them must not be refused
     //  because of them)
-    if (biggest() > lim && seg_total_ > 0) {
-      Bp_ -= seg_total_;
-      seg_total_ = 0;
+    if (biggest() > lim && up_.seg_total > 0) {
+      Bp_ -= up_.seg_total;
+      up_.seg_total = 0;
     }
-    if (biggest() > lim && twin_cap_ > 0) {
-      Bp_ -= twin_cap_;
-      twin_cap_ = 0;
+    if (biggest() > lim && up_.twin_cap > 0) {
+      Bp_ -= up_.twin_cap;
+      up_.twin_cap = 0;
     }
     pd_.Bp = Bp_;
     if (biggest() > lim) {
@@ -1850,7 +1688,7 @@ class Engine final : public EngineBase {
   }
   // the per-instance device arrays, every one Bp_ columns wide
   altro_status AllocArrays() {
-    std::memset(&A_, 0, sizeof(A_));
+    A_ = HandleView();
     A_.B = B_;
     A_.Bp = Bp_;
     A_.N = N_;
@@ -1874,8 +1712,7 @@ class Engine final : public EngineBase {
       A_.KD = kd;
     }
     ALTRO_TRY(Alloc(&A_.CTG, (size_t)(N_ + 1) * R::CP * bp + kBlock));  // (+ the junk sink of the recording backward pass)
-    ALTRO_HIP_CHECK(hipMalloc((void**)&A_.trial, (size_t)(N_ + 1) * nm * kLineSearchLanes * bp * sizeof(T)));
-    allocs_.push_back((void*)A_.trial);
+    ALTRO_HIP_CHECK(up_.pool.alloc(&A_.trial, (size_t)(N_ + 1) * nm * kLineSearchLanes * bp));  // (the one array Alloc()'s zero fill is not spent on)
     if (sw_.poison_on) {
       std::vector<unsigned> junk((size_t)(N_ + 1) * nm * kLineSearchLanes * bp * sizeof(T) / 4);
       for (size_t i = 0; i < junk.size(); ++i) junk[i] = sw_.poison_mix ? (sw_.poison_pattern ^ ((unsigned)i * 2654435761u)) : sw_.poison_pattern;
@@ -1884,34 +1721,34 @@ class Engine final : public EngineBase {
     ALTRO_TRY(Alloc(&A_.lam, rows * bp));
     ALTRO_TRY(Alloc(&A_.pen, rows * bp));
     ALTRO_TRY(Alloc(&A_.cval, rows * bp));
-    ALTRO_TRY(Alloc(&d_tmp_, bp));
-    // mailboxes of the workers (twin_cap_ primaries, then twin_cap_ pool workgroups), then their state words
-    if (twin_cap_ > 0) ALTRO_TRY(Alloc(&d_twin_box_, TwinBoxWords()));
-    if (seg_total_ > 0) {
+    ALTRO_TRY(Alloc(&up_.d_tmp, bp));
+    // mailboxes of the workers (up_.twin_cap primaries, then up_.twin_cap pool workgroups), then their state words
+    if (up_.twin_cap > 0) ALTRO_TRY(Alloc(&up_.d_twin_box, TwinBoxWords()));
+    if (up_.seg_total > 0) {
       // (kept out of A_: only the launches of Solve that take part in the scheme see them, SegArrays)
-      ALTRO_TRY(Alloc(&seg_.end, bp));
-      ALTRO_TRY(Alloc(&seg_.next, bp));
-      ALTRO_TRY(Alloc(&seg_.flag, bp));
-      ALTRO_TRY(Alloc(&seg_.streak, bp));
-      ALTRO_TRY(Alloc(&seg_.tot0, bp));
-      ALTRO_TRY(Alloc(&seg_.rho0, bp));
-      ALTRO_TRY(Alloc(&seg_.drho0, bp));
-      ALTRO_TRY(Alloc(&d_seg_cursor_, kMaxChains));
+      ALTRO_TRY(Alloc(&up_.seg.end, bp));
+      ALTRO_TRY(Alloc(&up_.seg.next, bp));
+      ALTRO_TRY(Alloc(&up_.seg.flag, bp));
+      ALTRO_TRY(Alloc(&up_.seg.streak, bp));
+      ALTRO_TRY(Alloc(&up_.seg.tot0, bp));
+      ALTRO_TRY(Alloc(&up_.seg.rho0, bp));
+      ALTRO_TRY(Alloc(&up_.seg.drho0, bp));
+      ALTRO_TRY(Alloc(&up_.d_seg_cursor, kMaxChains));
     }
-    ALTRO_TRY(Alloc(&d_list_[0], bp));
-    ALTRO_TRY(Alloc(&d_list_[1], bp));
+    ALTRO_TRY(Alloc(&up_.d_list[0], bp));
+    ALTRO_TRY(Alloc(&up_.d_list[1], bp));
     // the reference-term records, only for a problem with a tracking cost (a group marked kParPerKnot)
     bool tracking = false;
     for (int k = 0; k <= N_; ++k) tracking = tracking || pd_.grp[pd_.cls[knot_class_[k]].cost_group].q_pi == kParPerKnot;
     if (tracking) {
-      ALTRO_TRY(Alloc(&d_ref_, (size_t)(N_ + 1) * kRefRT * bp));
-      A_.ref = d_ref_;
+      ALTRO_TRY(Alloc(&up_.d_ref, (size_t)(N_ + 1) * kRefRT * bp));
+      A_.ref = up_.d_ref;
       A_.ref_rt = kRefRT;
     }
     // the knot-parameter records, only for a problem with a knot constraint (a ConDesc marked kParPerKnotCon)
     if (knot_record_ > 0) {
-      ALTRO_TRY(Alloc(&d_kpar_, (size_t)(N_ + 1) * knot_record_ * bp));
-      A_.kpar = d_kpar_;
+      ALTRO_TRY(Alloc(&up_.d_kpar, (size_t)(N_ + 1) * knot_record_ * bp));
+      A_.kpar = up_.d_kpar;
       A_.kpar_kt = knot_record_;
     }
     return ALTRO_OK;
@@ -1934,11 +1771,11 @@ class Engine final : public EngineBase {
     if (chains_ > 1) {
       ChainClaim(desc_.device_id, +1);
       counted_chained_ = true;
-      ALTRO_TRY(Alloc(&d_iota_, bp));
-      ALTRO_TRY(Alloc(&d_merged_, bp));
+      ALTRO_TRY(Alloc(&up_.d_iota, bp));
+      ALTRO_TRY(Alloc(&up_.d_merged, bp));
       std::vector<int> iota(bp);
       for (int i = 0; i < (int)bp; ++i) iota[i] = i;
-      ALTRO_HIP_CHECK(CopySync(d_iota_, iota.data(), (size_t)bp * sizeof(int), hipMemcpyHostToDevice));
+      ALTRO_HIP_CHECK(CopySync(up_.d_iota, iota.data(), (size_t)bp * sizeof(int), hipMemcpyHostToDevice));
       for (int c = 1; c < chains_; ++c) {
         ALTRO_HIP_CHECK(hipStreamCreateWithFlags(&chain_stream_[c], hipStreamNonBlocking));
         ALTRO_HIP_CHECK(hipEventCreateWithFlags(&chain_ev_[c], hipEventDisableTiming));
@@ -1958,15 +1795,15 @@ class Engine final : public EngineBase {
   altro_status ProbeChainStreams() {
     const long long ticks = 20000;  // of the 100 MHz constant clock: 200 us
     ALTRO_HIP_CHECK(hipStreamSynchronize(stream_));
-    long long* d_stamps = nullptr;
-    ALTRO_HIP_CHECK(hipMalloc((void**)&d_stamps, 2 * kMaxChains * sizeof(long long)));
+    DevBlock<long long> stamps;  // (goes on every return, the early ones included)
+    ALTRO_HIP_CHECK(stamps.alloc(2 * kMaxChains));
     long long h_stamps[2 * kMaxChains] = {0};
     long long best_overlap = -(1ll << 60);
     for (int rep = 0; rep < 2; ++rep) {  // (the first round also loads the kernel)
       for (int c = 0; c < chains_; ++c)
-        hipLaunchKernelGGL((k_spin<0>), dim3(1), dim3(kBlock), 0, c == 0 ? stream_ : chain_stream_[c], ticks, d_stamps + 2 * c);
+        hipLaunchKernelGGL((k_spin<0>), dim3(1), dim3(kBlock), 0, c == 0 ? stream_ : chain_stream_[c], ticks, stamps.get() + 2 * c);
       for (int c = 0; c < chains_; ++c) ALTRO_HIP_CHECK(hipStreamSynchronize(c == 0 ? stream_ : chain_stream_[c]));
-      ALTRO_HIP_CHECK(CopySync(h_stamps, d_stamps, sizeof(h_stamps), hipMemcpyDeviceToHost));
+      ALTRO_HIP_CHECK(CopySync(h_stamps, stamps.get(), sizeof(h_stamps), hipMemcpyDeviceToHost));
       long long last_start = h_stamps[0], first_end = h_stamps[1];
       for (int c = 1; c < chains_; ++c) {
         last_start = std::max(last_start, h_stamps[2 * c]);
@@ -1974,7 +1811,6 @@ class Engine final : public EngineBase {
       }
       best_overlap = std::max(best_overlap, first_end - last_start);
     }
-    hipFree(d_stamps);
     chain_overlap_ticks_ = best_overlap;
     if (best_overlap < ticks / 2) {  // two of them ran (mostly) one after the other
       DropChains();
@@ -1987,8 +1823,8 @@ class Engine final : public EngineBase {
     const size_t bp = Bp_;
     const std::vector<T>& pool = cp.pool;
     const std::vector<std::vector<T>>& ip = cp.ip;
-    ALTRO_TRY(Alloc(&X_init_, (size_t)(N_ + 1) * R::nP * bp));
-    ALTRO_TRY(Alloc(&U_init_, (size_t)N_ * R::mP * bp));
+    ALTRO_TRY(Alloc(&up_.X_init, (size_t)(N_ + 1) * R::nP * bp));
+    ALTRO_TRY(Alloc(&up_.U_init, (size_t)N_ * R::mP * bp));
     T* dpool = nullptr;
     T* dipool = nullptr;
     ALTRO_TRY(Alloc(&dpool, pool.size()));
@@ -2010,24 +1846,24 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(CopySync(dkr, knot_rowbase_.data(), (N_ + 1) * sizeof(int), hipMemcpyHostToDevice));
     A_.knot_class = dkc;
     A_.knot_rowbase = dkr;
-    ALTRO_TRY(Alloc(&d_phi_, kMaxClasses * kMaxConPerKnot));
+    ALTRO_TRY(Alloc(&up_.d_phi, kMaxClasses * kMaxConPerKnot));
     {
       std::vector<double> v(kMaxClasses * kMaxConPerKnot, s.phi >= 1.0 ? s.phi : 10.0);  // constraint_values.hpp:30
-      ALTRO_HIP_CHECK(CopySync(d_phi_, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+      ALTRO_HIP_CHECK(CopySync(up_.d_phi, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    A_.phi = d_phi_;
-    ALTRO_TRY(Alloc(&d_pd_, 1));
-    ALTRO_HIP_CHECK(CopySync(d_pd_, &pd_, sizeof(pd_), hipMemcpyHostToDevice));
+    A_.phi = up_.d_phi;
+    ALTRO_TRY(Alloc(&up_.d_pd, 1));
+    ALTRO_HIP_CHECK(CopySync(up_.d_pd, &pd_, sizeof(pd_), hipMemcpyHostToDevice));
     // per-instance scalar state, one slab each so GetStats is two copies
-    ALTRO_TRY(Alloc(&d_scalarT_, (size_t)kNumScalarT * bp));
-    ALTRO_TRY(Alloc(&d_scalarI_, (size_t)kNumScalarI * bp));
+    ALTRO_TRY(Alloc(&up_.d_scalarT, (size_t)kNumScalarT * bp));
+    ALTRO_TRY(Alloc(&up_.d_scalarI, (size_t)kNumScalarI * bp));
     double** tp[kNumScalarT] = {&A_.rho_reg, &A_.drho,     &A_.dV0,  &A_.dV1,  &A_.J0,
                            &A_.initial_cost, &A_.cost_cur, &A_.cost_prev, &A_.dJ, &A_.grad,
                            &A_.viol,    &A_.penmax,   &A_.alpha, &A_.z,   &A_.reg_log};
-    for (int i = 0; i < kNumScalarT; ++i) *tp[i] = d_scalarT_ + (size_t)i * bp;
+    for (int i = 0; i < kNumScalarT; ++i) *tp[i] = up_.d_scalarT + (size_t)i * bp;
     int** ipn[kNumScalarI] = {&A_.status, &A_.status_al, &A_.it_inner, &A_.it_outer,
                               &A_.it_total, &A_.phase,   &A_.need_init_cost};
-    for (int i = 0; i < kNumScalarI; ++i) *ipn[i] = d_scalarI_ + (size_t)i * bp;
+    for (int i = 0; i < kNumScalarI; ++i) *ipn[i] = up_.d_scalarI + (size_t)i * bp;
     std::vector<int> ones(bp, ALTRO_UNSOLVED);
     ALTRO_HIP_CHECK(CopySync(A_.status, ones.data(), bp * sizeof(int), hipMemcpyHostToDevice));
     ALTRO_HIP_CHECK(CopySync(A_.status_al, ones.data(), bp * sizeof(int), hipMemcpyHostToDevice));
@@ -2191,7 +2027,7 @@ class Engine final : public EngineBase {
   // E -> B -> F for the instances in their slots; as many workgroups as the GPU holds at once (registers: two waves per
   // SIMD; LDS: the forward block, which the gain buffer of the backward pass shares), never more than the batch fills.
   altro_status PlanSweepLoop() {
-    loop_groups_ = 0;
+    up_.loop_groups = 0;
     if constexpr (kMfmaBackward) {
       if (sw_.sweep_loop != 0 && fwd_lds_bytes_ > 0 && !kdg_ && fwd_per_wave_ == lanes_per_wave() && B_ > persist_at_) {
         const size_t bwd_bytes = ((size_t)kBwdChunk * 4 * RR::KP + kBlock) * sizeof(double);  // (backward_mfma_body's sKD)
@@ -2204,7 +2040,7 @@ class Engine final : public EngineBase {
           ALTRO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kFwdWaves * kBlock, loop_lds_bytes_));
           if (sw_.loop_per_cu.set) per_cu = std::max(1, std::min(per_cu, sw_.loop_per_cu.v));
           const int slots = lanes_per_wave();
-          loop_groups_ = std::max(0, std::min(per_cu * num_cus_, (B_ + slots - 1) / slots));
+          up_.loop_groups = std::max(0, std::min(per_cu * num_cus_, (B_ + slots - 1) / slots));
           loop_per_cu_ = per_cu;
           // WHEN it takes the bulk phase (measured, profiles/r06_experiments.txt #1): a batch that fits the slots of the
           // resident workgroups (two per CU, three slots each: 1536 instances on an MI355X) runs as fast (kTurn90) or up to
@@ -2212,12 +2048,12 @@ class Engine final : public EngineBase {
           // worked off in generations -- slots refilled as instances finish -- at 1536 instances in flight against the
           // sweeps' whole batch over four chains, and is 15 - 25 % slower (4096 kTurn90: 7.5 against 6.3 ms).  So: the
           // loop by default iff the batch fits the slots; ALTRO_HIP_SWEEP_LOOP=1 forces it for any batch, =0 never.
-          if (sw_.sweep_loop != 1 && B_ > per_cu * num_cus_ * slots) loop_groups_ = 0;
+          if (sw_.sweep_loop != 1 && B_ > per_cu * num_cus_ * slots) up_.loop_groups = 0;
         }
-        if (loop_groups_ > 0) {
-          ALTRO_TRY(Alloc(&d_loop_win_, (size_t)loop_groups_ * 4));
-          ALTRO_TRY(Alloc(&d_loop_ctl_, (size_t)kLwWords + kRwWords));  // (+ the words the persistent tail kernel reports)
-          ALTRO_TRY(Alloc(&d_loop_tail_, (size_t)B_ + 16));
+        if (up_.loop_groups > 0) {
+          ALTRO_TRY(Alloc(&up_.d_loop_win, (size_t)up_.loop_groups * 4));
+          ALTRO_TRY(Alloc(&up_.d_loop_ctl, (size_t)kLwWords + kRwWords));  // (+ the words the persistent tail kernel reports)
+          ALTRO_TRY(Alloc(&up_.d_loop_tail, (size_t)B_ + 16));
         }
       }
     }
@@ -2258,7 +2094,7 @@ class Engine final : public EngineBase {
     ALTRO_TRY(UploadKnotModels(s));
     uploaded_ = true;
     // penalties start at one (constraint_values.hpp:44); an earlier SetPenalty overrides
-    hipLaunchKernelGGL(k_set_rows<T>, GridB(), dim3(kBlock), 0, stream_, A_, d_pd_, 0, 1,
+    hipLaunchKernelGGL(k_set_rows<T>, GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 0, 1,
                        T(s.penalty >= 0 ? s.penalty : 1.0));
     altro_status st = Sync();
     if (st == ALTRO_OK) st = SetInitialStateImpl(s);
@@ -2268,10 +2104,10 @@ class Engine final : public EngineBase {
       st = SetReference(s.ref_X.data(), s.ref_U.empty() ? nullptr : s.ref_U.data(), s.ref_rows, s.ref_per_instance, 0);
       if (st == ALTRO_OK && s.ref_offset > 0) st = SetReferenceOffset(s.ref_offset);
     } else if (st == ALTRO_OK) {
-      ref_offset_ = s.ref_offset;
+      up_.ref_offset = s.ref_offset;
     }
     // the knot constraints, and whatever altro_set_constraint_track / altro_set_track_offset recorded before the upload
-    kcons_.clear();
+    up_.kcons.clear();
     for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i) {
       if (con_knot_off_[i] < 0) continue;
       KnotCon c;
@@ -2281,9 +2117,9 @@ class Engine final : public EngineBase {
       c.np = s.cons[i].nparams;
       c.off = con_knot_off_[i];
       c.kind = s.cons[i].kind;
-      kcons_.push_back(std::move(c));
+      up_.kcons.push_back(std::move(c));
     }
-    if (st == ALTRO_OK) track_offset_ = s.track_offset;
+    if (st == ALTRO_OK) up_.track_offset = s.track_offset;
     for (size_t i = 0; i < s.cons.size() && st == ALTRO_OK; ++i)
       if (con_knot_off_[i] >= 0 && s.cons[i].track_rows > 0)
         st = SetConstraintTrack((int)i, s.cons[i].track.data(), s.cons[i].track_rows, s.cons[i].track_per_instance, 0);
@@ -2294,8 +2130,8 @@ class Engine final : public EngineBase {
   // ALTRO_HIP_DEBUG_POISON: shadow columns (segments of the batched sweeps, twins of the persistent kernel) start every
   // solve full of NaN words (k_poison_columns)
   void PoisonShadowColumns() {
-    if (!sw_.poison_on || seg_total_ + twin_cap_ <= 0) return;
-    const unsigned col0 = (unsigned)(Bp_ - seg_total_ - twin_cap_), ncols = (unsigned)(seg_total_ + twin_cap_);
+    if (!sw_.poison_on || up_.seg_total + up_.twin_cap <= 0) return;
+    const unsigned col0 = (unsigned)(Bp_ - up_.seg_total - up_.twin_cap), ncols = (unsigned)(up_.seg_total + up_.twin_cap);
     auto fill = [&](void* arr, size_t rows, size_t bytes_per_column_row) {
       if (!arr || rows == 0) return;
       hipLaunchKernelGGL((k_poison_columns<0>), dim3(1024), dim3(256), 0, stream_, (unsigned*)arr, (unsigned)rows, (unsigned)Bp_, col0, ncols,
@@ -2428,7 +2264,7 @@ class Engine final : public EngineBase {
       // columns' flags (no shadow column starts a solve as an active instance, whatever the last solve left in it: the
       // dense expansion launches rebuild their lists from these flags), of the sweep counters and of the twins' mailboxes
       DevArrays<T> As = A_;
-      if (seg_total_ > 0) SegArrays(As);  // (resets the bookkeeping of the segments, DevArrays::seg_*)
+      if (up_.seg_total > 0) SegArrays(As);  // (resets the bookkeeping of the segments, DevArrays::seg_*)
       ZeroJobs z{};
       int nz = 0;
       auto zero = [&](void* ptr, size_t words) {
@@ -2437,31 +2273,31 @@ class Engine final : public EngineBase {
         z.n[nz++] = (unsigned)words;
         return true;
       };
-      if (seg_total_ + twin_cap_ > 0 && !zero(A_.phase + (Bp_ - seg_total_ - twin_cap_), (size_t)(seg_total_ + twin_cap_)))
-        ALTRO_HIP_CHECK(hipMemsetAsync(A_.phase + (Bp_ - seg_total_ - twin_cap_), 0, (size_t)(seg_total_ + twin_cap_) * sizeof(int), stream_));
-      if (!zero(d_counter_, counter_words))
-        ALTRO_HIP_CHECK(hipMemsetAsync(d_counter_, 0, counter_words * sizeof(int), stream_));
-      if (twin_cap_ > 0) twin_box_clean_ = zero(d_twin_box_, TwinBoxWords() * 2);  // (else: cleared at the launch)
+      if (up_.seg_total + up_.twin_cap > 0 && !zero(A_.phase + (Bp_ - up_.seg_total - up_.twin_cap), (size_t)(up_.seg_total + up_.twin_cap)))
+        ALTRO_HIP_CHECK(hipMemsetAsync(A_.phase + (Bp_ - up_.seg_total - up_.twin_cap), 0, (size_t)(up_.seg_total + up_.twin_cap) * sizeof(int), stream_));
+      if (!zero(hm_.d_counter.get(), counter_words))
+        ALTRO_HIP_CHECK(hipMemsetAsync(hm_.d_counter.get(), 0, counter_words * sizeof(int), stream_));
+      if (up_.twin_cap > 0) twin_box_clean_ = zero(up_.d_twin_box, TwinBoxWords() * 2);  // (else: cleared at the launch)
       size_t words = 0;
       for (int j = 0; j < nz; ++j) words += z.n[j];
       const int gx = (B_ + kBlock - 1) / kBlock;
       const int rows_y = (mode == kFwdAL) ? std::max(1, (pd_.total_rows + kAlInitRows - 1) / kAlInitRows) : 0;
       const int zero_y = (int)std::min<size_t>(32, std::max<size_t>(1, words / ((size_t)gx * kBlock * 16)));
-      hipLaunchKernelGGL((k_begin_solve<T, M>), dim3(gx, 1 + rows_y + zero_y), dim3(kBlock), 0, stream_, As, d_pd_, d,
+      hipLaunchKernelGGL((k_begin_solve<T, M>), dim3(gx, 1 + rows_y + zero_y), dim3(kBlock), 0, stream_, As, up_.d_pd, d,
                          mode == kFwdAL ? 1 : 0, rows_y, z);
       timing_.launches += 1;
     } else {
-      if (mode == kFwdAL) hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, d_pd_, d);
-      if (seg_total_ + twin_cap_ > 0)
-        ALTRO_HIP_CHECK(hipMemsetAsync(A_.phase + (Bp_ - seg_total_ - twin_cap_), 0, (size_t)(seg_total_ + twin_cap_) * sizeof(int), stream_));
+      if (mode == kFwdAL) hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, up_.d_pd, d);
+      if (up_.seg_total + up_.twin_cap > 0)
+        ALTRO_HIP_CHECK(hipMemsetAsync(A_.phase + (Bp_ - up_.seg_total - up_.twin_cap), 0, (size_t)(up_.seg_total + up_.twin_cap) * sizeof(int), stream_));
       {
         DevArrays<T> As = A_;
-        if (seg_total_ > 0) SegArrays(As);
+        if (up_.seg_total > 0) SegArrays(As);
         hipLaunchKernelGGL(k_solve_setup<T>, GridB(), dim3(kBlock), 0, stream_, As, d, 1);
       }
-      hipLaunchKernelGGL((k_rollout<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, d_pd_, 1);
+      hipLaunchKernelGGL((k_rollout<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1);
       timing_.launches += (mode == kFwdAL) ? 3 : 2;
-      ALTRO_HIP_CHECK(hipMemsetAsync(d_counter_, 0, counter_words * sizeof(int), stream_));
+      ALTRO_HIP_CHECK(hipMemsetAsync(hm_.d_counter.get(), 0, counter_words * sizeof(int), stream_));
     }
     if (r.prof) hipEventRecord(ProfEvent(r.nev++), stream_);
     ALTRO_HIP_CHECK(hipGetLastError());
@@ -2472,7 +2308,7 @@ class Engine final : public EngineBase {
     r.fused_ok = FusedOk(r.d);
     // the device-side sweep loop takes the bulk phase whenever the persistent tail kernel can follow it (FusedOk: MFMA
     // backward pass, staged forward pass, uniform step, <= 20 line-search trials, no cost-to-go records)
-    r.loop_on = loop_groups_ > 0 && r.fused_ok;
+    r.loop_on = up_.loop_groups > 0 && r.fused_ok;
     r.loop_handover = std::min(B_, persist_at_);
     // segments of rejection streaks: not with a recorded history (its rows are appended in iteration order)
     // ... nor with cost-to-go records: every shadow column writes P, p into its own CTG column, and neither
@@ -2480,10 +2316,10 @@ class Engine final : public EngineBase {
     // the instance's OWN column retired
     // ... nor with a tracking cost or a knot constraint: a shadow column would need the reference-term records / the
     // knot-parameter records of its instance (copy_column)
-    r.seg_on = seg_total_ > 0 && !A_.hist && !A_.record_ctg && !r.d.fast_forward_stalls && r.C * kBlock <= seg_total_ && !r.loop_on &&
+    r.seg_on = up_.seg_total > 0 && !A_.hist && !A_.record_ctg && !r.d.fast_forward_stalls && r.C * kBlock <= up_.seg_total && !r.loop_on &&
                !KnotRouted(A_) && sw_.spec_mode == kSpecAuto;  // (the persistent kernel's variants that know the segments: default modes only)
-    r.seg_capc = r.seg_on ? (seg_total_ / r.C) / kBlock * kBlock : 0;
-    if (r.seg_on) ALTRO_HIP_CHECK(hipMemsetAsync(d_seg_cursor_, 0, kMaxChains * sizeof(int), stream_));
+    r.seg_capc = r.seg_on ? (up_.seg_total / r.C) / kBlock * kBlock : 0;
+    if (r.seg_on) ALTRO_HIP_CHECK(hipMemsetAsync(up_.d_seg_cursor, 0, kMaxChains * sizeof(int), stream_));
     // may a sweep of a chain split streaks (SplitsIn)?  Only while the batch has room: a streak split while most of the batch
     // is still iterating only makes sweeps longer that the GPU already fills (the gain is in packing the plateau of the
     // long inner solves into fewer sweeps)
@@ -2506,8 +2342,8 @@ class Engine final : public EngineBase {
       ch.lo = C > 1 ? std::min(B_, c * chain_size_) : 0;
       ch.hi = C > 1 ? std::min(B_, (c + 1) * chain_size_) : B_;
       ch.st = c == 0 ? stream_ : chain_stream_[c];
-      ch.d_cnt = d_counter_ + (size_t)c * r.cstride;
-      ch.h_cnt = h_counter_ + (size_t)c * r.cstride;
+      ch.d_cnt = hm_.d_counter.get() + (size_t)c * r.cstride;
+      ch.h_cnt = hm_.h_counter.get() + (size_t)c * r.cstride;
       ch.h_cnt_dev = h_counter_dev_ + (size_t)c * r.cstride;
       ch.known = ch.hi - ch.lo;
       for (int i = 0; i < r.max_sweeps + 2; ++i) ch.h_cnt[i] = -1;
@@ -2540,7 +2376,7 @@ class Engine final : public EngineBase {
   }
   // a chain's slice of the two list buffers: its instances and its shadow columns -- every column is listed at most once
   // (a chain never holds more than hi - lo instances of its own)
-  int* ListOf(const SolveRun& r, int which, const Chain& ch) const { return d_list_[which] + ch.lo + (int)(&ch - r.chain) * r.seg_capc; }
+  int* ListOf(const SolveRun& r, int which, const Chain& ch) const { return up_.d_list[which] + ch.lo + (int)(&ch - r.chain) * r.seg_capc; }
   // the segments' arrays and this chain's slice of shadow columns into the launch arguments of its sweep i
   void SegFields(const SolveRun& r, DevArrays<T>& A, const Chain& ch, int i) const {
     if (!r.seg_on || i < kSegFrom) {
@@ -2549,7 +2385,7 @@ class Engine final : public EngineBase {
     }
     const int c = (int)(&ch - r.chain);
     SegArrays(A);
-    A.seg_cursor = d_seg_cursor_ + c;
+    A.seg_cursor = up_.d_seg_cursor + c;
     A.seg_lo = seg_col0_ + c * r.seg_capc;
     A.seg_hi = A.seg_lo + r.seg_capc;
     A.seg_parts = seg_parts_;
@@ -2580,7 +2416,7 @@ class Engine final : public EngineBase {
     A.chain_hi = (C > 1 || r.seg_on) ? ch.hi : 0;
     SegFields(r, A, ch, i);
     if (i == 0) {
-      A.act_list = C > 1 ? d_iota_ + ch.lo : nullptr;
+      A.act_list = C > 1 ? up_.d_iota + ch.lo : nullptr;
       A.act_count = nullptr;
       A.act_count_const = ch.hi - ch.lo;
       A.host_count = nullptr;
@@ -2613,9 +2449,9 @@ class Engine final : public EngineBase {
     // (a handle with a tracking cost: the twin kernel that reads the reference-term records, same launches)
     auto expansions = [&](dim3 grid, int all, int* order_list, int* order_count) {
       if (KnotRouted(A))
-        hipLaunchKernelGGL((k_expansions_trk<T, M>), grid, dim3(kBlock), 0, ch.st, A, d_pd_, all, order_list, order_count);
+        hipLaunchKernelGGL((k_expansions_trk<T, M>), grid, dim3(kBlock), 0, ch.st, A, up_.d_pd, all, order_list, order_count);
       else
-        hipLaunchKernelGGL((k_expansions<T, M>), grid, dim3(kBlock), 0, ch.st, A, d_pd_, all, order_list, order_count);
+        hipLaunchKernelGGL((k_expansions<T, M>), grid, dim3(kBlock), 0, ch.st, A, up_.d_pd, all, order_list, order_count);
     };
     if (i > 0 && sw_.dense_expansions && !kKdgEligible && 4 * (long long)std::max(1, ch.known) >= span) {  // (thresholds 1/2 ... 1/16 measured: 1/4 ... 1/8 best)
       // a good part of the chain is still iterating: lane = instance (coalesced rows and records), and the list is
@@ -2644,17 +2480,17 @@ class Engine final : public EngineBase {
   altro_status LaunchSweepLoop(SolveRun& r) {
     if (!r.loop_on) return ALTRO_OK;
     if constexpr (kMfmaBackward) {
-      ALTRO_HIP_CHECK(hipMemsetAsync(d_loop_ctl_, 0, (size_t)(kLwWords + kRwWords) * sizeof(int), stream_));
+      ALTRO_HIP_CHECK(hipMemsetAsync(up_.d_loop_ctl, 0, (size_t)(kLwWords + kRwWords) * sizeof(int), stream_));
       const int per_xcd = ((B_ + kLoopXcds - 1) / kLoopXcds + 15) / 16 * 16;
-      const LoopCtl lc{d_loop_win_, d_loop_ctl_, d_loop_tail_, r.loop_handover, per_xcd};
+      const LoopCtl lc{up_.d_loop_win, up_.d_loop_ctl, up_.d_loop_tail, r.loop_handover, per_xcd};
       PoisonLds();
       if (r.prof) {
         r.loop_ev = r.nev;
         hipEventRecord(ProfEvent(r.nev++), stream_);
       }
-      const dim3 gl(loop_groups_), bl(kFwdWaves * kBlock);
+      const dim3 gl(up_.loop_groups), bl(kFwdWaves * kBlock);
       WithForwardSrc([&](auto src) {
-        hipLaunchKernelGGL((k_sweep_loop<T, M, decltype(src)::value>), gl, bl, loop_lds_bytes_, stream_, A_, d_pd_, pd_, r.d, r.mode, lc);
+        hipLaunchKernelGGL((k_sweep_loop<T, M, decltype(src)::value>), gl, bl, loop_lds_bytes_, stream_, A_, up_.d_pd, pd_, r.d, r.mode, lc);
       });
       if (r.prof) hipEventRecord(ProfEvent(r.nev++), stream_);
       timing_.launches += 1;
@@ -2777,7 +2613,7 @@ class Engine final : public EngineBase {
         ninst_l = r.loop_handover;  // (an upper bound: the list's length stays on the device)
         A.chain_size = 0;
       }
-      const int ninst = (int)std::min<long long>(std::max<long long>(ninst_l, 1), (long long)B_ + (r.seg_on ? seg_total_ : 0));
+      const int ninst = (int)std::min<long long>(std::max<long long>(ninst_l, 1), (long long)B_ + (r.seg_on ? up_.seg_total : 0));
       const bool any_split = AnySplit(r);
       if (any_split) {
         SegArrays(A);
@@ -2785,8 +2621,8 @@ class Engine final : public EngineBase {
         A.seg_hi = r.seg_capc;
       }
       if (r.loop_launched) {
-        A.act_list = d_loop_tail_;
-        A.act_count = d_loop_ctl_ + kLwTail;
+        A.act_list = up_.d_loop_tail;
+        A.act_count = up_.d_loop_ctl + kLwTail;
       } else if (whole_batch) {
         A.act_list = nullptr;
         A.act_count = nullptr;
@@ -2795,9 +2631,9 @@ class Engine final : public EngineBase {
         A.act_list = lists.list[0];
         A.act_count = lists.count[0];
       } else {
-        int* const merged_count = d_counter_ + (size_t)C * r.cstride;
-        hipLaunchKernelGGL((k_merge_lists<0>), dim3(1), dim3(256), 0, stream_, lists, d_merged_, merged_count);
-        A.act_list = d_merged_;
+        int* const merged_count = hm_.d_counter.get() + (size_t)C * r.cstride;
+        hipLaunchKernelGGL((k_merge_lists<0>), dim3(1), dim3(256), 0, stream_, lists, up_.d_merged, merged_count);
+        A.act_list = up_.d_merged;
         A.act_count = merged_count;
         timing_.launches += 1;
       }
@@ -2814,22 +2650,22 @@ class Engine final : public EngineBase {
       for (int k = 0; k < pd_.nruns; ++k)
         circles = circles || pd_.runs[k].fast == kFastC || pd_.runs[k].fast == kFastCB || pd_.runs[k].fast == kFastBC;
       // (with a fourth wave that runs the next iteration's backward pass beside the forward pass: see the kernel)
-      int* const out = r.loop_launched ? d_loop_ctl_ + kLwWords : d_counter_ + r.max_sweeps + 2;
+      int* const out = r.loop_launched ? up_.d_loop_ctl + kLwWords : hm_.d_counter.get() + r.max_sweeps + 2;
       const int spec = sw_.spec_mode == kSpecAuto ? (circles ? (int)kSpecWave : (int)kSpecFree) : sw_.spec_mode;
       // twin workgroups (TwinCtl): one behind every primary, dispatched after all of them (same launch, higher block
       // indices); not with a recorded history (its rows are appended in iteration order)
       TwinCtl tw{};
-      if (twin_cap_ > 0 && !A.hist && !r.d.fast_forward_stalls) {
+      if (up_.twin_cap > 0 && !A.hist && !r.d.fast_forward_stalls) {
         if (!twin_box_clean_)  // (cleared by k_begin_solve otherwise: nothing touches the mailboxes before this launch)
-          hipMemsetAsync(d_twin_box_, 0, TwinBoxWords() * sizeof(unsigned long long), stream_);
+          hipMemsetAsync(up_.d_twin_box, 0, TwinBoxWords() * sizeof(unsigned long long), stream_);
         // the pool: a workgroup per primary, or -- a small batch -- what the device has CUs left for, one shadow column each.
         // (The variants that carry segments of the batched sweeps keep one twin per primary: their bookkeeping step is full.)
         // (They also keep the former minimum share: their launch has a straggler for every CU, and a claimer's start-up --
         //  a first iteration of 75 us -- is paid for with a CU another straggler waits for.  Config 3, alternating runs:
         //  32.2 - 32.4 ms at 12 against 32.6 - 32.7 at 4, inside a spread of 0.8; profiles/tail_endgame_experiments.txt.)
         const int min_share = any_split ? std::max(sw_.twin_min, kTwinSegMin) : sw_.twin_min;
-        const int pool = std::min(twin_cap_, std::max(ninst, num_cus_ - ninst));
-        tw = TwinCtl{d_twin_box_, d_twin_box_ + (size_t)2 * twin_cap_ * kTwWords, ninst, twin_cap_, Bp_ - twin_cap_, kTwinLag, sw_.twin_debug ? 1 : 0,
+        const int pool = std::min(up_.twin_cap, std::max(ninst, num_cus_ - ninst));
+        tw = TwinCtl{up_.d_twin_box, up_.d_twin_box + (size_t)2 * up_.twin_cap * kTwWords, ninst, up_.twin_cap, Bp_ - up_.twin_cap, kTwinLag, sw_.twin_debug ? 1 : 0,
                      pool, any_split ? 1 : sw_.twin_depth, min_share, sw_.twin_spread, sw_.twin_misclaim};
       }
       const dim3 g(ninst + (tw.base > 0 ? tw.npool : 0)), b3(kFwdWaves * kBlock), b4((kFwdWaves + 1) * kBlock);
@@ -2841,7 +2677,7 @@ class Engine final : public EngineBase {
         using V = decltype(v);
         if (V::circles == circles && V::spec == spec && V::segments == any_split)
           hipLaunchKernelGGL((k_sweep_fused<T, M, V::circles, V::spec, V::segments>), g, V::spec == kSpecOff ? b3 : b4, fused_lds_bytes_,
-                             stream_, A, d_pd_, pd_, r.d, r.mode, 1, out, tw);
+                             stream_, A, up_.d_pd, pd_, r.d, r.mode, 1, out, tw);
       });
       if (r.prof) hipEventRecord(ProfEvent(r.nev++), stream_);
       r.persistent_launched = true;
@@ -2880,10 +2716,10 @@ class Engine final : public EngineBase {
     if constexpr (kMfmaBackward) {
       DevArrays<T> As = A_;
       SegArrays(As);
-      hipLaunchKernelGGL((k_seg_fixup<T, M>), dim3(B_), dim3(kBlock), 0, stream_, As, d_pd_);
+      hipLaunchKernelGGL((k_seg_fixup<T, M>), dim3(B_), dim3(kBlock), 0, stream_, As, up_.d_pd);
       timing_.launches += 1;
       int cur[kMaxChains] = {0};
-      ALTRO_HIP_CHECK(CopySync(cur, d_seg_cursor_, sizeof(cur), hipMemcpyDeviceToHost));  // (synchronises the stream)
+      ALTRO_HIP_CHECK(CopySync(cur, up_.d_seg_cursor, sizeof(cur), hipMemcpyDeviceToHost));  // (synchronises the stream)
       for (int c = 0; c < r.C; ++c) timing_.segment_columns += std::min(cur[c], r.seg_capc);
     }
     return ALTRO_OK;
@@ -2896,7 +2732,7 @@ class Engine final : public EngineBase {
       int extra[kRwWords] = {0};  // TailReportWord
       if (r.loop_launched) {
         int words[kLwWords + kRwWords];
-        ALTRO_HIP_CHECK(CopySync(words, d_loop_ctl_, sizeof(words), hipMemcpyDeviceToHost));
+        ALTRO_HIP_CHECK(CopySync(words, up_.d_loop_ctl, sizeof(words), hipMemcpyDeviceToHost));
         std::memcpy(extra, words + kLwWords, sizeof(extra));
         timing_.loop_workgroups = words[kLwGroups];
         timing_.loop_instance_iterations = words[kLwUnits];
@@ -2911,18 +2747,18 @@ class Engine final : public EngineBase {
                   per * words[kLwTicks + 1], per * words[kLwTicks + 2], per * words[kLwTicks + 3]);
         }
       } else {
-        ALTRO_HIP_CHECK(CopySync(extra, d_counter_ + r.max_sweeps + 2, sizeof(extra), hipMemcpyDeviceToHost));
+        ALTRO_HIP_CHECK(CopySync(extra, hm_.d_counter.get() + r.max_sweeps + 2, sizeof(extra), hipMemcpyDeviceToHost));
       }
       timing_.twin_handovers = extra[kRwHandovers];
       timing_.twin_claims = extra[kRwClaims];
       timing_.fused_workgroup_iterations = extra[kRwGroupLoops];
       if (r.seg_on && sw_.twin_debug) {
         int cur[kMaxChains] = {0};
-        ALTRO_HIP_CHECK(CopySync(cur, d_seg_cursor_, sizeof(cur), hipMemcpyDeviceToHost));
+        ALTRO_HIP_CHECK(CopySync(cur, up_.d_seg_cursor, sizeof(cur), hipMemcpyDeviceToHost));
         fprintf(stderr, "segments: shadow columns used per chain %d %d %d %d (of %d each), persistent launch over <= %d slots, longest own chain %d, longest workgroup %d\n",
                 cur[0], cur[1], cur[2], cur[3], r.seg_capc, (int)timing_.twin_workgroups, extra[kRwChainLoops], extra[kRwGroupLoops]);
       }
-      if (twin_cap_ > 0 && sw_.twin_debug) ALTRO_TRY(DumpTwinMailboxes());
+      if (up_.twin_cap > 0 && sw_.twin_debug) ALTRO_TRY(DumpTwinMailboxes());
       if (extra[kRwSyncErr] != 0) {
         err_ = "k_sweep_fused: a forward wave gave up waiting for its sequence word (software synchronisation)";
         return ALTRO_HIP_ERROR;
@@ -2934,15 +2770,15 @@ class Engine final : public EngineBase {
     timing_.sweeps = sweeps;
     return ALTRO_OK;
   }
-  size_t TwinBoxWords() const { return (size_t)2 * twin_cap_ * (kTwWords + 1); }
+  size_t TwinBoxWords() const { return (size_t)2 * up_.twin_cap * (kTwWords + 1); }
   // ALTRO_HIP_TWIN_DEBUG: the twins' mailboxes after the persistent launch, slot by slot (debug print only)
   altro_status DumpTwinMailboxes() {
-    const int nbox = 2 * twin_cap_;
+    const int nbox = 2 * up_.twin_cap;
     std::vector<unsigned long long> box((size_t)nbox * kTwWords);
-    ALTRO_HIP_CHECK(CopySync(box.data(), d_twin_box_, box.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    ALTRO_HIP_CHECK(CopySync(box.data(), up_.d_twin_box, box.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     int hist[4] = {0, 0, 0, 0}, why[8] = {0}, by_depth[kTwinMaxDepth + 2] = {0};
     unsigned long long t0 = ~0ull;
-    for (int s = 0; s < twin_cap_; ++s)
+    for (int s = 0; s < up_.twin_cap; ++s)
       if (box[(size_t)s * kTwWords + kTwStamp + kTsPStart]) t0 = std::min(t0, box[(size_t)s * kTwWords + kTwStamp + kTsPStart]);
     auto us_of = [&](const unsigned long long* ts, int i) { return ts[i] ? (double)(long long)(ts[i] - t0) * 0.01 : -1.0; };
     // one line per segment that a pool workgroup took: who it claimed from, its depth, its iterations and its timeline
@@ -2953,7 +2789,7 @@ class Engine final : public EngineBase {
       const unsigned long long* w = &box[(size_t)s * kTwWords];
       const unsigned long long* ts = w + kTwStamp;
       auto us = [&](int i) { return us_of(ts, i); };
-      if (s >= twin_cap_ && w[kTwClaim] != 0) {
+      if (s >= up_.twin_cap && w[kTwClaim] != 0) {
         hist[w[kTwHand] & 3]++;
         by_depth[std::min<unsigned long long>(w[kTwGen], kTwinMaxDepth + 1)]++;
         const int limit = timing_.twin_claims <= 48 || sw_.twin_debug_all ? 1 : 8;  // (every segment of a small launch, every eighth otherwise)
@@ -2963,10 +2799,10 @@ class Engine final : public EngineBase {
                   (int)(w[kTwClaim] >> 32), (int)w[kTwEnd], (int)(w[kTwHand] & 3), us(kTsTStart), us(kTsTGo), us(kTsTCloned), us(kTsTFirst), us(kTsPSnap),
                   us(kTsPClaim), us(kTsTDone), ts[kTsTLoops], us(kTsTVerdict), us(kTsPHand), us(kTsTCommit));
       }
-      if (sw_.twin_debug_all && s < twin_cap_ && ts[kTsPStart] != 0)
+      if (sw_.twin_debug_all && s < up_.twin_cap && ts[kTsPStart] != 0)
         fprintf(stderr, "  primary %4d: start %.0f snap %.0f claimed %.0f handed %.0f end %.0f\n", s, us(kTsPStart), us(kTsPSnap), us(kTsPClaim),
                 us(kTsPHand), us(kTsPEnd));
-      if (sw_.twin_debug_all && s >= twin_cap_ && w[kTwClaim] == 0 && ts[kTsTIdleEnd] != 0)
+      if (sw_.twin_debug_all && s >= up_.twin_cap && w[kTwClaim] == 0 && ts[kTsTIdleEnd] != 0)
         fprintf(stderr, "  idle %4d: start %.0f left %.0f\n", s, us(kTsTStart), us(kTsTIdleEnd));
       if (w[kTwWhy] != 0) {
         why[w[kTwWhy] & 7]++;
@@ -3040,19 +2876,60 @@ class Engine final : public EngineBase {
   // (time-varying dynamics, user discrete dynamics and per-knot model lists: every knot has its own (step, time, model))
   static constexpr bool kTimeVarying = model_knot_path<M>::value;
   static constexpr int kModelCount = model_list<M>::type::size;
-  float *d_hk_ = nullptr, *d_tk_ = nullptr;  // per-knot steps / times (SetKnotTimes), owned through allocs_
-  // the reference of the tracking costs, ALWAYS fp64: path points [row][cols][kRefPT] (cols = 1 shared, B per instance; the
-  // engine's own allocation, it grows with the path) and term records [k][Bp][kRefRT] (owned through allocs_; = A_.ref)
   static constexpr int kRefPT = RefPathRecord(n, m), kRefRT = RefTermRecord(n, m);
-  double *d_refpath_ = nullptr, *d_ref_ = nullptr;
-  size_t refpath_cap_ = 0;
-  int ref_rows_ = 0, ref_cols_ = 0, ref_offset_ = 0;
-  // the knot constraints and their tracks (each track the engine's own allocation, it grows with the track), the window
-  // offset they share, and the records [k][Bp][knot_record_] (owned through allocs_; = A_.kpar), ALWAYS fp64
-  std::vector<KnotCon> kcons_;
+  struct SegPtrs {
+    int *end = nullptr, *next = nullptr, *flag = nullptr, *streak = nullptr, *tot0 = nullptr;
+    double *rho0 = nullptr, *drho0 = nullptr;
+  };
+  // Everything that lives as long as ONE problem upload: the pool behind Alloc(), the blocks that grow on their own, every
+  // pointer into them and number that goes with them.  DropUpload() assigns a fresh one.  (A_: the view the kernels get.)
+  struct Uploaded {
+    DevPool pool;
+    float *d_hk = nullptr, *d_tk = nullptr;  // per-knot steps / times (SetKnotTimes)
+    // the reference of the tracking costs, ALWAYS fp64: path points [row][cols][kRefPT] (cols = 1 shared, B per instance; a
+    // block of its own, it grows with the path) and term records [k][Bp][kRefRT] (= A_.ref)
+    DevBlock<double> refpath;
+    double* d_ref = nullptr;
+    int ref_rows = 0, ref_cols = 0, ref_offset = 0;
+    // the knot constraints and their tracks (each track a block of its own, it grows with the track), the window offset they
+    // share, and the records [k][Bp][knot_record_] (= A_.kpar), ALWAYS fp64
+    std::vector<KnotCon> kcons;
+    int track_offset = 0;
+    double* d_kpar = nullptr;
+    ProblemDesc* d_pd = nullptr;
+    double* d_tmp = nullptr;
+    SegPtrs seg;
+    int seg_total = 0;            // shadow columns of the batched sweeps' segments (DevArrays::seg_*)
+    int* d_seg_cursor = nullptr;  // next free column of each chain's slice
+    int twin_cap = 0;                          // shadow columns behind the batch (twin workgroups of the persistent kernel)
+    unsigned long long* d_twin_box = nullptr;  // their mailboxes, [twin_cap][kTwWords]
+    int* d_list[2] = {nullptr, nullptr};
+    // the device-side sweep loop (k_sweep_loop): persistent workgroups, their windows, the control words, the tail list
+    int loop_groups = 0;
+    int *d_loop_win = nullptr, *d_loop_ctl = nullptr, *d_loop_tail = nullptr;
+    int* d_iota = nullptr;    // 0, 1, 2, ...: the active list of a chain's first sweep
+    int* d_merged = nullptr;  // the lists of all chains, concatenated for the persistent kernel
+    T *X_init = nullptr, *U_init = nullptr;
+    double *d_scalarT = nullptr, *d_phi = nullptr;
+    int* d_scalarI = nullptr;
+    std::map<int, int*> mpc_maps;  // shift -> device row map of the advance
+  };
+  // The memory that belongs to the handle and survives a dropped upload.  Release() assigns a fresh one.
+  struct HandleMem {
+    DevBlock<double> stage;     // staging buffer of the host boundary, grow-only (EnsureStage)
+    DevBlock<double> hist;      // the iteration history (SetRecordHistory; = A_.hist, A_.hist_len)
+    DevBlock<int> hist_len;
+    PinnedBlock<int> h_counter;  // one word per sweep, pinned + mapped ...
+    DevBlock<int> d_counter;     // ... and its device twin (ReserveCounters)
+    LoopRun run;                 // the closed-loop run in progress (LoopBegin .. LoopEnd)
+    DevBlock<int> ms_win;        // winners of the last multi-start call, [B] (MsCheck)
+    DevBlock<double> cov_f;      // covariance: F | Kw of the last propagation, [steps][n n + m n][Bp] (LaunchCov)
+    DevBlock<double> team_rad;   // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
+  };
+  Uploaded up_;
+  HandleMem hm_;
   std::vector<int> con_knot_off_;
-  int knot_record_ = 0, track_offset_ = 0;
-  double* d_kpar_ = nullptr;
+  int knot_record_ = 0;
   altro_desc desc_;
   int B_ = 0, Bp_ = 0, N_ = 0;
   bool uploaded_ = false;
@@ -3061,24 +2938,14 @@ class Engine final : public EngineBase {
   bool ctg_fresh_ = false;       // the cost-to-go records are those of the last backward pass
   bool ctg_replayable_ = false;  // ... or can be recomputed from what the last whole solve left in memory
   ProblemDesc pd_{};
-  ProblemDesc* d_pd_ = nullptr;
   DevArrays<T> A_{};
-  double* d_tmp_ = nullptr;
-  struct SegPtrs {
-    int *end = nullptr, *next = nullptr, *flag = nullptr, *streak = nullptr, *tot0 = nullptr;
-    double *rho0 = nullptr, *drho0 = nullptr;
-  } seg_;
   void SegArrays(DevArrays<T>& A) const {  // the bookkeeping arrays of the segments into a launch's copy of A_
-    A.seg_end = seg_.end; A.seg_next = seg_.next; A.seg_flag = seg_.flag; A.seg_streak = seg_.streak;
-    A.seg_tot0 = seg_.tot0; A.seg_rho0 = seg_.rho0; A.seg_drho0 = seg_.drho0;
+    A.seg_end = up_.seg.end; A.seg_next = up_.seg.next; A.seg_flag = up_.seg.flag; A.seg_streak = up_.seg.streak;
+    A.seg_tot0 = up_.seg.tot0; A.seg_rho0 = up_.seg.rho0; A.seg_drho0 = up_.seg.drho0;
   }
-  int seg_total_ = 0, seg_col0_ = 0, seg_parts_ = 4;  // shadow columns of the batched sweeps' segments (DevArrays::seg_*)
-  int* d_seg_cursor_ = nullptr;                       // next free column of each chain's slice
+  int seg_col0_ = 0, seg_parts_ = 4;
   const Switches sw_;  // the ALTRO_HIP_* switches, read once when the engine is constructed (no getenv on the solve path)
   int seg_below_pct_ = 65;  // split only below this share of the batch
-  int twin_cap_ = 0;                          // shadow columns behind the batch (twin workgroups of the persistent kernel)
-  unsigned long long* d_twin_box_ = nullptr;  // their mailboxes, [twin_cap_][kTwWords]
-  int* d_list_[2] = {nullptr, nullptr};
   bool mfma_offsets_ok_ = false;
   bool kdg_ = false;  // forward pass reads the feedback gains from global memory (k_forward2<.., kSrcKdg>)
   bool rg_ = false;   // ... all of the rollout wave's per-knot inputs (k_forward2<.., kSrcGlb>)
@@ -3086,8 +2953,6 @@ class Engine final : public EngineBase {
   size_t fwd_lds_bytes_ = 0, fwd_shared_bytes_ = 0, fwd_per_inst_bytes_ = 0;
   int num_cus_ = 256;
   bool twin_box_clean_ = false;  // this solve's k_begin_solve has cleared the twins' mailboxes
-  double* d_stage_ = nullptr;
-  size_t stage_cap_ = 0;
   static constexpr int kMaxChains = kMaxSweepChains;
   static constexpr int kDefaultChains = 4;
   bool counted_chained_ = false;
@@ -3103,10 +2968,8 @@ class Engine final : public EngineBase {
   static constexpr unsigned kHostSpinsBeforeNap = 400;  // ~10 us of pause instructions
   static constexpr double kHostNapAfterUs = 500.0;      // a solve shorter than this never naps
   bool host_wait_backoff_ = true;
-  // the device-side sweep loop (k_sweep_loop): persistent workgroups, their windows, the control words, the tail list
-  int loop_groups_ = 0, loop_per_cu_ = 0;
+  int loop_per_cu_ = 0;  // the device-side sweep loop (k_sweep_loop; Uploaded::loop_groups)
   size_t loop_lds_bytes_ = 0;
-  int *d_loop_win_ = nullptr, *d_loop_ctl_ = nullptr, *d_loop_tail_ = nullptr;
   static constexpr int lanes_per_wave() { return kBlock / kLineSearchLanes; }
   template <int SRC>
   static const void* LoopKernel() {
@@ -3115,30 +2978,15 @@ class Engine final : public EngineBase {
     else
       return nullptr;
   }
-  int* d_iota_ = nullptr;    // 0, 1, 2, ...: the active list of a chain's first sweep
-  int* d_merged_ = nullptr;  // the lists of all chains, concatenated for the persistent kernel
   hipStream_t cur_ = nullptr;  // the stream the launch helpers enqueue on (a chain's, otherwise the engine's)
   int fwd_single_at_ = 512;  // active instances (all chains) below which every instance gets a forward workgroup of its own
   int persist_at_ = 256;  // active instances at which the persistent tail kernel takes over
   size_t fused_lds_bytes_ = 0;
   bool no_fused_first_ = false;  // (A/B builds: first sweep of a small batch as three launches)
-  T *X_init_ = nullptr, *U_init_ = nullptr;
-  double* d_scalarT_ = nullptr;
-  int* d_scalarI_ = nullptr;
-  double* d_phi_ = nullptr;
   std::vector<int> knot_class_, knot_rowbase_;
   std::vector<int> con_kb_, con_ke_, con_p_, con_eq_;  // knots, rows and cone of every registered constraint
-  std::map<int, int*> mpc_maps_;                       // shift -> device row map of the advance (owned through allocs_)
-  LoopRun run_;                 // the closed-loop run in progress (LoopBegin .. LoopEnd)
-  DevBlock<int> ms_win_;        // winners of the last multi-start call, [B] (MsCheck)
-  DevBlock<double> cov_f_;      // covariance: F | Kw of the last propagation, [steps][n n + m n][Bp] (LaunchCov)
-  DevBlock<double> team_rad_;   // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
-  std::vector<void*> allocs_;
   hipStream_t stream_ = nullptr;
-  volatile int* h_counter_ = nullptr;  // pinned + mapped: one word per sweep
-  int* h_counter_dev_ = nullptr;       // the same words as the device sees them
-  int* d_counter_ = nullptr;
-  int counter_cap_ = 0;
+  int* h_counter_dev_ = nullptr;  // hm_.h_counter as the device sees it (ReserveCounters)
   std::vector<hipEvent_t> prof_ev_;
   altro_timing timing_{};
   std::string err_;

@@ -241,11 +241,10 @@ int altro_user_check_functors(int device, const double* z_host, int samples, dou
     v = (v ^ (v >> 27)) * 0x94D049BB133111EBull;
     return 0.5 + (double)((v ^ (v >> 31)) >> 11) * 0x1p-53;
   };
-  double *dz = nullptr, *derr = nullptr;
+  DevBlock<double> bz, berr;  // (every copy below is a blocking one and every launch is waited for: nothing in flight when they go)
   int rc = 0;
-  if (hipMalloc((void**)&dz, (size_t)samples * nm * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&derr, (size_t)samples * 3 * sizeof(double)) != hipSuccess)
-    rc = 2;
+  if (bz.alloc((size_t)samples * nm) != hipSuccess || berr.alloc((size_t)samples * 3) != hipSuccess) rc = 2;
+  double *const dz = bz.get(), *const derr = berr.get();
   if (!rc && hipMemcpy(dz, z_host, (size_t)samples * nm * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = 3;
   std::vector<double> herr((size_t)samples * 3, 0.0);
   for (int t = 0; !rc && t < (kCosts > kCons ? kCosts : kCons); ++t) {  // pass t: cost type t beside constraint type t
@@ -256,10 +255,9 @@ int altro_user_check_functors(int device, const double* z_host, int samples, dou
     std::vector<double> pc((size_t)samples * (npc > 0 ? npc : 1)), pk((size_t)samples * (npk > 0 ? npk : 1));
     for (double& v : pc) v = next();
     for (double& v : pk) v = next();
-    double *dpc = nullptr, *dpk = nullptr;
-    if (hipMalloc((void**)&dpc, pc.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&dpk, pk.size() * sizeof(double)) != hipSuccess)
-      rc = 2;
+    DevBlock<double> bpc, bpk;
+    if (bpc.alloc(pc.size()) != hipSuccess || bpk.alloc(pk.size()) != hipSuccess) rc = 2;
+    double *const dpc = bpc.get(), *const dpk = bpk.get();
     if (!rc && (hipMemcpy(dpc, pc.data(), pc.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(dpk, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
       rc = 3;
@@ -269,8 +267,6 @@ int altro_user_check_functors(int device, const double* z_host, int samples, dou
       if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = 4;
     }
     if (!rc && hipMemcpy(herr.data(), derr, herr.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = 3;
-    hipFree(dpc);
-    hipFree(dpk);
     if (rc) break;
     for (int s = 0; s < samples; ++s)
       for (int q = 0; q < 3; ++q) {
@@ -281,8 +277,6 @@ int altro_user_check_functors(int device, const double* z_host, int samples, dou
         }
       }
   }
-  hipFree(dz);
-  hipFree(derr);
   return rc;
 }
 
@@ -292,12 +286,9 @@ int altro_user_check_jacobian(int device, const double* z_host, int samples, dou
   using namespace altro_hip;
   constexpr int nm = UserM::n + UserM::m;
   if (hipSetDevice(device) != hipSuccess) return 1;
-  double *dz = nullptr, *derr = nullptr;
-  if (hipMalloc((void**)&dz, (size_t)samples * nm * sizeof(double)) != hipSuccess) return 2;
-  if (hipMalloc((void**)&derr, (size_t)samples * sizeof(double)) != hipSuccess) {
-    hipFree(dz);
-    return 2;
-  }
+  DevBlock<double> bz, berr;
+  if (bz.alloc((size_t)samples * nm) != hipSuccess || berr.alloc((size_t)samples) != hipSuccess) return 2;
+  double *const dz = bz.get(), *const derr = berr.get();
   int rc = 0;
   std::vector<double> herr(samples, 0.0);
   if (hipMemcpy(dz, z_host, (size_t)samples * nm * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = 3;
@@ -311,8 +302,6 @@ int altro_user_check_jacobian(int device, const double* z_host, int samples, dou
     if (!rc && hipMemcpy(herr.data(), derr, (size_t)samples * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = 3;
     for (double e : herr) mx = (e > mx || e != e) ? e : mx;
   }
-  hipFree(dz);
-  hipFree(derr);
   *max_err = mx;
   return rc;
 }

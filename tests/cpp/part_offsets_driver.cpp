@@ -1,6 +1,7 @@
 // part_offsets_driver.cpp -- prints, as one JSON object, where Parts (altro_common.hpp: host code, no HIP) puts the parts of the
 // two device blocks the closed-loop code carves: the block of a tracked run (TrackedRunParts) and the block Engine::MpcTrack
-// stages for a host caller (TrackStageParts).  argv: n m B cycles shift.  tests/test_part_offsets.py holds the expectations.
+// stages for a host caller (TrackStageParts), and the named layouts of the other staged calls and of the other runs.
+// argv: n m B cycles shift.  tests/test_part_offsets.py holds the expectations.
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +28,32 @@ int main(int argc, char** argv) {
   // one cycle of that run as a host call: B lanes (one sample), `shift` steps, every array present ...
   Print("track_stage", TrackStageParts(n, m, B, shift, true, true, true, true, true, true), ",");
   // ... and with only w and the statistics: an array the caller leaves out takes no room
-  Print("track_stage_sparse", TrackStageParts(n, m, B, shift, false, true, false, false, false, true), "}");
+  Print("track_stage_sparse", TrackStageParts(n, m, B, shift, false, true, false, false, false, true), ",");
+  // the block of a multi-start run (w, dU [2][N = shift][m]) and of a plain one (neither; no clearances either)
+  Print("plain_run", PlainRunParts(n, m, B, cycles, shift, true, 2 * shift * m, 0), ",");
+  Print("plain_run_sparse", PlainRunParts(n, m, B, cycles, shift, false, 0, 0), ",");
+  // the other staged calls, with `shift` steps (and a horizon of `shift` knots): everything per instance and per knot ...
+  double x = 0;  // (only whether a pointer is null matters)
+  CovArgs c{};
+  c.steps = (int)shift;
+  c.sigma0_per_instance = 1;
+  c.w_mode = 3;
+  c.Sigma0 = c.W = &x;
+  c.Sigma = c.sx = c.su = c.rpos = &x;
+  Print("cov_stage", CovStageParts(n, m, B, c), ",");
+  // ... and one shared W, no Sigma0, of the outputs only sx and rpos
+  c.w_mode = 0;
+  c.Sigma0 = nullptr;
+  c.Sigma = c.su = nullptr;
+  Print("cov_stage_sparse", CovStageParts(n, m, B, c), ",");
+  Print("inflate_stage", InflateStageParts(B, shift, 3, B, shift + 1), ",");  // one obstacle, a base track per instance
+  Print("inflate_stage_shared", InflateStageParts(1, shift, 3, B, shift + 1), ",");
+  Print("ms_best_stage", MsBestStageParts(n, m, B, shift, true, true, 7), ",");  // statistics of 7 doubles
+  Print("ms_best_stage_sparse", MsBestStageParts(n, m, B, shift, false, true, 0), ",");
+  Print("perturb_stage", PerturbStageParts(m, B, shift), ",");
+  Print("advance_stage", AdvanceStageParts(n, B, true, true), ",");
+  Print("advance_stage_sparse", AdvanceStageParts(n, B, false, true), ",");
+  Print("reference_stage", ReferenceStageParts(n, m, B * (shift + 1), true), ",");
+  Print("reference_stage_sparse", ReferenceStageParts(n, m, B * (shift + 1), false), "}");
   return 0;
 }

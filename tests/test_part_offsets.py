@@ -4,7 +4,9 @@ altro-cpp_amd/csrc/altro_common.hpp).
 Engine::LoopBegin takes the pointers of a tracked run's eight arrays, and Engine::MpcTrack those of the six arrays it stages
 for a host caller, from ONE helper that turns element counts into offsets.  tests/cpp/part_offsets_driver.cpp is built against
 the header with plain g++ (it must not need HIP) and prints counts and offsets for n = 3, m = 2, B = 5, cycles = 3, shift = 2;
-the expectations below are the sums written out by hand.
+the expectations below are the sums written out by hand.  The other blocks with a named layout -- the other closed-loop runs,
+and what CovPropagate, CovInflate, MsGetBest, MsPerturb, Advance and SetReference stage -- follow, for the same numbers
+(tests/test_devmem.py sends arrays through every one of them).
 """
 import json
 import os
@@ -56,3 +58,45 @@ def test_an_absent_array_takes_no_room(parts):
     assert p["cnt"] == [0, 30, 0, 0, 0, 25]
     assert p["off"] == [0, 0, 30, 30, 30, 30, 55]
     assert p["total"] == 55
+
+
+def _is(p, cnt):
+    """counts as given; every offset is the sum of the counts before it"""
+    assert p["cnt"] == cnt
+    assert p["off"] == [sum(cnt[:i]) for i in range(len(cnt) + 1)]
+    assert p["total"] == sum(cnt)
+
+
+def test_plain_run_block(parts):
+    """X log | U log | w [cycles][B][n] | dU | clearances"""
+    #                      X log: 5 (3 2 + 1) 3 | U log: 5 (3 2) 2 | w: 3 5 3 | dU: 2 2 2 | none
+    _is(parts["plain_run"], [105, 60, 45, 8, 0])
+    assert parts["plain_run"]["off"] == [0, 105, 165, 210, 218, 218]
+    _is(parts["plain_run_sparse"], [105, 60, 0, 0, 0])
+
+
+def test_cov_stage_block(parts):
+    """Sigma0 | W | Sigma | sx | su | rpos with 2 steps"""
+    #                      Sigma0: 5 9 | W: 5 2 9 | Sigma: 5 3 9 | sx: 5 3 3 | su: 5 2 2 | rpos: 5 3
+    _is(parts["cov_stage"], [45, 90, 135, 45, 20, 15])
+    assert parts["cov_stage"]["off"] == [0, 45, 135, 270, 315, 335, 350]
+    #                      no Sigma0 | one shared W: 9 | no Sigma | sx | no su | rpos
+    _is(parts["cov_stage_sparse"], [0, 9, 0, 45, 0, 15])
+    assert parts["cov_stage_sparse"]["off"] == [0, 0, 9, 9, 54, 54, 69]
+
+
+def test_two_part_blocks(parts):
+    _is(parts["inflate_stage"], [30, 15])          # base: 5 2 3 | rpos: 5 (2 + 1)
+    _is(parts["inflate_stage_shared"], [6, 15])    # base: 1 2 3
+    _is(parts["advance_stage"], [15, 15])          # x0: 5 3 | w: 5 3
+    _is(parts["advance_stage_sparse"], [0, 15])
+    _is(parts["reference_stage"], [45, 30])        # Xref: 15 points of 3 | Uref: 15 points of 2
+    _is(parts["reference_stage_sparse"], [45, 0])
+    _is(parts["perturb_stage"], [20])              # dU: 5 2 2
+
+
+def test_get_best_stage_block(parts):
+    """X [P][N + 1][n] | U [P][N][m] | statistics, P = 5 problems, N = 2"""
+    _is(parts["ms_best_stage"], [45, 20, 35])      # 5 3 3 | 5 2 2 | 5 7
+    assert parts["ms_best_stage"]["off"] == [0, 45, 65, 100]
+    _is(parts["ms_best_stage_sparse"], [0, 20, 0])
