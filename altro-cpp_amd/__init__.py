@@ -814,6 +814,37 @@ class BatchSolver:
         out["clear"] = clear[:self._teams(agents), :max(cycles, 0)]
         return out
 
+    # -- the solve mask and sequential team rounds (include/altro_subset.h) -------------------------
+    def set_solve_mask(self, mask):
+        """The instances the whole solves that follow run: ``mask`` [batch], non-zero = takes part; None clears it.  A
+        masked-out instance keeps everything it holds, bit for bit; the step-level calls ignore the mask."""
+        if mask is None:
+            self._call("set_solve_mask", C.c_void_p(None))
+            return
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape != (self.batch,):
+            raise ValueError(f"mask must have shape ({self.batch},)")
+        self._call("set_solve_mask", mask.ctypes.data_as(C.c_void_p))
+
+    def set_solve_mask_device(self, mask_ptr):
+        """set_solve_mask from ``batch`` bytes in memory of this handle's device."""
+        self._call("set_solve_mask_device", C.c_void_p(mask_ptr or None))
+
+    def get_solve_mask(self):
+        """The mask as a bool array [batch] (all True without a mask)."""
+        mask = np.zeros(max(self.batch, 1), dtype=np.uint8)
+        count = C.c_int(0)
+        self._call("get_solve_mask", mask.ctypes.data_as(C.c_void_p), C.byref(count))
+        out = mask[:self.batch] != 0
+        assert int(out.sum()) == count.value
+        return out
+
+    def team_solve_sequential(self, agents, index, radius, sweeps=1):
+        """``sweeps`` x (for a in range(agents): team_fill_tracks(TEAM_ALL, blend 1); mask = agent a of every team; solve);
+        the mask the handle had before is back afterwards."""
+        radius, per = self._team_radius(agents, radius)
+        self._call("team_solve_sequential", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_int(sweeps))
+
     # -- closed-loop covariance (include/altro_covariance.h) -----------------------------------------
     def _cov_inputs(self, steps, Sigma0, W):
         n, B, K = self.n, self.batch, max(int(steps), 0)

@@ -39,12 +39,13 @@
 #include "../../include/altro_multistart.h"
 #include "../../include/altro_team.h"
 #include "../../include/altro_covariance.h"
+#include "../../include/altro_subset.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 14  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 15  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -1640,6 +1641,62 @@ altro_status altro_mpc_run_team(altro_handle h, int agents, int index, const dou
   spec.radius = rad.data();
   return RunClosedLoop(h, "altro_mpc_run_team", spec, [&] { return TeamRounds(h, agents, index, mode, blend, rounds); },
                        LoopOut{X_cl, U_cl, iterations, status, nullptr, clear, nullptr});
+}
+
+}  // extern "C"
+
+// ---- the solve mask and sequential team rounds (include/altro_subset.h) ---------------------------------------------------
+extern "C" {
+
+altro_status altro_set_solve_mask(altro_handle h, const unsigned char* mask) {
+  if (!h) return ALTRO_INVALID_ARG;
+  return Forward(h, [&](EngineBase& e) { return e.SetSolveMask(mask, 0); });
+}
+altro_status altro_set_solve_mask_device(altro_handle h, const void* mask_device) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (!mask_device) {
+    h->err = "altro_set_solve_mask_device: mask_device is required (altro_set_solve_mask(h, NULL) clears the mask)";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.SetSolveMask((const unsigned char*)mask_device, 1); });
+}
+altro_status altro_get_solve_mask(altro_handle h, unsigned char* mask, int* count) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (!mask) {
+    h->err = "altro_get_solve_mask: mask is required";
+    return ALTRO_INVALID_ARG;
+  }
+  return Forward(h, [&](EngineBase& e) { return e.GetSolveMask(mask, count); });
+}
+altro_status altro_team_solve_sequential(altro_handle h, int agents, int index, const double* radius, int radius_per_instance,
+                                         int sweeps) {
+  std::vector<double> rad;
+  altro_status st = TeamCheck(h, agents, index, radius, radius_per_instance, "altro_team_solve_sequential", &rad);
+  if (st != ALTRO_OK) return st;
+  if (sweeps < 1) {
+    h->err = "altro_team_solve_sequential: at least one sweep";
+    return ALTRO_INVALID_ARG;
+  }
+  st = Forward(h, [&](EngineBase& e) {
+    const altro_status s = e.TeamRadius(rad.data());
+    return s != ALTRO_OK ? s : e.SaveSolveMask();
+  });
+  if (st != ALTRO_OK) return st;
+  for (int s = 0; s < sweeps && st == ALTRO_OK; ++s)
+    for (int a = 0; a < agents && st == ALTRO_OK; ++a) {
+      st = Forward(h, [&](EngineBase& e) {
+        const altro_status f = e.TeamFill(agents, index, ALTRO_TEAM_ALL, 1.0);
+        return f != ALTRO_OK ? f : e.TeamTurnMask(agents, a);
+      });
+      if (st == ALTRO_OK) st = altro_solve_al(h);
+    }
+  // the caller's mask comes back whatever happened; the first failure keeps its text
+  const std::string err = h->err;
+  const altro_status back = Forward(h, [&](EngineBase& e) { return e.RestoreSolveMask(); });
+  if (st != ALTRO_OK) h->err = err;
+  return st != ALTRO_OK ? st : back;
 }
 
 }  // extern "C"

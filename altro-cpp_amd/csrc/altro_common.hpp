@@ -560,6 +560,14 @@ class EngineBase {
   virtual altro_status TeamRadius(const double* radius_per_instance) = 0;
   virtual altro_status TeamFill(int A, int index, int mode, double blend) = 0;
   virtual altro_status TeamClearance(int A, int index, double* clear, int on_device) = 0;
+  // the solve mask (include/altro_subset.h): a byte per instance, host memory or (on_device) memory of the engine's device;
+  // a null host pointer clears it.  GetSolveMask: mask [B] (all ones without a mask), count may be null.  The three below
+  // serve a sequential team round: keep the caller's mask aside, set "agent a of every team" on the device, put it back.
+  virtual altro_status SetSolveMask(const unsigned char* mask, int on_device) = 0;
+  virtual altro_status GetSolveMask(unsigned char* mask, int* count) = 0;
+  virtual altro_status SaveSolveMask() = 0;
+  virtual altro_status TeamTurnMask(int A, int a) = 0;
+  virtual altro_status RestoreSolveMask() = 0;
   // closed-loop covariance (include/altro_covariance.h): CovPropagate changes nothing on the engine; CovInflate writes the
   // per-instance track of knot circle constraint `index` (base [rows][np] or [B][rows][np], rpos [B][N + 1]) and leaves the
   // window offset alone.  Host arrays, or (on_device) memory of the engine's device.

@@ -520,12 +520,7 @@ class Engine final : public EngineBase {
   altro_status GetTiming(altro_timing* t) override {
     if (timing_.instance_iterations < 0 && uploaded_) {
       ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-      ALTRO_TRY(Sync());
-      std::vector<int> it(Bp_);
-      ALTRO_HIP_CHECK(CopySync(it.data(), A_.it_total, (size_t)Bp_ * sizeof(int), hipMemcpyDeviceToHost));
-      long long tot = 0;
-      for (int b = 0; b < B_; ++b) tot += it[b];
-      timing_.instance_iterations = tot;
+      ALTRO_TRY(SumInstanceIterations());
     }
     *t = timing_;
     return ALTRO_OK;
@@ -1004,6 +999,146 @@ class Engine final : public EngineBase {
     LaunchTeamClearance(A, *c, dst, 1, 0);
     ALTRO_TRY(Sync());
     if (!on_device) ALTRO_HIP_CHECK(CopySync(clear, dst, (size_t)(B_ / A) * sizeof(double), hipMemcpyDeviceToHost));
+    return ALTRO_OK;
+  }
+
+  // ---- the solve mask (include/altro_subset.h) ------------------------------------------------------
+  // A byte per instance in hm_.mask; k_mask_compact turns it into one ascending list per chain slice (the slices StartChains
+  // cuts), which the first sweep of a chain, or the persistent tail kernel, takes where an unmasked solve takes "everyone".
+  // The host keeps the slices' counts: it sizes grids with them and decides with them whether the solve fits the tail at once.
+  MaskSlices MaskSlicesNow() const {
+    MaskSlices s{};
+    s.n = chains_;
+    for (int c = 0; c < chains_; ++c) {
+      s.lo[c] = chains_ > 1 ? std::min(B_, c * chain_size_) : 0;
+      s.hi[c] = chains_ > 1 ? std::min(B_, (c + 1) * chain_size_) : B_;
+    }
+    return s;
+  }
+  int* MaskCounts() const { return hm_.mask_list.get() + B_; }
+  altro_status MaskBlocks() {
+    if (!hm_.mask) ALTRO_HIP_CHECK(hm_.mask.alloc((size_t)B_));
+    if (!hm_.mask_list) ALTRO_HIP_CHECK(hm_.mask_list.alloc((size_t)B_ + kMaxSweepChains + 1));
+    return ALTRO_OK;
+  }
+  // `src` (device bytes, possibly hm_.mask itself) -> hm_.mask, the lists and their counts.  `known`: the counts per slice
+  // where the host can tell them without looking (a host mask, a team's turn); otherwise s.n + 1 words come back, once.
+  altro_status CompactMask(const unsigned char* src, const MaskSlices& s, const int* known) {
+    ALTRO_HIP_CHECK(hipMemsetAsync(MaskCounts() + s.n, 0, sizeof(int), stream_));
+    hipLaunchKernelGGL((k_mask_compact<0>), dim3(s.n), dim3(kMaskThreads), 0, stream_, src, hm_.mask.get(), s, hm_.mask_list.get(),
+                       MaskCounts());
+    ALTRO_HIP_CHECK(hipGetLastError());
+    int words[kMaxSweepChains + 1] = {};
+    if (known) {
+      for (int c = 0; c < s.n; ++c) words[s.n] += (words[c] = known[c]);
+    } else {
+      ALTRO_HIP_CHECK(CopySync(words, MaskCounts(), (size_t)(s.n + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    mask_.chains = chains_;
+    mask_.chain_size = chain_size_;
+    for (int c = 0; c < kMaxSweepChains; ++c) mask_.count[c] = c < s.n ? words[c] : 0;
+    mask_.total = words[s.n];
+    mask_.on = true;
+    return ALTRO_OK;
+  }
+  altro_status SetSolveMask(const unsigned char* mask, int on_device) override {
+    if (!uploaded_) {
+      err_ = "altro_set_solve_mask: no problem on the device";
+      return ALTRO_NOT_READY;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(SumInstanceIterations());  // (of the last solve, under the mask it ran with)
+    if (!mask) {
+      mask_.on = false;
+      return ALTRO_OK;
+    }
+    ALTRO_TRY(Sync());
+    ALTRO_TRY(MaskBlocks());
+    const MaskSlices s = MaskSlicesNow();
+    if (on_device) {
+      ALTRO_TRY(CompactMask(mask, s, nullptr));
+      return Sync();
+    }
+    // a host mask: staged as the other host arrays are (the bytes packed into doubles), its counts known here
+    const Parts<1> p = {((size_t)B_ + sizeof(double) - 1) / sizeof(double)};
+    ALTRO_TRY(EnsureStage(p.total() + 1));
+    std::vector<double> packed(p.total(), 0.0);
+    std::memcpy(packed.data(), mask, (size_t)B_);
+    int known[kMaxSweepChains] = {};
+    for (int c = 0; c < s.n; ++c)
+      for (int b = s.lo[c]; b < s.hi[c]; ++b) known[c] += mask[b] != 0;
+    Staged<1> sg(false, hm_.stage.get(), p, stream_);
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(sg.in(0, packed.data()));
+    const altro_status st = sg.ok() ? CompactMask(src, s, known) : ALTRO_OK;
+    ALTRO_HIP_CHECK(sg.finish(st == ALTRO_OK));
+    return st;
+  }
+  altro_status GetSolveMask(unsigned char* mask, int* count) override {
+    if (!mask_.on) {  // no mask: everyone
+      std::memset(mask, 1, (size_t)B_);
+      if (count) *count = B_;
+      return ALTRO_OK;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_HIP_CHECK(CopySync(mask, hm_.mask.get(), (size_t)B_, hipMemcpyDeviceToHost));
+    if (count) *count = mask_.total;
+    return ALTRO_OK;
+  }
+  // the lists belong to the chain slices they were cut for: should the slices have moved since, compact again
+  altro_status Recompact() {
+    if (!mask_.on || (mask_.chains == chains_ && mask_.chain_size == chain_size_)) return ALTRO_OK;
+    return CompactMask(hm_.mask.get(), MaskSlicesNow(), nullptr);
+  }
+  // one turn of a sequential team round: the mask "agent a of every team", written and compacted on the device; the
+  // counts follow from A and the slices
+  altro_status TeamTurnMask(int A, int a) override {
+    if (!uploaded_ || A < 1 || a < 0 || a >= A) return ALTRO_INVALID_ARG;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(SumInstanceIterations());
+    ALTRO_TRY(MaskBlocks());
+    hipLaunchKernelGGL((k_team_turn_mask<0>), dim3((B_ + kMaskThreads - 1) / kMaskThreads), dim3(kMaskThreads), 0, stream_, hm_.mask.get(),
+                       B_, A, a);
+    const MaskSlices s = MaskSlicesNow();
+    int known[kMaxSweepChains] = {};
+    // (instances b in [lo, hi) with b % A == a: those below hi less those below lo)
+    auto below = [&](int x) { return x <= a ? 0 : (x - a - 1) / A + 1; };
+    for (int c = 0; c < s.n; ++c) known[c] = below(s.hi[c]) - below(s.lo[c]);
+    return CompactMask(hm_.mask.get(), s, known);
+  }
+  // what a sequential team round puts back when it is over: the mask bytes the handle had, kept on the device meanwhile
+  altro_status SaveSolveMask() override {
+    mask_saved_on_ = mask_.on;
+    if (!mask_.on) return ALTRO_OK;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    if (!hm_.mask_saved) ALTRO_HIP_CHECK(hm_.mask_saved.alloc((size_t)B_));
+    ALTRO_HIP_CHECK(CopySync(hm_.mask_saved.get(), hm_.mask.get(), (size_t)B_, hipMemcpyDeviceToDevice));
+    mask_saved_ = mask_;
+    return ALTRO_OK;
+  }
+  altro_status RestoreSolveMask() override {
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    ALTRO_TRY(SumInstanceIterations());
+    if (!mask_saved_on_) {
+      mask_.on = false;
+      return ALTRO_OK;
+    }
+    ALTRO_TRY(CompactMask(hm_.mask_saved.get(), MaskSlicesNow(), mask_saved_.chains == chains_ && mask_saved_.chain_size == chain_size_ ? mask_saved_.count : nullptr));
+    return Sync();
+  }
+  // timing_.instance_iterations of the last solve, if nobody has asked yet: the iterations of the instances it ran
+  altro_status SumInstanceIterations() {
+    if (!(timing_.instance_iterations < 0) || !uploaded_) return ALTRO_OK;
+    ALTRO_TRY(Sync());
+    std::vector<int> it(Bp_);
+    ALTRO_HIP_CHECK(CopySync(it.data(), A_.it_total, (size_t)Bp_ * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<unsigned char> in;
+    if (last_solve_masked_) {
+      in.resize((size_t)B_);
+      ALTRO_HIP_CHECK(CopySync(in.data(), hm_.mask.get(), (size_t)B_, hipMemcpyDeviceToHost));
+    }
+    long long tot = 0;
+    for (int b = 0; b < B_; ++b) tot += in.empty() || in[b] ? it[b] : 0;
+    timing_.instance_iterations = tot;
     return ALTRO_OK;
   }
 
@@ -2206,6 +2341,22 @@ class Engine final : public EngineBase {
   altro_status Solve(const altro_options& o, int mode) {
     if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    if (mask_.on) {
+      // a solve mask (include/altro_subset.h): the start of the solve, the first sweep of every chain and a tail that
+      // starts at once take the compacted lists instead of "everyone"; everything behind them runs on lists anyway
+      if (A_.record_ctg) {
+        // (ReplayCtg and the batched backward kernels' records cover whole batches: a masked-out instance's records
+        //  would not stay what they were)
+        err_ = "a masked solve does not record the cost-to-go (altro_set_record_ctg): clear the mask or switch the records off";
+        return ALTRO_UNSUPPORTED;
+      }
+      ALTRO_TRY(SumInstanceIterations());
+      ALTRO_TRY(Recompact());
+      if (mask_.total == 0) {  // nobody takes part: nothing is launched, nothing changes
+        std::memset(&timing_, 0, sizeof(timing_));
+        return ALTRO_OK;
+      }
+    }
     SolveRun r;
     ALTRO_TRY(StartRun(r, o, mode));
     ALTRO_TRY(BeginSolve(r));
@@ -2232,7 +2383,8 @@ class Engine final : public EngineBase {
     last_mode_ilqr_ = (mode == kFwdILQR);
     last_opts_ = r.d;
     ctg_fresh_ = A_.record_ctg != 0;  // (recorded by the batched backward kernels of this solve, or readable through ReplayCtg)
-    ctg_replayable_ = true;
+    ctg_replayable_ = !mask_.on;  // (a replay recomputes every instance's records from what it finds)
+    last_solve_masked_ = mask_.on;
     std::memset(&timing_, 0, sizeof(timing_));
     cur_ = stream_;
     PoisonShadowColumns();
@@ -2283,19 +2435,35 @@ class Engine final : public EngineBase {
       const int gx = (B_ + kBlock - 1) / kBlock;
       const int rows_y = (mode == kFwdAL) ? std::max(1, (pd_.total_rows + kAlInitRows - 1) / kAlInitRows) : 0;
       const int zero_y = (int)std::min<size_t>(32, std::max<size_t>(1, words / ((size_t)gx * kBlock * 16)));
-      hipLaunchKernelGGL((k_begin_solve<T, M>), dim3(gx, 1 + rows_y + zero_y), dim3(kBlock), 0, stream_, As, up_.d_pd, d,
-                         mode == kFwdAL ? 1 : 0, rows_y, z);
+      if (mask_.on)
+        hipLaunchKernelGGL((k_begin_solve_masked<T, M>), dim3(gx, 1 + rows_y + zero_y), dim3(kBlock), 0, stream_, As, up_.d_pd, d,
+                           mode == kFwdAL ? 1 : 0, rows_y, z, (const unsigned char*)hm_.mask.get());
+      else
+        hipLaunchKernelGGL((k_begin_solve<T, M>), dim3(gx, 1 + rows_y + zero_y), dim3(kBlock), 0, stream_, As, up_.d_pd, d,
+                           mode == kFwdAL ? 1 : 0, rows_y, z);
       timing_.launches += 1;
     } else {
-      if (mode == kFwdAL) hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, up_.d_pd, d);
+      const unsigned char* const mk = hm_.mask.get();
+      if (mode == kFwdAL) {
+        if (mask_.on)
+          hipLaunchKernelGGL(k_al_init_masked<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, up_.d_pd, d, mk);
+        else
+          hipLaunchKernelGGL(k_al_init<T>, GridAlInit(), dim3(kBlock), 0, stream_, A_, up_.d_pd, d);
+      }
       if (up_.seg_total + up_.twin_cap > 0)
         ALTRO_HIP_CHECK(hipMemsetAsync(A_.phase + (Bp_ - up_.seg_total - up_.twin_cap), 0, (size_t)(up_.seg_total + up_.twin_cap) * sizeof(int), stream_));
       {
         DevArrays<T> As = A_;
         if (up_.seg_total > 0) SegArrays(As);
-        hipLaunchKernelGGL(k_solve_setup<T>, GridB(), dim3(kBlock), 0, stream_, As, d, 1);
+        if (mask_.on)
+          hipLaunchKernelGGL(k_solve_setup_masked<T>, GridB(), dim3(kBlock), 0, stream_, As, d, 1, mk);
+        else
+          hipLaunchKernelGGL(k_solve_setup<T>, GridB(), dim3(kBlock), 0, stream_, As, d, 1);
       }
-      hipLaunchKernelGGL((k_rollout<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1);
+      if (mask_.on)
+        hipLaunchKernelGGL((k_rollout_masked<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1, mk);
+      else
+        hipLaunchKernelGGL((k_rollout<T, M>), GridB(), dim3(kBlock), 0, stream_, A_, up_.d_pd, 1);
       timing_.launches += (mode == kFwdAL) ? 3 : 2;
       ALTRO_HIP_CHECK(hipMemsetAsync(hm_.d_counter.get(), 0, counter_words * sizeof(int), stream_));
     }
@@ -2308,7 +2476,8 @@ class Engine final : public EngineBase {
     r.fused_ok = FusedOk(r.d);
     // the device-side sweep loop takes the bulk phase whenever the persistent tail kernel can follow it (FusedOk: MFMA
     // backward pass, staged forward pass, uniform step, <= 20 line-search trials, no cost-to-go records)
-    r.loop_on = up_.loop_groups > 0 && r.fused_ok;
+    // ... and no solve mask is set: its workgroups pull index ranges of the batch, not a list
+    r.loop_on = up_.loop_groups > 0 && r.fused_ok && !mask_.on;
     r.loop_handover = std::min(B_, persist_at_);
     // segments of rejection streaks: not with a recorded history (its rows are appended in iteration order)
     // ... nor with cost-to-go records: every shadow column writes P, p into its own CTG column, and neither
@@ -2345,7 +2514,8 @@ class Engine final : public EngineBase {
       ch.d_cnt = hm_.d_counter.get() + (size_t)c * r.cstride;
       ch.h_cnt = hm_.h_counter.get() + (size_t)c * r.cstride;
       ch.h_cnt_dev = h_counter_dev_ + (size_t)c * r.cstride;
-      ch.known = ch.hi - ch.lo;
+      ch.known = mask_.on ? mask_.count[c] : ch.hi - ch.lo;
+      ch.done = mask_.on && ch.known == 0;  // (a slice the mask leaves empty: this chain launches nothing)
       for (int i = 0; i < r.max_sweeps + 2; ++i) ch.h_cnt[i] = -1;
     }
     if (C > 1) {
@@ -2415,7 +2585,11 @@ class Engine final : public EngineBase {
     A.chain_lo = ch.lo;
     A.chain_hi = (C > 1 || r.seg_on) ? ch.hi : 0;
     SegFields(r, A, ch, i);
-    if (i == 0) {
+    if (i == 0 && mask_.on) {  // the masked-in instances of the chain's slice, in order (k_mask_compact)
+      A.act_list = hm_.mask_list.get() + ch.lo;
+      A.act_count = MaskCounts() + (int)(&ch - r.chain);
+      A.host_count = nullptr;
+    } else if (i == 0) {
       A.act_list = C > 1 ? up_.d_iota + ch.lo : nullptr;
       A.act_count = nullptr;
       A.act_count_const = ch.hi - ch.lo;
@@ -2432,7 +2606,8 @@ class Engine final : public EngineBase {
     if (!may_split) A.seg_parts = 1;
     // (a batch that fits the CUs from the start -- the MPC case, one or a few dozen instances -- goes to the persistent
     //  kernel at once: its first sweep as three launches and a host round trip would only add latency)
-    if (r.fused_ok && (i > 0 || (C == 1 && !no_fused_first_)) &&
+    // (under a solve mask the chains of a large batch too: what counts is how many instances take part)
+    if (r.fused_ok && (i > 0 || ((C == 1 || mask_.on) && !no_fused_first_)) &&
         (r.tail_mode || TotalKnown(r) <= (AnySplit(r) ? r.seg_persist_at : persist_at_))) {
       // the tail: every instance left gets a workgroup that runs whole iterations (k_sweep_fused, launched by LaunchTail
       // for all chains together); this chain's list is the one sweep i would have worked on
@@ -2545,6 +2720,7 @@ class Engine final : public EngineBase {
   // others -- until every chain has run dry, met its cap or turned to the tail.
   altro_status RunChains(SolveRun& r) {
     for (int c = 0; c < r.C && !r.loop_launched; ++c) {
+      if (r.chain[c].done) continue;  // (a chain whose slice the solve mask leaves empty)
       ALTRO_TRY(EnqueueSweep(r, r.chain[c], 0));
       if (!r.chain[c].tail) r.chain[c].sweeps = 1;  // (tail already: the persistent kernel takes the batch from its first sweep)
     }
@@ -2595,6 +2771,13 @@ class Engine final : public EngineBase {
         Chain& ch = r.chain[c];
         A.chain_base[c] = ch.sweeps;  // batched sweeps this chain ran (0 .. sweeps-1)
         if (!ch.tail) continue;
+        if (ch.sweeps == 0 && mask_.on) {  // (no batched sweep ran: the masked-in instances of the chain's slice, in order)
+          lists.list[lists.n] = hm_.mask_list.get() + ch.lo;
+          lists.count[lists.n] = MaskCounts() + c;
+          lists.n++;
+          ninst_l += ch.known;
+          continue;
+        }
         if (ch.sweeps == 0) {  // (single chain, no batched sweep ran: every instance, in order)
           whole_batch = true;
           ninst_l += B_;
@@ -2925,7 +3108,22 @@ class Engine final : public EngineBase {
     DevBlock<int> ms_win;        // winners of the last multi-start call, [B] (MsCheck)
     DevBlock<double> cov_f;      // covariance: F | Kw of the last propagation, [steps][n n + m n][Bp] (LaunchCov)
     DevBlock<double> team_rad;   // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
+    // the solve mask (SetSolveMask): a byte per instance [B]; the masked-in instances of every chain slice, ascending, at the
+    // slice's own place [B], then the slices' counts and their sum [kMaxSweepChains + 1] (k_mask_compact)
+    DevBlock<unsigned char> mask;
+    DevBlock<int> mask_list;
+    DevBlock<unsigned char> mask_saved;  // the caller's mask while a sequential team round runs under its turns' masks
   };
+  // the host's side of the solve mask: is one set, the chain slices it was compacted for, how many instances each holds
+  struct MaskState {
+    bool on = false;
+    int chains = 0, chain_size = 0;
+    int count[kMaxSweepChains] = {};
+    int total = 0;
+  };
+  MaskState mask_, mask_saved_;
+  bool mask_saved_on_ = false;
+  bool last_solve_masked_ = false;  // (GetTiming sums the iterations of the instances the last solve ran)
   Uploaded up_;
   HandleMem hm_;
   std::vector<int> con_knot_off_;

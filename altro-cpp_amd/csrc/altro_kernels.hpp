@@ -1328,12 +1328,18 @@ __global__ __launch_bounds__(kBlock) void k_backward_mfma16(DevArrays<T> A, DevO
 // -------------------------------------------------------------------------------------------------
 // iLQR::Rollout (ilqr.hpp:453-459), one lane per instance
 // -------------------------------------------------------------------------------------------------
-template <class T, class M>
-__global__ __launch_bounds__(kBlock) void k_rollout(DevArrays<T> A, const ProblemDesc* __restrict__ pd, int all) {
+// (MASKED, here and in the other kernels that start a whole solve: `mask` holds a byte per instance, and an instance whose
+//  byte is zero is left exactly as it is -- the solve mask of include/altro_subset.h.  Every such kernel is a body with the
+//  flag and two entry points: the one every unmasked solve and the step-level API launch, whose name, arguments and
+//  resources are what they were before the mask existed, and k_*_masked.)
+template <class T, class M, bool MASKED>
+ALTRO_DEV void rollout_body(DevArrays<T> A, const ProblemDesc* __restrict__ pd, int all, const unsigned char* __restrict__ mask) {
   constexpr int n = M::n, m = M::m;
   using R = Rec<T, n, m>;
   const int b = blockIdx.x * kBlock + threadIdx.x;
   if (b >= A.B) return;
+  if constexpr (MASKED)
+    if (!mask[b]) return;
   if (!all && A.phase[b] != 1) return;
   const unsigned Bp = A.Bp;
   T x[R::nP], u[R::mP], xn[n];
@@ -1346,6 +1352,15 @@ __global__ __launch_bounds__(kBlock) void k_rollout(DevArrays<T> A, const Proble
     for (int i = 0; i < n; ++i) x[i] = xn[i];
   }
   store_rec<T, R::nP>(RECP(A.X, A.N, R::nP), x);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_rollout(DevArrays<T> A, const ProblemDesc* __restrict__ pd, int all) {
+  rollout_body<T, M, false>(A, pd, all, nullptr);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_rollout_masked(DevArrays<T> A, const ProblemDesc* __restrict__ pd, int all,
+                                                           const unsigned char* __restrict__ mask) {
+  rollout_body<T, M, true>(A, pd, all, mask);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1489,10 +1504,12 @@ __global__ __launch_bounds__(kBlock) void k_reset_stats(DevArrays<T> A) {
 // writing them one after the other was 18 us of every solve (a batch of one as much as a batch of 4096); blockIdx.y
 // takes kAlInitRows rows each, the blocks of chunk 0 do the per-instance part.
 constexpr int kAlInitRows = 32;
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_al_init(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o) {
+template <class T, bool MASKED>
+ALTRO_DEV void al_init_body(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o, const unsigned char* __restrict__ mask) {
   const int b = blockIdx.x * kBlock + threadIdx.x;
   if (b >= A.B) return;
+  if constexpr (MASKED)
+    if (!mask[b]) return;
   {
     const bool zero_lam = o.reset_duals != 0, set_pen = o.initial_penalty > 0;  // quirk Q8
     const int r0 = (int)blockIdx.y * kAlInitRows, r1 = min(r0 + kAlInitRows, pd->total_rows);
@@ -1513,6 +1530,15 @@ __global__ __launch_bounds__(kBlock) void k_al_init(DevArrays<T> A, const Proble
   }
   A.status_al[b] = ALTRO_UNSOLVED;
 }
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_al_init(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o) {
+  al_init_body<T, false>(A, pd, o, nullptr);
+}
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_al_init_masked(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o,
+                                                           const unsigned char* __restrict__ mask) {
+  al_init_body<T, true>(A, pd, o, mask);
+}
 // finishing touch of AL Init for the step-level API: log viol (after a cost evaluation) and pen
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_log_viol_pen(DevArrays<T> A, const ProblemDesc* __restrict__ pd) {
@@ -1523,10 +1549,28 @@ __global__ __launch_bounds__(kBlock) void k_log_viol_pen(DevArrays<T> A, const P
   A.viol[b] = (double)v;
   A.penmax[b] = (double)p;
 }
+// a masked-out instance at the start of a masked solve: it is no active instance of this solve (the dense expansion launches
+// rebuild their lists from `phase`), and no segment bookkeeping of its last solve survives (k_seg_fixup walks every column);
+// neither is observable, and nothing else of it is touched
 template <class T>
-__global__ __launch_bounds__(kBlock) void k_solve_setup(DevArrays<T> A, DevOpts o, int activate) {
+ALTRO_DEV void park_masked_out(const DevArrays<T>& A, int b) {
+  A.phase[b] = 0;
+  if (A.seg_end) {
+    A.seg_end[b] = kSegNoEnd;
+    A.seg_next[b] = -1;
+    A.seg_flag[b] = 0;
+    A.seg_streak[b] = 0;
+  }
+}
+template <class T, bool MASKED>
+ALTRO_DEV void solve_setup_body(DevArrays<T> A, DevOpts o, int activate, const unsigned char* __restrict__ mask) {
   const int b = blockIdx.x * kBlock + threadIdx.x;
   if (b >= A.B) return;
+  if constexpr (MASKED)
+    if (!mask[b]) {
+      park_masked_out(A, b);
+      return;
+    }
   begin_inner_solve(A, o, b);
   if (activate) A.phase[b] = 1;
   if (A.seg_end) {  // no segment bookkeeping survives a solve
@@ -1535,6 +1579,15 @@ __global__ __launch_bounds__(kBlock) void k_solve_setup(DevArrays<T> A, DevOpts 
     A.seg_flag[b] = 0;
     A.seg_streak[b] = 0;
   }
+}
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_solve_setup(DevArrays<T> A, DevOpts o, int activate) {
+  solve_setup_body<T, false>(A, o, activate, nullptr);
+}
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_solve_setup_masked(DevArrays<T> A, DevOpts o, int activate,
+                                                               const unsigned char* __restrict__ mask) {
+  solve_setup_body<T, true>(A, o, activate, mask);
 }
 // -------------------------------------------------------------------------------------------------
 // The start of a whole solve in ONE launch (round 6): what Solve() used to enqueue as k_al_init, a memset of the shadow
@@ -1555,9 +1608,9 @@ struct ZeroJobs {
   unsigned* p[kZeroJobs];
   unsigned n[kZeroJobs];  // 32-bit words
 };
-template <class T, class M>
-__global__ __launch_bounds__(kBlock) void k_begin_solve(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o, int al,
-                                                        int rows_y, ZeroJobs z) {
+template <class T, class M, bool MASKED>
+ALTRO_DEV void begin_solve_body(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o, int al, int rows_y, ZeroJobs z,
+                                const unsigned char* __restrict__ mask) {
   constexpr int n = M::n;
   using R = Rec<T, M::n, M::m>;
   const int by = (int)blockIdx.y;
@@ -1571,6 +1624,11 @@ __global__ __launch_bounds__(kBlock) void k_begin_solve(DevArrays<T> A, const Pr
   }
   const int b = blockIdx.x * kBlock + threadIdx.x;
   if (b >= A.B) return;
+  if constexpr (MASKED)
+    if (!mask[b]) {  // masked out: skipped in every part
+      if (by == 0) park_masked_out(A, b);
+      return;
+    }
   if (by > 0) {
     const bool zero_lam = o.reset_duals != 0, set_pen = o.initial_penalty > 0;  // quirk Q8
     const int r0 = (by - 1) * kAlInitRows, r1 = min(r0 + kAlInitRows, pd->total_rows);
@@ -1624,6 +1682,16 @@ __global__ __launch_bounds__(kBlock) void k_begin_solve(DevArrays<T> A, const Pr
     md = mdn;
   }
   store_rec<T, R::nP>(RECP(A.X, N, R::nP), x);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_begin_solve(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o, int al,
+                                                        int rows_y, ZeroJobs z) {
+  begin_solve_body<T, M, false>(A, pd, o, al, rows_y, z, nullptr);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_begin_solve_masked(DevArrays<T> A, const ProblemDesc* __restrict__ pd, DevOpts o, int al,
+                                                               int rows_y, ZeroJobs z, const unsigned char* __restrict__ mask) {
+  begin_solve_body<T, M, true>(A, pd, o, al, rows_y, z, mask);
 }
 
 template <class T>
@@ -6056,6 +6124,62 @@ __global__ __launch_bounds__(kTeamThreads) void k_cov_inflate(double* __restrict
   dst[0] = src[0];
   dst[1] = src[1];
   dst[2] = src[2] + kappa * rpos[b * (size_t)(N + 1) + (size_t)at];
+}
+
+// -------------------------------------------------------------------------------------------------
+// The solve mask (include/altro_subset.h): which instances the whole solves that follow run.
+//
+// k_mask_compact: one workgroup per chain slice [lo[c], hi[c]) of the batch.  It writes the masked-in instances of its slice
+// in ASCENDING order into list[lo[c] ...] -- neighbouring instances stay neighbours in the workgroups of the sweeps, and a
+// full mask gives the list 0, 1, 2, ... that an unmasked first sweep walks -- the slice's count into count[c], and the
+// normalised mask (0 / 1) into `mask` (which may be `src` itself: every byte is read and written by the same lane).  Order
+// comes from a two-level prefix, not from arrival: the workgroup walks its slice in tiles of kMaskThreads instances; within
+// a wave a ballot and the popcount of the lanes below give a lane its place, the waves' totals meet in LDS and are summed
+// in wave order, and the tile's total moves the running base.  The one atomic of a workgroup adds the slice's count to the
+// batch's total, count[nslices] (cleared by the caller).  Bounds: a slice holds at most hi - lo masked-in instances, so
+// lo + base + prefix < hi.  (Templates, as k_merge_lists: one definition per program.)
+// -------------------------------------------------------------------------------------------------
+constexpr int kMaskThreads = 256;
+struct MaskSlices {
+  int lo[kMaxSweepChains], hi[kMaxSweepChains];
+  int n;
+};
+template <int kDummy>
+__global__ __launch_bounds__(kMaskThreads) void k_mask_compact(const unsigned char* src, unsigned char* mask, MaskSlices s,
+                                                               int* __restrict__ list, int* __restrict__ count) {
+  __shared__ int wave_total[kMaskThreads / 64];
+  const int c = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (c >= s.n) return;
+  const int lo = s.lo[c], hi = s.hi[c];
+  int base = 0;
+  for (int t0 = lo; t0 < hi; t0 += kMaskThreads) {
+    const int b = t0 + tid;
+    const bool in = b < hi && src[b] != 0;
+    if (b < hi) mask[b] = in ? 1 : 0;
+    const unsigned long long ballot = __ballot(in);
+    const int before = (int)__popcll(ballot & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wave] = (int)__popcll(ballot);
+    __syncthreads();
+    int off = base, tile = 0;
+#pragma unroll
+    for (int w = 0; w < kMaskThreads / 64; ++w) {
+      if (w < wave) off += wave_total[w];
+      tile += wave_total[w];
+    }
+    if (in) list[lo + off + before] = b;
+    base += tile;
+    __syncthreads();  // (the totals are rewritten by the next tile)
+  }
+  if (tid == 0) {
+    count[c] = base;
+    atomicAdd(count + s.n, base);
+  }
+}
+// The mask of one turn of a sequential team round (altro_team_solve_sequential): agent `a` of every team, one lane per instance.
+template <int kDummy>
+__global__ __launch_bounds__(kMaskThreads) void k_team_turn_mask(unsigned char* __restrict__ mask, int B, int A, int a) {
+  const int b = (int)blockIdx.x * kMaskThreads + (int)threadIdx.x;
+  if (b < B) mask[b] = (b % A == a) ? 1 : 0;
 }
 
 }  // namespace altro_hip

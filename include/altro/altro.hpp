@@ -41,6 +41,7 @@
 #include "../altro_multistart.h"
 #include "../altro_team.h"
 #include "../altro_covariance.h"
+#include "../altro_subset.h"
 
 namespace altro {
 
@@ -1495,6 +1496,31 @@ class AugmentedLagrangianiLQR {
     ilqr_solver_.PrepareSolve();
     detail::Check(Handle(), altro_team_solve(Handle(), agents, index, radius, radius_per_instance ? 1 : 0, mode, blend, rounds),
                   "altro_team_solve");
+    ilqr_solver_.Pull(true, true);
+    status_ = ilqr_solver_.StatusAL();
+    ilqr_solver_.AfterSolve();
+  }
+  // The solve mask (include/altro_subset.h): mask[BatchSize()], non-zero = the instance takes part in the whole solves that
+  // follow (Solve(), SolveTeam, the closed-loop runs); a masked-out instance keeps everything it holds.  Thin calls of the C
+  // entry points, giving their bits.
+  void SetSolveMask(const unsigned char* mask) {
+    ilqr_solver_.Push();
+    detail::Check(Handle(), altro_set_solve_mask(Handle(), mask), "altro_set_solve_mask");
+  }
+  void ClearSolveMask() { SetSolveMask(nullptr); }
+  int GetSolveMask(unsigned char* mask) {
+    ilqr_solver_.Push();
+    int count = 0;
+    detail::Check(Handle(), altro_get_solve_mask(Handle(), mask, &count), "altro_get_solve_mask");
+    return count;
+  }
+  // sweeps x (for every agent in turn: FillTeamTracks(ALTRO_TEAM_ALL, 1.0); mask = that agent of every team; solve); the mask
+  // set before the call is back afterwards
+  void SolveTeamSequential(int agents, int index, const double* radius, bool radius_per_instance, int sweeps) {
+    ilqr_solver_.Push();
+    ilqr_solver_.PrepareSolve();
+    detail::Check(Handle(), altro_team_solve_sequential(Handle(), agents, index, radius, radius_per_instance ? 1 : 0, sweeps),
+                  "altro_team_solve_sequential");
     ilqr_solver_.Pull(true, true);
     status_ = ilqr_solver_.StatusAL();
     ilqr_solver_.AfterSolve();
