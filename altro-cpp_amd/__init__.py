@@ -29,6 +29,9 @@ MODEL_UNICYCLE, MODEL_TRIPLE_INTEGRATOR, MODEL_QUADROTOR12 = 1, 2, 3
 CON_GOAL, CON_CONTROL_BOUND, CON_CIRCLE, CON_USER = 1, 2, 3, 4
 TEAM_ALL, TEAM_PRIORITY = 0, 1  # include/altro_team.h
 COV_W_PER_INSTANCE, COV_W_PER_KNOT = 1, 2  # include/altro_covariance.h: w_mode bits
+# include/altro_trigger.h: the bits of a reason
+(TRIGGER_FIRST, TRIGGER_AGE, TRIGGER_DEVIATION, TRIGGER_VIOLATION, TRIGGER_LIMIT, TRIGGER_UNSOLVED,
+ TRIGGER_AHEAD) = 1, 2, 4, 8, 16, 32, 64
 # altro::SolverStatus, altro/common/solver_stats.hpp:20-31
 (SOLVED, UNSOLVED, STATE_LIMIT, CONTROL_LIMIT, COST_INCREASE, MAX_ITERATIONS, MAX_OUTER_ITERATIONS,
  MAX_INNER_ITERATIONS, MAX_PENALTY, BACKWARD_PASS_REGULARIZATION_FAILED) = range(10)
@@ -80,6 +83,18 @@ class TrackStats(C.Structure):
 
 TRACK_STATS_DTYPE = np.dtype([(name, np.int32 if t is C.c_int else np.float64) for name, t in TrackStats._fields_])
 assert TRACK_STATS_DTYPE.itemsize == C.sizeof(TrackStats) == 40
+
+
+class TriggerRule(C.Structure):
+    """altro_trigger_rule (include/altro_trigger.h): when an instance is re-planned.  The defaults re-plan by age alone."""
+    _fields_ = [("max_age", C.c_int), ("dx_tol", C.c_double), ("viol_tol", C.c_double), ("on_unsolved", C.c_int),
+                ("lookahead", C.c_int), ("ahead_tol", C.c_double)]
+
+    def __init__(self, max_age=1, dx_tol=-1.0, viol_tol=-1.0, on_unsolved=0, lookahead=0, ahead_tol=0.0):
+        super().__init__(int(max_age), float(dx_tol), float(viol_tol), int(on_unsolved), int(lookahead), float(ahead_tol))
+
+
+assert C.sizeof(TriggerRule) == 40
 
 
 class Timing(C.Structure):
@@ -844,6 +859,53 @@ class BatchSolver:
         the mask the handle had before is back afterwards."""
         radius, per = self._team_radius(agents, radius)
         self._call("team_solve_sequential", C.c_int(agents), C.c_int(index), _dp(radius), C.c_int(per), C.c_int(sweeps))
+
+    # -- event-triggered re-planning (include/altro_trigger.h) ---------------------------------------
+    @staticmethod
+    def _rule(rule):
+        if isinstance(rule, TriggerRule):
+            return rule
+        return TriggerRule(**rule)
+
+    def mpc_trigger(self, rule, tracked=None, age=None, u_lo=None, u_hi=None):
+        """The trigger rule for every instance (altro_mpc_trigger): ``rule`` a TriggerRule or a dict of its fields, ``tracked``
+        [B] of TRACK_STATS_DTYPE (the segment just tracked; None: the tracked criteria are off), ``age`` [B] (None: 0).
+        Changes nothing on the handle.  Returns (mask [B] bool, reason [B] int32 of TRIGGER_* bits)."""
+        rule = self._rule(rule)
+        u_lo, u_hi = self._track_bounds(u_lo, u_hi)
+        if tracked is not None:
+            tracked = np.ascontiguousarray(tracked, dtype=TRACK_STATS_DTYPE)
+            if tracked.shape != (self.batch,):
+                raise ValueError(f"tracked must have shape ({self.batch},)")
+        if age is not None:
+            age = np.ascontiguousarray(age, dtype=np.int32)
+            if age.shape != (self.batch,):
+                raise ValueError(f"age must have shape ({self.batch},)")
+        mask = np.zeros(max(self.batch, 1), dtype=np.uint8)
+        reason = np.zeros(max(self.batch, 1), dtype=np.int32)
+        self._call("mpc_trigger", C.byref(rule), None if tracked is None else tracked.ctypes.data_as(C.POINTER(TrackStats)),
+                   None if age is None else self._ip(age), _dp(u_lo), _dp(u_hi), mask.ctypes.data_as(C.c_void_p), self._ip(reason))
+        return mask[:self.batch] != 0, reason[:self.batch]
+
+    def mpc_trigger_device(self, rule, tracked_ptr=0, age_ptr=0, u_lo_ptr=0, u_hi_ptr=0, mask_ptr=0, reason_ptr=0):
+        """mpc_trigger with every array in memory of this handle's device (any pointer may be 0); ``mask_ptr`` can go straight
+        into set_solve_mask_device."""
+        self._call("mpc_trigger_device", C.byref(self._rule(rule)), *(C.c_void_p(p or None) for p in
+                   (tracked_ptr, age_ptr, u_lo_ptr, u_hi_ptr, mask_ptr, reason_ptr)))
+
+    def mpc_run_triggered(self, cycles, shift, rule, w=None, u_lo=None, u_hi=None):
+        """mpc_run_tracked that re-plans only the instances the rule triggers (altro_mpc_run_triggered): cycle 0 solves
+        everyone, every later cycle the instances whose plan is ``max_age`` cycles old, was left by the plant, ...; the others
+        follow their shifted plan under its gains.  Returns the dict of mpc_run_tracked (iterations 0 where an instance was
+        not solved) plus reason [B][cycles] of TRIGGER_* bits, 0 where it was not solved."""
+        rule = self._rule(rule)
+        u_lo, u_hi = self._track_bounds(u_lo, u_hi)
+        w, out, logs = self._run_logs(cycles, shift, w, per_knot=True)
+        out["track"] = np.zeros((self.batch, max(cycles, 0)), dtype=TRACK_STATS_DTYPE)
+        out["reason"] = np.zeros((self.batch, max(cycles, 0)), dtype=np.int32)
+        self._call("mpc_run_triggered", C.c_int(cycles), C.c_int(shift), _dp(w), _dp(u_lo), _dp(u_hi), C.byref(rule), *logs,
+                   out["track"].ctypes.data_as(C.POINTER(TrackStats)), self._ip(out["reason"]))
+        return out
 
     # -- closed-loop covariance (include/altro_covariance.h) -----------------------------------------
     def _cov_inputs(self, steps, Sigma0, W):

@@ -40,12 +40,13 @@
 #include "../../include/altro_team.h"
 #include "../../include/altro_covariance.h"
 #include "../../include/altro_subset.h"
+#include "../../include/altro_trigger.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 15  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 16  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -54,6 +55,7 @@ struct altro_solver_s {
   bool uploaded = false;
   bool ilqr_mode = false;
   bool has_gains = false;  // a backward pass (a solve, altro_backward_pass) has left gains on the device: altro_mpc_track
+  bool record_ctg = false;  // altro_set_record_ctg(h, 1) went through: masked solves, and so the trigger calls, refuse the handle
   bool has_solved = false;  // a whole solve (altro_solve_al, altro_solve_ilqr, altro_wait) has finished: altro_multistart_select
   std::string err;
   // Asynchronous solve (altro_solve_al_async): ONE worker thread per handle, created on first use and
@@ -1086,7 +1088,9 @@ altro_status altro_get_gains(altro_handle h, double* K, double* d) {
   return Forward(h, [&](EngineBase& e) { return e.GetGains(K, d); });
 }
 altro_status altro_set_record_ctg(altro_handle h, int enable) {
-  return Forward(h, [&](EngineBase& e) { return e.SetRecordCtg(enable); });
+  const altro_status st = Forward(h, [&](EngineBase& e) { return e.SetRecordCtg(enable); });
+  if (h && st == ALTRO_OK) h->record_ctg = enable != 0;
+  return st;
 }
 altro_status altro_get_ctg(altro_handle h, double* P, double* p) {
   return Forward(h, [&](EngineBase& e) { return e.GetCtg(P, p); });
@@ -1324,7 +1328,7 @@ LoopSpec MakeLoopSpec(altro_handle h, LoopKind kind, int cycles, int shift, cons
   s.cycles = cycles;
   s.shift = shift;
   s.w = w;
-  s.w_stride = (size_t)h->spec.desc.batch * (size_t)h->spec.desc.n * (kind == kLoopTracked ? (size_t)std::max(shift, 0) : 1);
+  s.w_stride = (size_t)h->spec.desc.batch * (size_t)h->spec.desc.n * (kind == kLoopTracked || kind == kLoopTriggered ? (size_t)std::max(shift, 0) : 1);
   return s;
 }
 
@@ -1697,6 +1701,142 @@ altro_status altro_team_solve_sequential(altro_handle h, int agents, int index, 
   const altro_status back = Forward(h, [&](EngineBase& e) { return e.RestoreSolveMask(); });
   if (st != ALTRO_OK) h->err = err;
   return st != ALTRO_OK ? st : back;
+}
+
+}  // extern "C"
+
+// ---- event-triggered re-planning (include/altro_trigger.h) ------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(altro_trigger_rule) == sizeof(TriggerRule) && sizeof(altro_trigger_rule) == 40 &&
+                  offsetof(altro_trigger_rule, max_age) == offsetof(TriggerRule, max_age) &&
+                  offsetof(altro_trigger_rule, dx_tol) == offsetof(TriggerRule, dx_tol) &&
+                  offsetof(altro_trigger_rule, viol_tol) == offsetof(TriggerRule, viol_tol) &&
+                  offsetof(altro_trigger_rule, on_unsolved) == offsetof(TriggerRule, on_unsolved) &&
+                  offsetof(altro_trigger_rule, lookahead) == offsetof(TriggerRule, lookahead) &&
+                  offsetof(altro_trigger_rule, ahead_tol) == offsetof(TriggerRule, ahead_tol),
+              "altro_trigger_rule (include/altro_trigger.h) and TriggerRule (altro_common.hpp) are one layout");
+static_assert(ALTRO_TRIGGER_FIRST == kTrigFirst && ALTRO_TRIGGER_AGE == kTrigAge && ALTRO_TRIGGER_DEVIATION == kTrigDeviation &&
+                  ALTRO_TRIGGER_VIOLATION == kTrigViolation && ALTRO_TRIGGER_LIMIT == kTrigLimit &&
+                  ALTRO_TRIGGER_UNSOLVED == kTrigUnsolved && ALTRO_TRIGGER_AHEAD == kTrigAhead,
+              "ALTRO_TRIGGER_* (include/altro_trigger.h) and TriggerBit (altro_common.hpp) are the same bits");
+
+TriggerRule RuleOf(const altro_trigger_rule& r) {
+  return TriggerRule{r.max_age, r.dx_tol, r.viol_tol, r.on_unsolved, r.lookahead, r.ahead_tol};
+}
+// what can be said about a rule and the bounds without a device
+altro_status TriggerRuleCheck(altro_handle h, const altro_trigger_rule* rule, const double* u_lo, const double* u_hi, const char* who) {
+  const std::string w(who);
+  const int N = h->spec.desc.N;
+  if (!rule) {
+    h->err = w + ": rule is required";
+    return ALTRO_INVALID_ARG;
+  }
+  if (rule->max_age < 1) {
+    h->err = w + ": max_age must be at least 1, got " + std::to_string(rule->max_age);
+    return ALTRO_INVALID_ARG;
+  }
+  if (rule->dx_tol != rule->dx_tol || rule->viol_tol != rule->viol_tol || (rule->lookahead > 0 && rule->ahead_tol != rule->ahead_tol)) {
+    h->err = w + ": a tolerance is NaN (a negative dx_tol or viol_tol switches its criterion off)";
+    return ALTRO_INVALID_ARG;
+  }
+  if (rule->lookahead < 0 || rule->lookahead > N) {
+    h->err = w + ": lookahead must lie in [0, N] = [0, " + std::to_string(N) + "], got " + std::to_string(rule->lookahead);
+    return ALTRO_INVALID_ARG;
+  }
+  if (rule->lookahead > 0 && rule->ahead_tol < 0) {
+    h->err = w + ": ahead_tol must not be negative with a lookahead";
+    return ALTRO_INVALID_ARG;
+  }
+  if ((u_lo == nullptr) != (u_hi == nullptr)) {
+    h->err = w + ": u_lo and u_hi come together (both or neither)";
+    return ALTRO_INVALID_ARG;
+  }
+  return ALTRO_OK;
+}
+// a handle that records the cost-to-go: masked solves refuse it (include/altro_subset.h), and so does everything built on them
+altro_status TriggerCtgRefused(altro_handle h, const char* who) {
+  if (!h->record_ctg) return ALTRO_OK;
+  h->err = std::string(who) + ": a masked solve does not record the cost-to-go (altro_set_record_ctg): switch the records off";
+  return ALTRO_UNSUPPORTED;
+}
+// both evaluation entry points: everything that can be refused without a device first
+altro_status MpcTriggerImpl(altro_handle h, const altro_trigger_rule* rule, const altro_track_stats* tracked, const int* age,
+                            const double* u_lo, const double* u_hi, unsigned char* mask, int* reason, int on_device, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const altro_status st = TriggerRuleCheck(h, rule, u_lo, u_hi, who);
+  if (st != ALTRO_OK) return st;
+  if (!h->spec.hk.empty() || !h->spec.tk.empty() || !h->spec.knot_model.empty()) {
+    h->err = std::string(who) + ": per-knot steps, times or models (altro_set_steps, altro_set_times, altro_set_knot_models) do "
+             "not move along the horizon yet";
+    return ALTRO_UNSUPPORTED;
+  }
+  if (TriggerCtgRefused(h, who) != ALTRO_OK) return ALTRO_UNSUPPORTED;
+  if (rule->lookahead > 0 && !h->has_gains) {
+    h->err = std::string(who) + ": the lookahead needs gains, and no backward pass has produced any on this handle yet "
+             "(altro_solve_al, altro_solve_ilqr, altro_backward_pass)";
+    return ALTRO_NOT_READY;
+  }
+  if (ReferenceMissing(h)) return ALTRO_NOT_READY;
+  TriggerArgs g{};
+  g.rule = RuleOf(*rule);
+  g.tracked = reinterpret_cast<const TrackStats*>(tracked);
+  g.age = age;
+  g.u_lo = u_lo;
+  g.u_hi = u_hi;
+  g.mask = mask;
+  g.reason = reason;
+  g.track = TrackOpts(h);
+  return Forward(h, [&](EngineBase& e) { return e.Trigger(g, on_device, h->ilqr_mode); });
+}
+
+}  // namespace
+
+extern "C" {
+
+altro_status altro_mpc_trigger(altro_handle h, const altro_trigger_rule* rule, const altro_track_stats* tracked, const int* age,
+                               const double* u_lo, const double* u_hi, unsigned char* mask, int* reason) {
+  return MpcTriggerImpl(h, rule, tracked, age, u_lo, u_hi, mask, reason, 0, "altro_mpc_trigger");
+}
+altro_status altro_mpc_trigger_device(altro_handle h, const altro_trigger_rule* rule, const void* tracked_device,
+                                      const void* age_device, const void* u_lo_device, const void* u_hi_device, void* mask_device,
+                                      void* reason_device) {
+  return MpcTriggerImpl(h, rule, (const altro_track_stats*)tracked_device, (const int*)age_device, (const double*)u_lo_device,
+                        (const double*)u_hi_device, (unsigned char*)mask_device, (int*)reason_device, 1, "altro_mpc_trigger_device");
+}
+altro_status altro_mpc_run_triggered(altro_handle h, int cycles, int shift, const double* w, const double* u_lo, const double* u_hi,
+                                     const altro_trigger_rule* rule, double* X_cl, double* U_cl, int* iterations, int* status,
+                                     altro_track_stats* track, int* reason) {
+  const char* who = "altro_mpc_run_triggered";
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (cycles < 1) {
+    h->err = std::string(who) + ": at least one cycle";
+    return ALTRO_INVALID_ARG;
+  }
+  altro_status st = TriggerRuleCheck(h, rule, u_lo, u_hi, who);
+  if (st != ALTRO_OK) return st;
+  st = MpcCheck(h, shift, who);
+  if (st == ALTRO_INVALID_ARG) return st;
+  // a plan may be followed for max_age cycles: the last of them tracks knots (max_age - 1) shift .. max_age shift of it, and
+  // the rule behind every cycle but that one looks `lookahead` knots ahead -- none of it may reach the held tail
+  const int N = h->spec.desc.N;
+  if ((long long)(rule->max_age - 1) * shift + std::max(shift, rule->lookahead) > N) {
+    h->err = std::string(who) + ": (max_age - 1) * shift + max(shift, lookahead) = " +
+             std::to_string((long long)(rule->max_age - 1) * shift + std::max(shift, rule->lookahead)) + " exceeds N = " + std::to_string(N) +
+             ": a plan would be followed, or looked ahead, into the held tail";
+    return ALTRO_INVALID_ARG;
+  }
+  if (st != ALTRO_OK) return st;
+  if (TriggerCtgRefused(h, who) != ALTRO_OK) return ALTRO_UNSUPPORTED;
+  LoopSpec spec = MakeLoopSpec(h, kLoopTriggered, cycles, shift, w);
+  spec.u_lo = u_lo;
+  spec.u_hi = u_hi;
+  spec.rule = RuleOf(*rule);
+  LoopOut out{X_cl, U_cl, iterations, status, nullptr, nullptr, reinterpret_cast<TrackStats*>(track)};
+  out.reason = reason;
+  return RunClosedLoop(h, who, spec, [&] { return altro_solve_al(h); }, out);
 }
 
 }  // extern "C"

@@ -134,6 +134,35 @@ struct TrackArgs {
   double state_max, control_max;
 };
 
+// ---- event-triggered re-planning (include/altro_trigger.h) ------------------------------------------------
+// altro_trigger_rule as the kernel reads it (the C-ABI translation unit asserts that the two layouts agree) and the bits of
+// a reason (ALTRO_TRIGGER_*)
+struct TriggerRule {
+  int max_age;
+  double dx_tol, viol_tol;
+  int on_unsolved, lookahead;
+  double ahead_tol;
+};
+enum TriggerBit {
+  kTrigFirst = 1,
+  kTrigAge = 2,
+  kTrigDeviation = 4,
+  kTrigViolation = 8,
+  kTrigLimit = 16,
+  kTrigUnsolved = 32,
+  kTrigAhead = 64
+};
+// One call of Engine::Trigger / one launch of k_mpc_trigger.  Every pointer may be null; host or device memory as the call says.
+struct TriggerArgs {
+  TriggerRule rule;
+  const TrackStats* tracked;  // [B]
+  const int* age;             // [B]
+  const double *u_lo, *u_hi;  // [m] each, both or neither: the lookahead's
+  unsigned char* mask;        // [B]
+  int* reason;                // [B]
+  TrackArgs track;            // the options of the lookahead's tracking call (check_bounds, state_max, control_max)
+};
+
 // One call of Engine::CovPropagate / one launch of k_cov_recur (include/altro_covariance.h).  Every pointer may be null; host
 // or device memory as the call says.
 struct CovArgs {
@@ -194,6 +223,12 @@ inline Parts<2> InflateStageParts(size_t cols, size_t rows, size_t np, size_t B,
 inline Parts<3> MsBestStageParts(int n, int m, size_t P, size_t N, bool X, bool U, size_t stats_doubles) {
   return {X ? P * (N + 1) * n : 0, U ? P * N * m : 0, P * stats_doubles};
 }
+// Engine::Trigger: tracked | age | u_lo, u_hi | mask | reason (a host caller's; ints and bytes packed into doubles) | the
+// lookahead's statistics [B] (every caller's: they live for the call)
+inline Parts<6> TriggerStageParts(int m, size_t B, bool tracked, bool age, bool bounds, bool mask, bool reason, bool ahead) {
+  const size_t ts = sizeof(TrackStats) / sizeof(double), ints = (B + 1) / 2, bytes = (B + 7) / 8;
+  return {tracked ? B * ts : 0, age ? ints : 0, bounds ? 2 * (size_t)m : 0, mask ? bytes : 0, reason ? ints : 0, ahead ? B * ts : 0};
+}
 inline Parts<1> PerturbStageParts(int m, size_t cols, size_t N) { return {cols * N * m}; }
 inline Parts<2> AdvanceStageParts(int n, size_t B, bool x0, bool w) { return {x0 ? B * n : 0, w ? B * n : 0}; }
 inline Parts<2> ReferenceStageParts(int n, int m, size_t points, bool U) { return {points * n, U ? points * m : 0}; }
@@ -205,7 +240,8 @@ enum LoopKind {
   kLoopPlain = 0,   // advance under w[c]
   kLoopTracked,     // track `shift` knots under the gains and w[c], advance from the tracked state
   kLoopMultiStart,  // select and spread the best of G starts, advance under w[c], perturb by dU
-  kLoopTeam         // log the team's clearance, advance under w[c] (the C API runs the team's rounds as the cycle's solve)
+  kLoopTeam,        // log the team's clearance, advance under w[c] (the C API runs the team's rounds as the cycle's solve)
+  kLoopTriggered    // kLoopTracked whose solves run under the mask the trigger rule left (include/altro_trigger.h)
 };
 struct LoopSpec {
   int kind, cycles, shift;
@@ -215,7 +251,8 @@ struct LoopSpec {
   const double* dU;
   int A, index;                 // team: agents per team, the team's knot circle constraint
   const double* radius;         // team: one per instance
-  const double *u_lo, *u_hi;    // tracked: [m] each, both or neither
+  const double *u_lo, *u_hi;    // tracked, triggered: [m] each, both or neither
+  TriggerRule rule;             // triggered
 };
 struct LoopStep {  // what a cycle takes from the handle at the moment it runs
   double reset_pen;  // the penalty of a row that starts afresh
@@ -223,10 +260,11 @@ struct LoopStep {  // what a cycle takes from the handle at the moment it runs
   TrackArgs track;   // the options of a tracking call (check_bounds, state_max, control_max)
 };
 struct LoopOut {  // [B][cycles shift + 1][n], [B][cycles shift][m], [B][cycles] each; winner [B / G][cycles], clear [B / A][cycles]
-  double *X_cl, *U_cl;
-  int *iterations, *status, *winner;
-  double* clear;
-  TrackStats* track;
+  double *X_cl = nullptr, *U_cl = nullptr;
+  int *iterations = nullptr, *status = nullptr, *winner = nullptr;
+  double* clear = nullptr;
+  TrackStats* track = nullptr;
+  int* reason = nullptr;  // triggered: [B][cycles]
 };
 
 // ---- knot constraints (include/altro_knot_params.h) ----------------------------------------------------
@@ -341,6 +379,24 @@ ALTRO_HD int ms_select(const int* status, const double* cost, const double* viol
                   violation[w * stride]))
       w = g;
   return w;
+}
+
+// ---- event-triggered re-planning (include/altro_trigger.h): THE rule, host and device ----------------------------------
+// The reason instance b is re-planned, 0 if it is not: the OR of the criteria that hold.  `tracked`: the statistics of the
+// segment just tracked, null without any (the three tracked criteria are off); `status`: what altro_get_stats reports for
+// the instance; `ahead`: the statistics of the lookahead's track, read only with rule.lookahead > 0.  Every comparison is
+// !(v <= tol): a NaN triggers.  kTrigFirst is the run's own, never set here.
+ALTRO_HD int trigger_reason(const TriggerRule& rule, int age, const TrackStats* tracked, int status, const TrackStats* ahead) {
+  int why = 0;
+  if (age >= rule.max_age) why |= kTrigAge;
+  if (tracked) {
+    if (rule.dx_tol >= 0.0 && !(tracked->max_dx <= rule.dx_tol)) why |= kTrigDeviation;
+    if (rule.viol_tol >= 0.0 && !(tracked->violation <= rule.viol_tol)) why |= kTrigViolation;
+    if (tracked->status != ALTRO_UNSOLVED) why |= kTrigLimit;
+  }
+  if (rule.on_unsolved && status != ALTRO_SOLVED) why |= kTrigUnsolved;
+  if (rule.lookahead > 0 && ahead && (ahead->status != ALTRO_UNSOLVED || !(ahead->violation <= rule.ahead_tol))) why |= kTrigAhead;
+  return why;
 }
 // knots per synchronisation of the persistent kernel's knot loop (the batched sweeps: 2), see producer_syncs_after.
 // Round 2 (hardware barriers only): 4 measured 5.24 -> 5.30 ms on config 2, 5.03 -> 4.74 ms on config 3, the headline kept
@@ -574,6 +630,9 @@ class EngineBase {
   virtual altro_status CovPropagate(const CovArgs& call, int on_device) = 0;
   virtual altro_status CovInflate(int index, const double* base, int rows, int per_instance, double kappa, const double* rpos,
                                   int on_device) = 0;
+  // event-triggered re-planning (include/altro_trigger.h): the rule for every instance (k_mpc_trigger; the lookahead through
+  // k_mpc_track); changes nothing on the engine.  The loop kind kLoopTriggered keeps ages, masks and reasons on the device.
+  virtual altro_status Trigger(const TriggerArgs& call, int on_device, bool ilqr_mode) = 0;
   virtual const char* LastError() = 0;
 };
 

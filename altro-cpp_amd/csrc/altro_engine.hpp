@@ -1265,13 +1265,91 @@ class Engine final : public EngineBase {
     return ALTRO_OK;
   }
 
+  // ---- event-triggered re-planning (include/altro_trigger.h) ----------------------------------------
+  // What the trigger calls refuse once the device state exists, before any device work: what Advance refuses (the rule
+  // decides over a plan that moves along the horizon) and the cost-to-go records that a masked solve refuses.
+  altro_status TriggerCheck(const char* who) {
+    if (kTimeVarying || A_.hk || A_.knot_model) {
+      err_ = std::string(who) + ": per-knot steps, times or models (a time-varying or discrete user model included) do not move "
+             "along the horizon yet";
+      return ALTRO_UNSUPPORTED;
+    }
+    if (A_.record_ctg) {
+      err_ = std::string(who) + ": a masked solve does not record the cost-to-go (altro_set_record_ctg): switch the records off";
+      return ALTRO_UNSUPPORTED;
+    }
+    return ALTRO_OK;
+  }
+  // The lookahead's track -- one sample, no disturbance, statistics only, into `ahead` -- and k_mpc_trigger, on the engine's
+  // stream (every array of `g` in device memory).  Reads the engine's arrays only.
+  altro_status LaunchTrigger(const TriggerArgs& g, TrackStats* ahead, bool ilqr_mode) {
+    const bool look = g.rule.lookahead > 0;
+    if (look) {
+      TrackArgs t = g.track;
+      t.steps = g.rule.lookahead;
+      t.S = 1;
+      t.dx0 = t.w = nullptr;
+      t.u_lo = g.u_lo;
+      t.u_hi = g.u_hi;
+      t.X_cl = t.U_cl = t.x_end = nullptr;
+      t.stats = ahead;
+      ALTRO_TRY(LaunchTrack(t));
+    }
+    hipLaunchKernelGGL((k_mpc_trigger<0>), GridB(), dim3(kBlock), 0, stream_, g.rule, g.tracked, g.age,
+                       (const int*)(ilqr_mode ? A_.status : A_.status_al), (const TrackStats*)(look ? ahead : nullptr), g.mask, g.reason, B_);
+    return ALTRO_OK;
+  }
+  // Host arrays are staged through ONE device block that lives for the call (ints and bytes packed into doubles on the
+  // host, as SetSolveMask packs its bytes); device arrays are used where they are.  The lookahead's statistics live in
+  // that block for either caller.  No flag of the engine changes.
+  altro_status Trigger(const TriggerArgs& call, int on_device, bool ilqr_mode) override {
+    const TriggerRule& r = call.rule;
+    if (r.max_age < 1 || r.lookahead < 0 || r.lookahead > N_ || (call.u_lo == nullptr) != (call.u_hi == nullptr)) {
+      err_ = "altro_mpc_trigger: max_age must be positive, lookahead must lie in [0, N], and u_lo / u_hi come together";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_TRY(TriggerCheck("altro_mpc_trigger"));
+    if (r.lookahead > 0 && (!StepOk() || !RefOk())) return ALTRO_NOT_READY;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    const bool host = !on_device;
+    const size_t B = (size_t)B_;
+    const Parts<6> p = TriggerStageParts(m, B, host && call.tracked, host && call.age, host && call.u_lo, host && call.mask,
+                                         host && call.reason, r.lookahead > 0);
+    DevBlock<double> stage;
+    if (p.total() > 0 && stage.alloc(p.total()) != hipSuccess) {
+      err_ = "altro_mpc_trigger: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
+      return ALTRO_HIP_ERROR;
+    }
+    std::vector<double> age_h(p.cnt[1], 0.0), mask_h(p.cnt[3], 0.0), why_h(p.cnt[4], 0.0);
+    if (p.cnt[1]) std::memcpy(age_h.data(), call.age, B * sizeof(int));
+    Staged<6> sg(on_device != 0, stage.get(), p, stream_);
+    TriggerArgs g = call;
+    if (host) {
+      g.tracked = reinterpret_cast<const TrackStats*>(sg.in(0, reinterpret_cast<const double*>(call.tracked)));
+      g.age = reinterpret_cast<const int*>(sg.in(1, p.cnt[1] ? age_h.data() : nullptr));
+      g.u_lo = sg.in(2, call.u_lo, 0, m);
+      g.u_hi = sg.in(2, call.u_hi, m, m);
+      g.mask = reinterpret_cast<unsigned char*>(sg.out(3, p.cnt[3] ? mask_h.data() : nullptr));
+      g.reason = reinterpret_cast<int*>(sg.out(4, p.cnt[4] ? why_h.data() : nullptr));
+    }
+    const altro_status st = sg.ok() ? LaunchTrigger(g, reinterpret_cast<TrackStats*>(sg.part(5)), ilqr_mode) : ALTRO_OK;
+    const hipError_t e = sg.finish(st == ALTRO_OK);
+    ALTRO_TRY(st);
+    ALTRO_HIP_CHECK(e);
+    if (p.cnt[3]) std::memcpy(call.mask, mask_h.data(), B);
+    if (p.cnt[4]) std::memcpy(call.reason, why_h.data(), B * sizeof(int));
+    return ALTRO_OK;
+  }
+
   // ---- one closed-loop run (LoopSpec, altro_common.hpp) ----------------------------------------------
   // What lives on the device between LoopBegin and LoopEnd: one block of doubles, one of ints, one cycle counter.  The plain,
   // multi-start and team kinds log through k_mpc_advance (LogSlot): rows of X, U per instance, iterations and statuses
   // [B][cycles].  The closed-loop states of the tracked kind are the TRACKED ones, so it does not use that log: k_mpc_track
   // writes one cycle's rows, two strided copies append them, and iterations, statuses and TrackStats are recorded cycle-major
   // [cycles][B] (one contiguous row per cycle) and transposed on the host in LoopEnd.  One layout for both takes a kernel
-  // change.
+  // change.  The triggered kind is the tracked kind with three more things on the device: the age of every plan, the mask
+  // and the reasons the cycle's rule evaluation (LaunchTrigger) leaves for the next cycle's solve, and the log of the
+  // reasons.  Its cycle log is written by k_trigger_log, under the mask the cycle's solve ran with.
   struct LoopRun {
     LoopSpec spec{};  // (its host pointers belong to the C call that drives the run)
     int cycle = 0;    // cycles that went through
@@ -1282,6 +1360,11 @@ class Engine final : public EngineBase {
     double *w = nullptr, *dU = nullptr, *clear = nullptr;  // multi-start, team: w and dU on the device; team: [B / A][cycles]
     double *Xc = nullptr, *Uc = nullptr, *xend = nullptr, *wc = nullptr, *ulo = nullptr, *uhi = nullptr;  // tracked: one cycle's
     TrackStats* stats = nullptr;                                                                          // arrays; [cycles][B]
+    // triggered: reasons [cycles][B]; ages [B]; the reasons [B] and the mask bytes [B] of the solve to come
+    int *why_log = nullptr, *age = nullptr, *why = nullptr;
+    unsigned char* next_mask = nullptr;
+    DevBlock<double> ahead;  // triggered, with a lookahead: its statistics [B]
+    bool masked = false;     // triggered: the run has put its mask on the handle
   };
   altro_status LoopBegin(const LoopSpec& s) override {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
@@ -1295,15 +1378,24 @@ class Engine final : public EngineBase {
       }
       ALTRO_TRY(TeamRadius(s.radius));
     }
+    const bool trig = s.kind == kLoopTriggered;
+    if (trig) {
+      ALTRO_TRY(TriggerCheck("altro_mpc_run_triggered"));
+      if (mask_.on) {
+        err_ = "altro_mpc_run_triggered: the handle carries a solve mask; the run sets its own (clear it with altro_set_solve_mask(h, NULL))";
+        return ALTRO_UNSUPPORTED;
+      }
+    }
     LoopRun r;
     r.spec = s;
     const size_t B = (size_t)B_, cycles = (size_t)s.cycles;
-    const bool tracked = s.kind == kLoopTracked;
+    const bool tracked = s.kind == kLoopTracked || trig;
     const Parts<8> pt = TrackedRunParts(n, m, B, cycles, (size_t)s.shift);
     const Parts<5> pp = PlainRunParts(n, m, B, cycles, (size_t)s.shift, s.w && (ms || team),
                                       ms && s.dU ? (size_t)(s.dU_per_instance ? B_ : s.G) * N_ * m : 0, team ? (size_t)(B_ / s.A) * cycles : 0);
-    if (r.i.alloc(2 * B * cycles + (ms ? (size_t)(B_ / s.G) * cycles : 0)) != hipSuccess ||
-        r.d.alloc(tracked ? pt.total() : pp.total()) != hipSuccess) {
+    if (r.i.alloc(2 * B * cycles + (ms ? (size_t)(B_ / s.G) * cycles : 0) + (trig ? B * cycles + 2 * B + (B + 3) / 4 : 0)) != hipSuccess ||
+        r.d.alloc(tracked ? pt.total() : pp.total()) != hipSuccess ||
+        (trig && s.rule.lookahead > 0 && r.ahead.alloc(B * (sizeof(TrackStats) / sizeof(double))) != hipSuccess)) {
       err_ = "closed-loop run: out of device memory for the logs";
       return ALTRO_HIP_ERROR;
     }
@@ -1332,6 +1424,25 @@ class Engine final : public EngineBase {
       r.clear = sg.part(4);
       if (sg.copies() > 0) ALTRO_HIP_CHECK(sg.finish());
     }
+    if (trig) {
+      // cycle 0: everyone, reason kTrigFirst, age 0; the counts per slice are the slices' sizes
+      r.why_log = r.it + 2 * B * cycles;
+      r.age = r.why_log + B * cycles;
+      r.why = r.age + B;
+      r.next_mask = reinterpret_cast<unsigned char*>(r.why + B);
+      ALTRO_TRY(MaskBlocks());
+      ALTRO_HIP_CHECK(hipMemsetAsync(r.age, 0, B * sizeof(int), stream_));
+      ALTRO_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.why), kTrigFirst, B, stream_));
+      ALTRO_HIP_CHECK(hipMemsetAsync(r.next_mask, 1, B, stream_));
+      const MaskSlices sl = MaskSlicesNow();
+      int known[kMaxSweepChains] = {};
+      for (int c = 0; c < sl.n; ++c) known[c] = sl.hi[c] - sl.lo[c];
+      r.masked = true;  // (from here on LoopEnd takes the mask off again)
+      hm_.run = std::move(r);
+      ALTRO_TRY(SumInstanceIterations());  // (of the last solve before the run, as SetSolveMask)
+      ALTRO_TRY(CompactMask(hm_.run.next_mask, sl, known));
+      return Sync();
+    }
     hm_.run = std::move(r);
     return ALTRO_OK;
   }
@@ -1349,11 +1460,18 @@ class Engine final : public EngineBase {
     const LogSlot log{r.Xlog, r.Ulog, r.it, r.it + cb, r.cycle, s.cycles};
     if (s.kind == kLoopPlain) {
       ALTRO_TRY(Advance(s.shift, nullptr, w, 0, step.reset_pen, &log));
-    } else if (s.kind == kLoopTracked) {
+    } else if (s.kind == kLoopTracked || s.kind == kLoopTriggered) {
+      const bool trig = s.kind == kLoopTriggered;
       const size_t sh = (size_t)s.shift, Lk = (size_t)s.cycles * sh;
       // the statistics of the solve behind this cycle
-      ALTRO_HIP_CHECK(hipMemcpyAsync(r.it + c * B, A_.it_total, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
-      ALTRO_HIP_CHECK(hipMemcpyAsync(r.it + cb + c * B, A_.status_al, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+      if (trig) {  // (of the instances it ran; their ages start again, and every age counts the cycle being followed)
+        hipLaunchKernelGGL((k_trigger_log<0>), GridB(), dim3(kBlock), 0, stream_, (const unsigned char*)hm_.mask.get(), (const int*)A_.it_total,
+                           (const int*)(step.ilqr_mode ? A_.status : A_.status_al), (const int*)r.why, r.age, r.it + c * B, r.it + cb + c * B,
+                           r.why_log + c * B, B_);
+      } else {
+        ALTRO_HIP_CHECK(hipMemcpyAsync(r.it + c * B, A_.it_total, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+        ALTRO_HIP_CHECK(hipMemcpyAsync(r.it + cb + c * B, A_.status_al, B * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+      }
       if (w) ALTRO_HIP_CHECK(hipMemcpyAsync(r.wc, w, B * sh * n * sizeof(double), hipMemcpyHostToDevice, stream_));
       TrackArgs g = step.track;
       g.steps = s.shift;
@@ -1373,6 +1491,20 @@ class Engine final : public EngineBase {
       ALTRO_HIP_CHECK(hipMemcpy2DAsync(r.Ulog + c * sh * m, Lk * m * sizeof(double), r.Uc, sh * m * sizeof(double), sh * m * sizeof(double), B,
                                        hipMemcpyDeviceToDevice, stream_));
       ALTRO_TRY(Advance(s.shift, r.xend, nullptr, 1, step.reset_pen, nullptr));
+      if (trig && r.cycle + 1 < s.cycles) {
+        // the rule over what this cycle tracked, for the next cycle's solve; of the mask only the slices' counts come back
+        TriggerArgs g{};
+        g.rule = s.rule;
+        g.tracked = r.stats + c * B;
+        g.age = r.age;
+        g.u_lo = r.ulo;
+        g.u_hi = r.uhi;
+        g.mask = r.next_mask;
+        g.reason = r.why;
+        g.track = step.track;
+        ALTRO_TRY(LaunchTrigger(g, reinterpret_cast<TrackStats*>(r.ahead.get()), step.ilqr_mode));
+        ALTRO_TRY(CompactMask(r.next_mask, MaskSlicesNow(), nullptr));
+      }
     } else if (s.kind == kLoopMultiStart) {
       ctg_replayable_ = false;
       LaunchMsSelect(s.G, step.ilqr_mode, hm_.ms_win.get(), r.win, s.cycles, r.cycle);
@@ -1397,6 +1529,22 @@ class Engine final : public EngineBase {
     const LoopSpec& s = r.spec;
     hipError_t e = hipSetDevice(desc_.device_id);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (r.masked) {  // a triggered run leaves the handle without a mask, whatever happened (as SetSolveMask clears one)
+      if (e == hipSuccess && r.cycle == s.cycles) {
+        (void)SumInstanceIterations();  // (hm_.mask is still the last solve's)
+      } else if (e == hipSuccess && r.cycle > 0 && timing_.instance_iterations < 0) {
+        // a run that broke off: hm_.mask is the NEXT solve's already, so the sum of the last solve that went through comes
+        // from its row of the log, which holds 0 for the instances it skipped
+        std::vector<int> it((size_t)B_);
+        if (CopySync(it.data(), r.it + (size_t)(r.cycle - 1) * B_, it.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
+          long long tot = 0;
+          for (int v : it) tot += v;
+          timing_.instance_iterations = tot;
+        }
+      }
+      mask_.on = false;
+    }
+    const bool tracked = s.kind == kLoopTracked || s.kind == kLoopTriggered;
     auto down = [&](void* dst, const void* src, size_t bytes) {
       if (e == hipSuccess && dst) e = CopySync(dst, src, bytes, hipMemcpyDeviceToHost);
     };
@@ -1404,7 +1552,7 @@ class Engine final : public EngineBase {
       const size_t B = (size_t)B_, cycles = (size_t)s.cycles, Lk = cycles * s.shift, cb = cycles * B;
       down(o.X_cl, r.Xlog, B * (Lk + 1) * n * sizeof(double));
       down(o.U_cl, r.Ulog, B * Lk * m * sizeof(double));
-      if (s.kind != kLoopTracked) {
+      if (!tracked) {
         down(o.iterations, r.it, cb * sizeof(int));
         down(o.status, r.it + cb, cb * sizeof(int));
       } else {  // recorded [cycles][B], handed out [B][cycles]
@@ -1416,6 +1564,12 @@ class Engine final : public EngineBase {
               if (o.iterations) o.iterations[b * cycles + c] = h[c * B + b];
               if (o.status) o.status[b * cycles + c] = h[cb + c * B + b];
             }
+        }
+        if (o.reason && s.kind == kLoopTriggered) {
+          std::vector<int> h(cb);
+          down(h.data(), r.why_log, h.size() * sizeof(int));
+          for (size_t c = 0; c < cycles && e == hipSuccess; ++c)
+            for (size_t b = 0; b < B; ++b) o.reason[b * cycles + c] = h[c * B + b];
         }
         if (o.track) {
           std::vector<TrackStats> h(cb);
@@ -2350,7 +2504,9 @@ class Engine final : public EngineBase {
         err_ = "a masked solve does not record the cost-to-go (altro_set_record_ctg): clear the mask or switch the records off";
         return ALTRO_UNSUPPORTED;
       }
-      ALTRO_TRY(SumInstanceIterations());
+      // (not inside a triggered run: hm_.mask is the coming solve's there, and the sum would bring every instance's count to
+      //  the host between two cycles; LoopEnd sums what the run's last solve ran)
+      if (!hm_.run.masked) ALTRO_TRY(SumInstanceIterations());
       ALTRO_TRY(Recompact());
       if (mask_.total == 0) {  // nobody takes part: nothing is launched, nothing changes
         std::memset(&timing_, 0, sizeof(timing_));

@@ -6182,4 +6182,46 @@ __global__ __launch_bounds__(kMaskThreads) void k_team_turn_mask(unsigned char* 
   if (b < B) mask[b] = (b % A == a) ? 1 : 0;
 }
 
+// -------------------------------------------------------------------------------------------------
+// Event-triggered re-planning (include/altro_trigger.h): which instances get a new plan.
+//
+// k_mpc_trigger  ONE LANE PER INSTANCE evaluates THE rule (trigger_reason, altro_common.hpp) over the instance's tracked
+//                statistics, age, status and -- with a lookahead -- the statistics k_mpc_track has just written for the next
+//                knots of the plan as it stands.  Every input array is [B] with the instance as the index, so a wave reads 64
+//                neighbouring elements of each (40-byte TrackStats: 2560 contiguous bytes per wave) and stores 64 bytes of
+//                mask and 256 of reasons; about 100 bytes per instance, no LDS, no arithmetic to speak of.  Model-independent.
+//                Every pointer but `status` may be null (TriggerArgs); only `mask` and `reason` are written.
+// k_trigger_log  the masked write of a triggered run's cycle log, one lane per instance, behind the cycle's solve: row `c` of
+//                the iteration, status and reason logs ([cycles][B], one contiguous row per cycle, as the tracked kind
+//                records them) -- the iterations and the reason of an instance the solve ran, 0 for one it skipped -- and the
+//                age the cycle's rule evaluation will read: 0 for a solved instance, plus the cycle that is being followed.
+// (The template parameter is always 0: one definition per program, as k_mask_compact.)
+// -------------------------------------------------------------------------------------------------
+template <int kDummy>
+__global__ __launch_bounds__(kBlock) void k_mpc_trigger(TriggerRule rule, const TrackStats* __restrict__ tracked, const int* __restrict__ age,
+                                                        const int* __restrict__ status, const TrackStats* __restrict__ ahead,
+                                                        unsigned char* __restrict__ mask, int* __restrict__ reason, int B) {
+  const int b = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+  if (b >= B) return;
+  TrackStats seg{}, look{};
+  if (tracked) seg = tracked[b];
+  if (ahead) look = ahead[b];
+  const int why = trigger_reason(rule, age ? age[b] : 0, tracked ? &seg : nullptr, status[b], ahead ? &look : nullptr);
+  if (mask) mask[b] = why != 0 ? 1 : 0;
+  if (reason) reason[b] = why;
+}
+template <int kDummy>
+__global__ __launch_bounds__(kBlock) void k_trigger_log(const unsigned char* __restrict__ mask, const int* __restrict__ it_total,
+                                                        const int* __restrict__ status, const int* __restrict__ why,
+                                                        int* __restrict__ age, int* __restrict__ it_log, int* __restrict__ st_log,
+                                                        int* __restrict__ why_log, int B) {
+  const int b = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+  if (b >= B) return;
+  const bool in = mask[b] != 0;
+  it_log[b] = in ? it_total[b] : 0;
+  st_log[b] = status[b];
+  why_log[b] = in ? why[b] : 0;
+  age[b] = (in ? 0 : age[b]) + 1;
+}
+
 }  // namespace altro_hip

@@ -42,6 +42,7 @@
 #include "../altro_team.h"
 #include "../altro_covariance.h"
 #include "../altro_subset.h"
+#include "../altro_trigger.h"
 
 namespace altro {
 
@@ -1568,6 +1569,27 @@ class AugmentedLagrangianiLQR {
                        double* X_cl, double* U_cl, altro_track_stats* stats = nullptr) {
     ilqr_solver_.PushOptions();
     detail::Check(Handle(), altro_mpc_track(Handle(), steps, samples, dx0, w, u_lo, u_hi, X_cl, U_cl, stats), "altro_mpc_track");
+  }
+  // Event-triggered re-planning (include/altro_trigger.h).  EvaluateTrigger: the rule for every instance over the statistics of
+  // the segment just tracked (tracked [B], null: those criteria are off) and the plans' ages (age [B], null: 0) -> mask [B],
+  // reason [B] of ALTRO_TRIGGER_* bits; changes nothing on the solver.  RunTriggered: `cycles` x (solve the instances the rule
+  // triggered -- everyone in cycle 0 --; track `shift` knots under w[c]; advance from the tracked state; evaluate the rule), with
+  // the logs of altro_mpc_run_tracked plus reason [B][cycles].  Thin calls giving the C calls' bits.
+  void EvaluateTrigger(const altro_trigger_rule& rule, const altro_track_stats* tracked, const int* age, const double* u_lo,
+                       const double* u_hi, unsigned char* mask, int* reason = nullptr) {
+    ilqr_solver_.PushOptions();
+    detail::Check(Handle(), altro_mpc_trigger(Handle(), &rule, tracked, age, u_lo, u_hi, mask, reason), "altro_mpc_trigger");
+  }
+  void RunTriggered(int cycles, int shift, const double* w, const double* u_lo, const double* u_hi, const altro_trigger_rule& rule,
+                    double* X_cl, double* U_cl, int* iterations = nullptr, int* status = nullptr, altro_track_stats* track = nullptr,
+                    int* reason = nullptr) {
+    ilqr_solver_.Push();
+    ilqr_solver_.PrepareSolve();
+    detail::Check(Handle(), altro_mpc_run_triggered(Handle(), cycles, shift, w, u_lo, u_hi, &rule, X_cl, U_cl, iterations, status, track, reason),
+                  "altro_mpc_run_triggered");
+    ilqr_solver_.Pull(true, true);
+    status_ = ilqr_solver_.StatusAL();
+    ilqr_solver_.AfterSolve();
   }
   // The closed-loop covariance of the solved plan under its gains (include/altro_covariance.h), ON THE DEVICE: what a caller
   // of the reference composes on the host from GetFeedbackGain() and the knots' dynamics Jacobians,
