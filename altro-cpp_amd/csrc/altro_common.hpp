@@ -418,7 +418,8 @@ enum TailReportWord {
   kRwSyncErr = 3,      // a forward wave gave up waiting for a sequence word
   kRwHandovers = 4,    // confirmed joints between twin workgroups (depends on timing)
   kRwClaims = 5,       // claims of pool workgroups, at every level (depends on timing)
-  kRwGroupLoops = 6,   // most iterations any ONE workgroup ran (a twin or its primary: their share)
+  kRwGroupLoops = 6,   // most iterations any ONE job ran (a primary's or a pool workgroup's share; a worker of the
+                       // worker grid runs several jobs, each reports for itself)
   kRwWords = 8
 };
 // fh (wave 0's backward pass) and fh2 (the fourth wave's speculative one): what a backward pass hands to the forward pass
@@ -507,6 +508,7 @@ struct FusedLds {
   ALTRO_HD int oCost() const { return oSync() + kSyWords * (int)sizeof(int); }  // [N + 1] knot costs, padded to a pair
   ALTRO_HD int oCvalAhead() const { return oCost() + ((N + 2) & ~1) * kE; }  // [rows] constraint values computed ahead
   ALTRO_HD int used() const { return oCvalAhead() + blk.rowsP() * kE; }
+  ALTRO_HD int oTicket() const { return used(); }  // the worker grid's ticket word: the first int of the reserve below
   // the engine has always asked for a little more than the kernel lays out (8 doubles behind the sequence words, N + 4
   // knot costs); the LDS size decides how many workgroups share a CU, so the reserve stays
   ALTRO_HD size_t bytes() const { return (size_t)used() + 8 * kD + (size_t)(N + 4 - ((N + 2) & ~1)) * kE; }

@@ -74,6 +74,9 @@ struct Switches {
   int twin_min = tw_min_share(kTwinDefaultMin);  // ALTRO_HIP_TWIN_MIN=n: iterations both shares of a split must hold (>= kTwinMinFloor)
   int twin_spread = kTwinDefaultSpread;  // ALTRO_HIP_TWIN_SPREAD=s: the pool treats segments within 2^s iterations left of each other as equals (0: the longest first, for all)
   int twin_misclaim = 0;           // ALTRO_HIP_TWIN_MISCLAIM=k (tests): every k-th claim assumes a regularisation one ulp off
+  // ALTRO_HIP_TAIL_WORKERS: the persistent launch as a grid of resident workers that take its jobs by ticket.  Unset: as
+  // many as the device holds at once; 0: the one-shot grid, a workgroup per job; n: at most n workers (tests)
+  int tail_workers = kTailWorkersDefault;
   const char* sweep_log = nullptr; // ALTRO_HIP_SWEEP_LOG[=all]: timeline of the chains of sweeps
   bool loop_log = false;           // ALTRO_HIP_LOOP_LOG: phase log of the device-side loop
   bool force_valu_backward = false, force_coop_backward = false;  // ALTRO_HIP_BACKWARD = valu | coop: a fallback backward kernel (tests)
@@ -119,6 +122,7 @@ struct Switches {
     if (const char* e = env("ALTRO_HIP_TWIN_MIN")) twin_min = tw_min_share(atoi(e));
     if (const char* e = env("ALTRO_HIP_TWIN_SPREAD")) twin_spread = std::max(0, std::min(kTwinMaxSpread, atoi(e)));
     if (const char* e = env("ALTRO_HIP_TWIN_MISCLAIM")) twin_misclaim = std::max(0, atoi(e));
+    if (const char* e = env("ALTRO_HIP_TAIL_WORKERS")) tail_workers = std::max(0, atoi(e));
     sweep_log = env("ALTRO_HIP_SWEEP_LOG");
     loop_log = env("ALTRO_HIP_LOOP_LOG") != nullptr;
     force_valu_backward = Is(env("ALTRO_HIP_BACKWARD"), "valu");
@@ -3004,19 +3008,31 @@ class Engine final : public EngineBase {
         //  32.2 - 32.4 ms at 12 against 32.6 - 32.7 at 4, inside a spread of 0.8; profiles/tail_endgame_experiments.txt.)
         const int min_share = any_split ? std::max(sw_.twin_min, kTwinSegMin) : sw_.twin_min;
         const int pool = std::min(up_.twin_cap, std::max(ninst, num_cus_ - ninst));
-        tw = TwinCtl{up_.d_twin_box, up_.d_twin_box + (size_t)2 * up_.twin_cap * kTwWords, ninst, up_.twin_cap, Bp_ - up_.twin_cap, kTwinLag, sw_.twin_debug ? 1 : 0,
-                     pool, any_split ? 1 : sw_.twin_depth, min_share, sw_.twin_spread, sw_.twin_misclaim};
+        unsigned long long* const state = up_.d_twin_box + (size_t)2 * up_.twin_cap * kTwWords;
+        tw = TwinCtl{up_.d_twin_box, state, ninst, up_.twin_cap, Bp_ - up_.twin_cap, kTwinLag, sw_.twin_debug ? 1 : 0,
+                     pool, any_split ? 1 : sw_.twin_depth, min_share, sw_.twin_spread, sw_.twin_misclaim,
+                     0, reinterpret_cast<int*>(state + (size_t)2 * up_.twin_cap)};
       }
-      const dim3 g(ninst + (tw.base > 0 ? tw.npool : 0)), b3(kFwdWaves * kBlock), b4((kFwdWaves + 1) * kBlock);
-      timing_.twin_workgroups = tw.base > 0 ? (int)g.x - ninst : 0;  // twin workgroups of this launch
+      const int npool = tw.base > 0 ? tw.npool : 0;
+      const dim3 b3(kFwdWaves * kBlock), b4((kFwdWaves + 1) * kBlock);
+      timing_.twin_workgroups = npool;  // pool jobs of this launch (the one-shot grid: its pool workgroups)
       // The variant of (circles, speculation, segments).  Columns of split streaks may be in the lists once a chain has
       // split: then the variants that verify / retire / cancel them in the loop's bookkeeping step (seg_on holds only
       // under the default speculation modes); every other launch runs the kernels as they were before the segments existed.
       ForEachFusedVariant([&](auto v) {
         using V = decltype(v);
-        if (V::circles == circles && V::spec == spec && V::segments == any_split)
-          hipLaunchKernelGGL((k_sweep_fused<T, M, V::circles, V::spec, V::segments>), g, V::spec == kSpecOff ? b3 : b4, fused_lds_bytes_,
-                             stream_, A, up_.d_pd, pd_, r.d, r.mode, 1, out, tw);
+        if (V::circles == circles && V::spec == spec && V::segments == any_split) {
+          const dim3 blk = V::spec == kSpecOff ? b3 : b4;
+          // The WORKER grid (TwinCtl::workers, k_sweep_fused): as many workgroups as the device holds at once, by the
+          // occupancy query for this variant and its LDS (1 per CU today), each taking the launch's jobs by ticket.
+          // ALTRO_HIP_TAIL_WORKERS=0: the one-shot grid, a workgroup per job; =n: at most n workers (tests).  A launch
+          // without twins has no pool to keep fed and keeps the one-shot grid.
+          if (tw.base > 0 && sw_.tail_workers != 0)
+            tw.workers = tail_worker_count(ninst, npool, num_cus_, FusedPerCu(V::Fn(), (int)blk.x), sw_.tail_workers);
+          const dim3 g(tail_grid(ninst, npool, tw.workers));
+          hipLaunchKernelGGL((k_sweep_fused<T, M, V::circles, V::spec, V::segments>), g, blk, fused_lds_bytes_, stream_, A, up_.d_pd, pd_,
+                             r.d, r.mode, 1, out, tw);
+        }
       });
       if (r.prof) hipEventRecord(ProfEvent(r.nev++), stream_);
       r.persistent_launched = true;
@@ -3109,7 +3125,19 @@ class Engine final : public EngineBase {
     timing_.sweeps = sweeps;
     return ALTRO_OK;
   }
-  size_t TwinBoxWords() const { return (size_t)2 * up_.twin_cap * (kTwWords + 1); }
+  // (mailboxes, state words, and the two ticket counters of the worker grid in one more word: cleared together)
+  size_t TwinBoxWords() const { return (size_t)2 * up_.twin_cap * (kTwWords + 1) + 1; }
+  // workgroups of a k_sweep_fused variant that share a CU at the upload's LDS size (the runtime's answer, asked once)
+  int FusedPerCu(const void* fn, int threads) {
+    if (fn != fused_per_cu_fn_ || fused_lds_bytes_ != fused_per_cu_lds_) {
+      int n = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, fused_lds_bytes_) != hipSuccess) n = 0;
+      fused_per_cu_ = n;
+      fused_per_cu_fn_ = fn;
+      fused_per_cu_lds_ = fused_lds_bytes_;
+    }
+    return fused_per_cu_;
+  }
   // ALTRO_HIP_TWIN_DEBUG: the twins' mailboxes after the persistent launch, slot by slot (debug print only)
   altro_status DumpTwinMailboxes() {
     const int nbox = 2 * up_.twin_cap;
@@ -3134,15 +3162,15 @@ class Engine final : public EngineBase {
         const int limit = timing_.twin_claims <= 48 || sw_.twin_debug_all ? 1 : 8;  // (every segment of a small launch, every eighth otherwise)
         if ((shown++ % limit) == 0)
           fprintf(stderr, "  segment %4d depth %d inst %d from %d: it %d..%d hand %d | start %.0f go %.0f cloned %.0f first %.0f snap %.0f claimed %.0f "
-                  "done %.0f (loops %llu) verdict %.0f handed %.0f commit %.0f\n", s, (int)w[kTwGen], (int)w[kTwInst] - 1, (int)w[kTwPred] - 1,
+                  "done %.0f (loops %llu) verdict %.0f handed %.0f commit %.0f | xcd %d worker %d\n", s, (int)w[kTwGen], (int)w[kTwInst] - 1, (int)w[kTwPred] - 1,
                   (int)(w[kTwClaim] >> 32), (int)w[kTwEnd], (int)(w[kTwHand] & 3), us(kTsTStart), us(kTsTGo), us(kTsTCloned), us(kTsTFirst), us(kTsPSnap),
-                  us(kTsPClaim), us(kTsTDone), ts[kTsTLoops], us(kTsTVerdict), us(kTsPHand), us(kTsTCommit));
+                  us(kTsPClaim), us(kTsTDone), ts[kTsTLoops], us(kTsTVerdict), us(kTsPHand), us(kTsTCommit), (int)ts[kTsXcd] - 1, (int)ts[kTsWorker] - 1);
       }
       if (sw_.twin_debug_all && s < up_.twin_cap && ts[kTsPStart] != 0)
-        fprintf(stderr, "  primary %4d: start %.0f snap %.0f claimed %.0f handed %.0f end %.0f\n", s, us(kTsPStart), us(kTsPSnap), us(kTsPClaim),
-                us(kTsPHand), us(kTsPEnd));
+        fprintf(stderr, "  primary %4d: start %.0f snap %.0f claimed %.0f handed %.0f end %.0f | xcd %d worker %d\n", s, us(kTsPStart), us(kTsPSnap), us(kTsPClaim),
+                us(kTsPHand), us(kTsPEnd), (int)ts[kTsXcd] - 1, (int)ts[kTsWorker] - 1);
       if (sw_.twin_debug_all && s >= up_.twin_cap && w[kTwClaim] == 0 && ts[kTsTIdleEnd] != 0)
-        fprintf(stderr, "  idle %4d: start %.0f left %.0f\n", s, us(kTsTStart), us(kTsTIdleEnd));
+        fprintf(stderr, "  idle %4d: start %.0f left %.0f | xcd %d worker %d\n", s, us(kTsTStart), us(kTsTIdleEnd), (int)ts[kTsXcd] - 1, (int)ts[kTsWorker] - 1);
       if (w[kTwWhy] != 0) {
         why[w[kTwWhy] & 7]++;
         if (why[w[kTwWhy] & 7] <= 3)
@@ -3307,6 +3335,9 @@ class Engine final : public EngineBase {
   size_t fwd_lds_bytes_ = 0, fwd_shared_bytes_ = 0, fwd_per_inst_bytes_ = 0;
   int num_cus_ = 256;
   bool twin_box_clean_ = false;  // this solve's k_begin_solve has cleared the twins' mailboxes
+  const void* fused_per_cu_fn_ = nullptr;  // FusedPerCu(): the variant and LDS size the answer below belongs to
+  size_t fused_per_cu_lds_ = 0;
+  int fused_per_cu_ = 0;
   static constexpr int kMaxChains = kMaxSweepChains;
   static constexpr int kDefaultChains = 4;
   bool counted_chained_ = false;

@@ -22,7 +22,8 @@
 //                    k_forward is the single-wave, HBM-reading fallback.
 //   k_sweep_fused    the tail of a batched solve: one workgroup per straggler instance runs whole
 //                    iterations (expansions, MFMA backward pass, three-wave forward pass) in a loop
-//                    until its instance is finished -- one persistent launch, no host in the loop.
+//                    until its instance is finished -- one persistent launch, no host in the loop;
+//                    its workgroups are resident workers that take instances (jobs) by ticket.
 //
 // Instances are independent; the ones still iterating are kept in a dense list rebuilt every sweep.
 #pragma once
@@ -3991,6 +3992,8 @@ ALTRO_DEV constexpr bool spec_has_wave4(int spec) { return spec == kSpecWave || 
 //
 // So the launch carries, behind its `base` primary workgroups, a POOL of workgroups, each with a shadow column of the
 // per-instance arrays (index col0 + t: every array of DevArrays is allocated that much wider) and a mailbox of its own.
+// ("Workgroup" here and below names an IDENTITY of the launch -- block i of a grid with a workgroup per job.  On the worker
+//  grid, TwinCtl::workers, these are jobs that resident workgroups take by ticket: see k_sweep_fused.)
 // A streak is a CHAIN OF SEGMENTS [s0, s1) [s1, s2) ... [sk, end), one workgroup (WORKER) per segment, under ONE rule:
 //   * a worker inside a streak -- the primary or a pool workgroup alike -- publishes where it is: once per streak the
 //     counters and the regularisation its streak began with, then one relaxed progress word per iteration; its segment's
@@ -4044,10 +4047,37 @@ struct TwinCtl {
   int spread;               // the pool's scan takes segments whose iterations left agree above bit `spread` for equals, and every pool
                             // workgroup orders equals its own way (ALTRO_HIP_TWIN_SPREAD; 0: strictly the most iterations left)
   int misclaim;             // test only (ALTRO_HIP_TWIN_MISCLAIM=k): every k-th claim assumes a regularisation one ulp off
+  int workers;              // resident workgroups that take the launch's jobs by ticket (0: one workgroup per job, the one-shot grid)
+  int* tickets;             // [kTkWords] the next primary / pool ticket, cleared with the mailboxes (behind the state words)
 };
+// WORKERS (TwinCtl::workers > 0).  A launch has JOBS: primary job s is "block s" of the one-shot grid (slot s of the list,
+// mailbox s), pool job t is "block base + t" (shadow column col0 + t, mailbox cap + t).  The one-shot grid has a workgroup
+// per job and leaves it to the dispatcher when a CU gets its next one; the worker grid has exactly as many workgroups as
+// the device holds at once, and each takes jobs by ticket until none is left (k_sweep_fused).  Host-callable for
+// tests/test_tail_workers_policy.py (altro_tail_tickets); inlined into the kernel and used by LaunchTail.
+enum TailTicket { kTkPrimary = 0, kTkPool = 1, kTkWords = 2 };
+#ifndef ALTRO_TAIL_WORKERS
+#define ALTRO_TAIL_WORKERS -1
+#endif
+constexpr int kTailWorkersDefault = ALTRO_TAIL_WORKERS;  // ALTRO_HIP_TAIL_WORKERS unset (A/B builds -DALTRO_TAIL_WORKERS=0)
+// workgroups of the launch.  asked < 0: as many as are resident at once (cus * per_cu); 0: one per job; n > 0: at most n
+ALTRO_HD int tail_worker_count(int ninst, int npool, int cus, int per_cu, int asked) {
+  const int jobs = ninst + npool, room = cus * per_cu;
+  if (asked == 0 || room <= 0) return 0;
+  int n = jobs < room ? jobs : room;
+  if (asked > 0 && asked < n) n = asked;
+  return n;
+}
+ALTRO_HD int tail_grid(int ninst, int npool, int workers) { return workers > 0 ? workers : ninst + npool; }
+// the block of the one-shot grid whose identity a ticket carries, -1 when that kind of ticket has run out
+ALTRO_HD int tail_block_of_ticket(int kind, int ticket, int ninst, int npool) {
+  if (kind == kTkPrimary) return ticket < ninst ? ticket : -1;
+  return ticket < npool ? ninst + ticket : -1;
+}
 enum TwinStamp { kTsPStart = 0, kTsPSnap = 1, kTsPClaim = 2, kTsPHand = 3, kTsPLoopsAtSnap = 4, kTsTStart = 5, kTsTGo = 6, kTsTCloned = 7,
                  kTsTFirst = 8, kTsTDone = 9, kTsTVerdict = 10, kTsTCommit = 11, kTsTLoops = 12, kTsPEnd = 13,
-                 kTsTIdleEnd = 14 /* a pool workgroup that leaves without a segment (with kTsTStart) */ };
+                 kTsTIdleEnd = 14 /* a pool workgroup that leaves without a segment (with kTsTStart) */,
+                 kTsXcd = 15 /* XCD the job ran on + 1 */, kTsWorker = 16 /* physical workgroup of the launch + 1 */ };
 // One mailbox per WORKER (a primary or a pool workgroup).  Words 0 - 6 are what the worker shows as the publisher of its
 // segment, words 7 - 14 describe the joint at which it ENTERS the chain (pool workgroups only: written by the worker when
 // it claims, answered by its predecessor).
@@ -4181,6 +4211,11 @@ ALTRO_DEV void tw_cancel_chain(const TwinCtl& tw, unsigned long long* box) {
 // The steps of k_sweep_fused.  The kernel further down is a list of them; each is force-inlined into it, so what they
 // share -- fences, tw_order(), compare-and-swaps, barriers, bounded polls -- runs in the order the kernel calls them.
 // ---------------------------------------------------------------------------------------------------------------------
+// A decision every thread of the workgroup reads from the same LDS word behind a barrier, as a wave-uniform value.  The
+// ways out of a job are such decisions; as scalar branches a job ends for a whole wave at once, which is what lets the
+// worker loop of k_sweep_fused run one job after the other (a per-lane way out of a job inside that loop would keep the
+// lanes' masks of every job alive across the whole launch).
+ALTRO_DEV bool wg_uniform(bool c) { return __builtin_amdgcn_readfirstlane(c ? 1 : 0) != 0; }
 template <class T>
 struct TailCtx {  // what every step sees: the launch's arguments, the workgroup's ff words, the thread
   const DevArrays<T>& A;
@@ -4404,7 +4439,7 @@ ALTRO_DEV bool tw_enter_clone(const TailCtx<T>& C, TwinWorker& w, int tslot, lon
   const TwinCtl& tw = C.tw;
   double* const ff = C.ff;
   const int tid = C.tid;
-  const int src_id = (int)ff[kFfClaimSource];
+  const int src_id = __builtin_amdgcn_readfirstlane((int)ff[kFfClaimSource]);
   if (src_id < 0) return false;
   w.slot = tw.cap + tslot;
   w.box = tw.box + (size_t)w.slot * kTwWords;
@@ -4457,7 +4492,7 @@ ALTRO_DEV bool tw_enter_clone(const TailCtx<T>& C, TwinWorker& w, int tslot, lon
     }
   }
   __syncthreads();
-  return ff[kFfClaimOpen] != 0.0;
+  return wg_uniform(ff[kFfClaimOpen] != 0.0);
 }
 
 // ---- B was run ahead (fourth wave) during the previous forward pass: take its results ----
@@ -4716,7 +4751,7 @@ ALTRO_DEV bool tw_commit(const TailCtx<T>& C, TwinWorker& w, int loops, int b, i
     ff[kFfCommitOk] = h == kTwOk ? 1.0 : 0.0;
   }
   __syncthreads();
-  if (ff[kFfCommitOk] == 0.0) return false;
+  if (wg_uniform(ff[kFfCommitOk] == 0.0)) return false;
   w.loops0 = (int)ff[kFfLoopsBefore];
   copy_column<T, M>(C.A, C.pd, (unsigned)b, (unsigned)b_real, kColTwinCommit, C.tid, nthreads);
   if (C.tid == 0) w.stamp(tw, kTsTCommit);
@@ -4779,27 +4814,34 @@ ALTRO_DEV void fused_init_lds(const FusedSmem<T>& S, const DevOpts& o, int tid) 
   }
 }
 
-template <class T, class M, bool CIRC, int SPEC, bool SEG = false>
-__global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) * kBlock) void k_sweep_fused(
-    DevArrays<T> A, const ProblemDesc* __restrict__ pdg, const ProblemDesc pd_arg, DevOpts o, int mode, int persistent,
-    int* sweeps_out, TwinCtl tw) {
+// ONE JOB of the launch: what block `vblock` of the one-shot grid does from its first instruction to its last -- a primary
+// slot, or a pool slot -- run until it returns.  Everything a job keeps (TwinWorker, StallWatch, loops, adopt, e_done,
+// skipped) is declared in here and starts afresh with the next job; the LDS words are set by fused_init_lds, the sequence
+// base of FwdSync restarts with loops = 0.  Returns true iff a pool job found nothing to claim and nothing can come any
+// more (tw_find_work): the worker that ran it need not look at another ticket.
+template <class T, class M, bool CIRC, int SPEC, bool SEG>
+ALTRO_DEV bool fused_job(const DevArrays<T>& A, const ProblemDesc* __restrict__ pdg, const ProblemDesc* pd, const DevOpts& o, int mode,
+                         int persistent, int* sweeps_out, const TwinCtl& tw, unsigned char* smem_raw, int vblock) {
   constexpr int kThreads = (spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) * kBlock;
   constexpr bool kWave4 = spec_has_wave4(SPEC), kSoft = SPEC == kSpecFree;
   using R = Rec<T, M::n, M::m>;
   constexpr int nm = M::n + M::m;
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const ProblemDesc* pd = &pd_arg;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  if (blockIdx.x == 0 && tid == 0) publish_count(A);
+  // (the thread's index as a value the compiler cannot follow out of the job: what a job's prologue and epilogue derive from
+  //  it -- the addresses of the staging, of a clone, of a commit -- would otherwise be hoisted in front of the worker loop and
+  //  kept in registers through every iteration: 20 more AGPRs and scratch in the SEG variants, against 10 and none this way;
+  //  profiles/tail_workers_experiments.txt #5)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int wave = tid >> 6, lane = tid & 63;
   // (twin workgroups, see TwinCtl: blocks [base, ...) of the launch are a POOL -- each serves whichever slot of the launch
   //  publishes a streak first -- and block base + t owns shadow column col0 + t)
   TwinWorker w;
-  w.is_twin = tw.base > 0 && (int)blockIdx.x >= tw.base;
-  const int tslot = w.is_twin ? (int)blockIdx.x - tw.base : -1;
-  w.slot = w.is_twin ? -1 : (int)blockIdx.x;
+  w.is_twin = tw.base > 0 && vblock >= tw.base;
+  const int tslot = w.is_twin ? vblock - tw.base : -1;
+  w.slot = w.is_twin ? -1 : vblock;
   int b_real = w.is_twin ? -1 : instance_of_slot(A, w.slot, 0);
-  if (!w.is_twin && b_real < 0) return;  // uniform over the workgroup
-  if (w.is_twin && (tslot >= tw.npool || tslot >= tw.cap || !persistent)) return;
+  if (!w.is_twin && b_real < 0) return false;  // uniform over the workgroup
+  if (w.is_twin && (tslot >= tw.npool || tslot >= tw.cap || !persistent)) return false;
   if (!w.is_twin && tw.base > 0 && w.slot < tw.cap && persistent) w.box = tw.box + (size_t)w.slot * kTwWords;
   int b = b_real;  // (a twin switches to its shadow column once it has claimed its share of the iterations)
   const int N = A.N;
@@ -4820,6 +4862,13 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
 #endif
   const long long tstart_clock = tw.debug ? wall_clock64() : 0;
   if (tid == 0 && !w.is_twin) w.stamp(tw, kTsPStart);
+  // (where the job ran, for the mailbox dump's residency table.  XCC_ID, bits 0 - 3: hwreg 20, offset 0, size 4)
+  const unsigned xcc = tw.debug ? (__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 15u) : 0u;
+  if (tid == 0 && tw.debug && tw.base > 0 && (w.is_twin || w.box)) {
+    unsigned long long* own = (w.is_twin ? tw.box + (size_t)(tw.cap + tslot) * kTwWords : w.box) + kTwStamp;
+    tw_store(own + kTsXcd, (unsigned long long)xcc + 1ull);
+    tw_store(own + kTsWorker, (unsigned long long)blockIdx.x + 1ull);
+  }
   if (w.is_twin) {
     if (wave == 0) tw_find_work(C, tw.cap + tslot, lane);
     __syncthreads();
@@ -4829,7 +4878,9 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
         tw_store(own + kTsTStart, (unsigned long long)tstart_clock);
         tw_store(own + kTsTIdleEnd, (unsigned long long)wall_clock64());
       }
-      return;
+      // (no claim: nothing can come any more, or the look ran out -- the worker leaves; a claim that was refused while
+      //  the clone was made: the job is over, the pool may still have work)
+      return wg_uniform(S.ff[kFfClaimSource] < 0.0);
     }
   }
   if (wave == 2 && lane == 0) {  // LDS mirrors of initial_cost / need_init_cost (read by this same lane: forward2_body)
@@ -4906,7 +4957,7 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
       if (wave == 0) ALTRO_STAMP_ADD(14, st_it);
     }
 #endif
-    if (!persistent || *S.active_flag == 0) break;
+    if (!persistent || wg_uniform(*S.active_flag == 0)) break;
     // (the expansions ahead are the next iteration's iff the step was rejected and the inner solve goes on: then their
     //  constraint values become c_, as the expansion step at the top of the loop would have stored them)
     e_done = S.ff[kFfRejected] != 0.0 && S.ff[kFfInnerDone] == 0.0;
@@ -4921,7 +4972,7 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     if (SEG && A.seg_end) {
       if (tid == 0) fused_seg_joint(C, b);
       if (SPEC && adopt) lds_barrier(); else __syncthreads();
-      if (S.ff[kFfSegLeave] != 0.0) break;
+      if (wg_uniform(S.ff[kFfSegLeave] != 0.0)) break;
     }
     if (w.box) tw_bookkeeping<T, SEG>(C, w, loops, b, b_real);
     // (waves of a workgroup share the CU's vector L1, which stores write through and keep coherent,
@@ -4930,23 +4981,23 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     // the next iteration reads this one's scalars from global memory: drain the stores
     if (SPEC && adopt) lds_barrier(); else __syncthreads();
     if (w.box) {
-      const double act = S.ff[kFfTwinAction];
-      if (act == 1.0) {  // pool workgroup: refused (the refusing worker has told the chain) -- nothing of the clone is visible outside its column
+      const int act = __builtin_amdgcn_readfirstlane((int)S.ff[kFfTwinAction]);
+      if (act == 1) {  // pool workgroup: refused (the refusing worker has told the chain) -- nothing of the clone is visible outside its column
         if (tid == 0) w.close(tw);
-        return;
+        return false;
       }
-      if (act == 2.0) {
-        const double res = tw_hand_over(C, w, loops);
-        if (res == 3.0) {
+      if (act == 2) {
+        const int res = __builtin_amdgcn_readfirstlane((int)tw_hand_over(C, w, loops));
+        if (res == 3) {
           fused_report<T, SEG, kSoft>(C, b_real, S.sync_words, (int)S.ff[kFfLoopsBefore] + loops + skipped, loops, skipped);
-          return;  // the successor's chain owns the instance: its last copy-back is the instance's state
+          return false;  // the successor's chain owns the instance: its last copy-back is the instance's state
         }
-        if (res == 1.0) return;
+        if (res == 1) return false;
       }
     }
   }
   if (w.is_twin) {
-    if (!tw_commit<T, M>(C, w, loops, b, b_real, kThreads)) return;
+    if (!tw_commit<T, M>(C, w, loops, b, b_real, kThreads)) return false;
     b = b_real;  // (the gains below go to the instance's own records)
   } else if (w.box && tid == 0 && !w.closed) {
     tw_cancel_chain(tw, w.box);  // the instance is finished: a successor's work is void, and the pool need not wait for a streak
@@ -4964,8 +5015,67 @@ __global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) 
     if (e < (Rec<RS, M::n, M::m>::KP)) RECP((RS*)A.KD, k, (Rec<RS, M::n, M::m>::KP))[e] = (RS)S.sKDf[i];
   }
   fused_report<T, SEG, kSoft>(C, b_real, S.sync_words, w.loops0 + loops + skipped, loops, skipped);
+  return false;
 }
 
+// The launch.  tw.workers == 0 (and every launch that is not persistent): the ONE-SHOT grid, a workgroup per job -- block i
+// runs job i and is gone; when a CU gets its next workgroup is the dispatcher's business.
+// tw.workers > 0: the WORKER grid.  The launch has exactly as many workgroups as the device holds at once (LaunchTail:
+// min(jobs, CUs x workgroups per CU by the occupancy query)), each stays for the whole launch and takes jobs by ticket:
+//   * primary tickets 0 .. base-1 first; ticket s IS block s of the one-shot grid (slot s, mailbox s);
+//   * pool tickets 0 .. npool-1 once the primary tickets are gone; ticket t IS block base + t (shadow column col0 + t,
+//     mailbox cap + t).  A pool job that finds nothing keeps looking on tw_find_work's rule (a look every ~27 us, until no
+//     worker can publish a claimable segment any more) and the worker leaves with it; a worker takes a fresh pool ticket
+//     only after it has served a claim, and leaves when the tickets have run out.
+// The twin protocol sees the same identities as before; which physical workgroup plays block i is all that changes.
+// RESIDENCY, and why no wait can depend on a job that has not started: the grid does not exceed what the device holds, so
+// every worker is resident from the start and stays.  A job waits for one thing only, the verdict of its predecessor
+// (tw_await_verdict), and it has a predecessor only because it claimed from a segment that was PUBLISHED -- one that is
+// being run, or has been run to its joint, by a resident worker, which answers at the joint without waiting for anybody
+// but ITS predecessor, down to a primary, which waits for nobody.  Primary tickets are exhausted before the first pool
+// ticket is taken, so no claimer exists while a primary job is still unstarted.  Every wait stays bounded by the polls
+// that end in the error word (kTwinHandPolls, kTwinIdlePolls).
+template <class T, class M, bool CIRC, int SPEC, bool SEG = false>
+__global__ __launch_bounds__((spec_has_wave4(SPEC) ? kFwdWaves + 1 : kFwdWaves) * kBlock) void k_sweep_fused(
+    DevArrays<T> A, const ProblemDesc* __restrict__ pdg, const ProblemDesc pd_arg, DevOpts o, int mode, int persistent,
+    int* sweeps_out, TwinCtl tw) {
+  using R = Rec<T, M::n, M::m>;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const ProblemDesc* pd = &pd_arg;
+  if (blockIdx.x == 0 && threadIdx.x == 0) publish_count(A);
+  const bool workers = tw.workers > 0 && persistent;
+  const int N = A.N;
+  const FusedLds<T> F{FwdLds<T>{(N + 1) * R::nP, N * R::mP, N * R::KP, pd->total_rows, pd->nslots, R::V}, N, M::n + M::m, pd->npool};
+  int* const ticket = reinterpret_cast<int*>(smem_raw + F.oTicket());
+  double* const ff = reinterpret_cast<double*>(smem_raw + F.oFf());
+  double* const fh = reinterpret_cast<double*>(smem_raw + F.oFh());
+  double* const fh2 = reinterpret_cast<double*>(smem_raw + F.oFh2());
+  bool pool_phase = false;  // (uniform: every thread reads the same ticket)
+  // (one copy of the job for both grids: the one-shot grid is this loop run once with the block's own index for a ticket)
+  for (;;) {
+    int vb = (int)blockIdx.x;
+    if (workers) {
+      // the job before is over for every wave: its LDS is free, and the ticket word may be rewritten
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        int t = -1;
+        if (!pool_phase) t = tail_block_of_ticket(kTkPrimary, atomicAdd(tw.tickets + kTkPrimary, 1), tw.base, tw.npool);
+        if (t < 0) t = tail_block_of_ticket(kTkPool, atomicAdd(tw.tickets + kTkPool, 1), tw.base, tw.npool);
+        *ticket = t;
+      }
+      // (what the job before left in the words through which thread 0 tells the workgroup its decisions: a job reads none
+      //  of them before it has written it -- a fresh workgroup finds arbitrary bits there --, cleared all the same)
+      if (threadIdx.x < kFfWords) ff[threadIdx.x] = 0.0;
+      if (threadIdx.x < kFhWords) fh[threadIdx.x] = 0.0;
+      if (threadIdx.x < kFh2Words) fh2[threadIdx.x] = 0.0;
+      __syncthreads();
+      vb = __builtin_amdgcn_readfirstlane(*ticket);  // (wave-uniform: the job's identity lives in scalar registers, as blockIdx.x does)
+      if (vb < 0) break;
+      pool_phase = vb >= tw.base;
+    }
+    if (fused_job<T, M, CIRC, SPEC, SEG>(A, pdg, pd, o, mode, persistent, sweeps_out, tw, smem_raw, vb) || !workers) break;
+  }
+}
 
 // The last valid column of every chain of segments (DevArrays::seg_*) over the instance's own: one workgroup per instance,
 // follows seg_next while the column it stands on has retired (= its successor started from exactly the state it arrived

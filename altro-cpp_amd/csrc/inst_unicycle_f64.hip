@@ -14,3 +14,14 @@ extern "C" int altro_twin_policy(int R, int lag, int asked_min, int* keep, int* 
   if (see_claim) *see_claim = altro_hip::kTwinSeeClaim;
   return min_share;
 }
+
+// The ticket arithmetic of the persistent tail's worker grid as the kernel and LaunchTail use it, on the host, for
+// tests/test_tail_workers_policy.py.  Returns the launch's grid for `asked` (ALTRO_HIP_TAIL_WORKERS; negative: unset);
+// *workers: resident workers (0: the one-shot grid); *block: the block of the one-shot grid whose identity ticket `ticket`
+// of `kind` (0 primary, 1 pool) carries, -1 past the last one.
+extern "C" int altro_tail_tickets(int ninst, int npool, int cus, int per_cu, int asked, int kind, int ticket, int* workers, int* block) {
+  const int w = altro_hip::tail_worker_count(ninst, npool, cus, per_cu, asked);
+  if (workers) *workers = w;
+  if (block) *block = altro_hip::tail_block_of_ticket(kind, ticket, ninst, npool);
+  return altro_hip::tail_grid(ninst, npool, w);
+}

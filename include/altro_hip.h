@@ -169,8 +169,8 @@ typedef struct altro_timing {
                            /* of one straggler's rejection streak (0: none launched, ALTRO_HIP_TWIN=0)        */
   int twin_claims;         /* ... twins that found a streak and claimed its second half                      */
   int twin_handovers;      /* ... claims the primary confirmed: instances finished by their twin              */
-  int fused_workgroup_iterations; /* most iterations ONE workgroup of the persistent launch ran (a twin or its    */
-                           /* primary: their share of the instance's iterations)                               */
+  int fused_workgroup_iterations; /* most iterations ONE job of the persistent launch ran (a twin's or its       */
+                           /* primary's share of the instance's iterations; a resident worker runs several jobs) */
   int segment_columns;     /* shadow columns the batched sweeps used for segments of rejection streaks (a streak   */
                            /* split in four: three columns; 0: none split, ALTRO_HIP_SEGMENTS=0)                   */
   /* the device-side sweep loop (k_sweep_loop, round 6): ONE launch of persistent workgroups runs the bulk phase --   */
