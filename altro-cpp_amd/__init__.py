@@ -85,6 +85,24 @@ TRACK_STATS_DTYPE = np.dtype([(name, np.int32 if t is C.c_int else np.float64) f
 assert TRACK_STATS_DTYPE.itemsize == C.sizeof(TrackStats) == 40
 
 
+class EnsembleStats(C.Structure):
+    """altro_ensemble_stats (include/altro_ensemble.h): one per instance of mpc_ensemble."""
+    _fields_ = [("samples", C.c_int), ("stopped_state", C.c_int), ("stopped_control", C.c_int), ("violated", C.c_int),
+                ("cost_mean", C.c_double), ("cost_max", C.c_double), ("violation_max", C.c_double), ("max_dx", C.c_double),
+                ("max_du", C.c_double)]
+
+
+ENSEMBLE_STATS_DTYPE = np.dtype([(name, np.int32 if t is C.c_int else np.float64) for name, t in EnsembleStats._fields_])
+assert ENSEMBLE_STATS_DTYPE.itemsize == C.sizeof(EnsembleStats) == 56
+
+
+def ensemble_covariance(dev_mean, dev_mom2):
+    """The sample covariance about the sample mean from what mpc_ensemble returns: dev_mom2 - dev_mean dev_mean^T, per
+    (instance, knot); dev_mean [...][n], dev_mom2 [...][n][n]."""
+    mean, mom2 = np.asarray(dev_mean, dtype=np.float64), np.asarray(dev_mom2, dtype=np.float64)
+    return mom2 - mean[..., :, None] * mean[..., None, :]
+
+
 class TriggerRule(C.Structure):
     """altro_trigger_rule (include/altro_trigger.h): when an instance is re-planned.  The defaults re-plan by age alone."""
     _fields_ = [("max_age", C.c_int), ("dx_tol", C.c_double), ("viol_tol", C.c_double), ("on_unsolved", C.c_int),
@@ -961,6 +979,69 @@ class BatchSolver:
         """cov_inflate_circles with ``base`` and ``rpos`` in fp64 memory of this handle's device."""
         self._call("cov_inflate_circles_device", C.c_int(index), C.c_void_p(base_ptr or None), C.c_int(rows),
                    C.c_int(1 if per_instance else 0), C.c_double(kappa), C.c_void_p(rpos_ptr or None))
+
+    # -- Monte-Carlo ensembles (include/altro_ensemble.h) --------------------------------------------
+    ENSEMBLE_OUTPUTS = ("dev_mean", "dev_mom2", "alive", "viol_count", "summary", "stats")
+
+    def mpc_ensemble(self, steps, samples, seed=0, instance_base=0, Sigma0=None, W=None, u_lo=None, u_hi=None, viol_tol=0.0,
+                     want=("dev_mean", "dev_mom2", "alive", "viol_count", "summary")):
+        """``samples`` closed-loop runs per instance under Gaussian initial errors (covariance ``Sigma0``) and process noise
+        (covariance ``W``, shapes as cov_propagate) drawn on the device, reduced there (altro_mpc_ensemble).  Returns a dict
+        of the arrays named in ``want``: dev_mean [B][steps+1][n] and dev_mom2 [B][steps+1][n][n] (moments of x_k - Xbar_k
+        over the samples alive at k; ``ensemble_covariance`` gives the covariance), alive and viol_count int32
+        [B][steps+1], summary [B] of ENSEMBLE_STATS_DTYPE, stats [B][samples] of TRACK_STATS_DTYPE.  Changes nothing on the
+        handle."""
+        K, S, B, n = max(int(steps), 0), max(int(samples), 0), self.batch, self.n
+        Sigma0, per, W, w_mode = self._cov_inputs(steps, Sigma0, W)
+        u_lo, u_hi = self._track_bounds(u_lo, u_hi)
+        make = dict(dev_mean=lambda: np.zeros((B, K + 1, n)), dev_mom2=lambda: np.zeros((B, K + 1, n, n)),
+                    alive=lambda: np.zeros((B, K + 1), dtype=np.int32), viol_count=lambda: np.zeros((B, K + 1), dtype=np.int32),
+                    summary=lambda: np.zeros(B, dtype=ENSEMBLE_STATS_DTYPE), stats=lambda: np.zeros((B, S), dtype=TRACK_STATS_DTYPE))
+        unknown = [k for k in want if k not in make]
+        if unknown:
+            raise ValueError(f"want names {', '.join(self.ENSEMBLE_OUTPUTS)}; got {unknown}")
+        out = {k: make[k]() for k in want}
+        ptr = lambda k, t: None if k not in out else out[k].ctypes.data_as(C.POINTER(t))  # noqa: E731
+        self._call("mpc_ensemble", C.c_int(steps), C.c_int(samples), C.c_ulonglong(seed), C.c_ulonglong(instance_base), _dp(Sigma0),
+                   C.c_int(per), _dp(W), C.c_int(w_mode), _dp(u_lo), _dp(u_hi), C.c_double(viol_tol), _dp(out.get("dev_mean")),
+                   _dp(out.get("dev_mom2")), ptr("alive", C.c_int), ptr("viol_count", C.c_int), ptr("summary", EnsembleStats),
+                   ptr("stats", TrackStats))
+        return out
+
+    def mpc_ensemble_device(self, steps, samples, seed=0, instance_base=0, Sigma0_ptr=0, sigma0_per_instance=False, W_ptr=0,
+                            w_mode=0, u_lo_ptr=0, u_hi_ptr=0, viol_tol=0.0, dev_mean_ptr=0, dev_mom2_ptr=0, alive_ptr=0,
+                            viol_count_ptr=0, summary_ptr=0, stats_ptr=0):
+        """mpc_ensemble with every array in memory of this handle's device (any pointer may be 0, not all outputs)."""
+        self._call("mpc_ensemble_device", C.c_int(steps), C.c_int(samples), C.c_ulonglong(seed), C.c_ulonglong(instance_base),
+                   C.c_void_p(Sigma0_ptr or None), C.c_int(1 if sigma0_per_instance else 0), C.c_void_p(W_ptr or None),
+                   C.c_int(w_mode), C.c_void_p(u_lo_ptr or None), C.c_void_p(u_hi_ptr or None), C.c_double(viol_tol),
+                   *(C.c_void_p(p or None) for p in (dev_mean_ptr, dev_mom2_ptr, alive_ptr, viol_count_ptr, summary_ptr, stats_ptr)))
+
+    def noise_fill(self, steps, samples, seed=0, instance_base=0, Sigma0=None, W=None):
+        """The arrays mpc_track takes, from the draws mpc_ensemble makes (altro_noise_fill): dict(dx0 [B][S][n],
+        w [B][S][steps][n]); zeros for a covariance that is None."""
+        K, S = max(int(steps), 0), max(int(samples), 0)
+        Sigma0, per, W, w_mode = self._cov_inputs(steps, Sigma0, W)
+        dx0, w = np.zeros((self.batch, S, self.n)), np.zeros((self.batch, S, K, self.n))
+        self._call("noise_fill", C.c_int(steps), C.c_int(samples), C.c_ulonglong(seed), C.c_ulonglong(instance_base), _dp(Sigma0),
+                   C.c_int(per), _dp(W), C.c_int(w_mode), _dp(dx0), _dp(w))
+        return dict(dx0=dx0, w=w)
+
+    def noise_fill_device(self, steps, samples, seed=0, instance_base=0, Sigma0_ptr=0, sigma0_per_instance=False, W_ptr=0, w_mode=0,
+                          dx0_ptr=0, w_ptr=0):
+        """noise_fill with every array in fp64 memory of this handle's device (either output may be 0, not both)."""
+        self._call("noise_fill_device", C.c_int(steps), C.c_int(samples), C.c_ulonglong(seed), C.c_ulonglong(instance_base),
+                   C.c_void_p(Sigma0_ptr or None), C.c_int(1 if sigma0_per_instance else 0), C.c_void_p(W_ptr or None),
+                   C.c_int(w_mode), C.c_void_p(dx0_ptr or None), C.c_void_p(w_ptr or None))
+
+    def multistart_perturb_gaussian(self, starts, seed, sigma, instance_base=0, keep_first=True):
+        """U[b][k][i] += sigma[i] z with z drawn on the device (altro_multistart_perturb_gaussian); with ``keep_first`` the
+        first start of every problem stays bit for bit."""
+        sigma = _f64(sigma)
+        if sigma is not None and sigma.shape != (self.m,):
+            raise ValueError(f"sigma must have shape ({self.m},)")
+        self._call("multistart_perturb_gaussian", C.c_int(starts), C.c_ulonglong(seed), C.c_ulonglong(instance_base), _dp(sigma),
+                   C.c_int(1 if keep_first else 0))
 
     # -- device interop ---------------------------------------------------------------------------
     def pack_results_device(self, device_ptr):

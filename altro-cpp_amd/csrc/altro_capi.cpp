@@ -41,6 +41,7 @@
 #include "../../include/altro_covariance.h"
 #include "../../include/altro_subset.h"
 #include "../../include/altro_trigger.h"
+#include "../../include/altro_ensemble.h"
 
 using namespace altro_hip;
 
@@ -400,7 +401,7 @@ altro_status altro_register_model_source(const char* name, const char* source, i
     inc = slash == std::string::npos ? "." : inc.substr(0, slash);
   }
   std::string hdrs;
-  for (const char* f : {"altro_common.hpp", "altro_devmem.hpp", "altro_problem.hpp", "altro_device.hpp", "altro_kernels.hpp", "altro_engine.hpp",
+  for (const char* f : {"altro_common.hpp", "altro_devmem.hpp", "altro_problem.hpp", "altro_device.hpp", "altro_rng.hpp", "altro_kernels.hpp", "altro_engine.hpp",
                         "altro_user_model.hpp", "../../include/altro_hip.h"}) {
     std::string txt;
     if (!ReadFile(inc + "/" + f, &txt)) {
@@ -1933,6 +1934,143 @@ altro_status altro_cov_inflate_circles_device(altro_handle h, int index, const v
                                               double kappa, const void* rpos_device) {
   return CovInflateImpl(h, index, (const double*)base_device, rows, per_instance, kappa, (const double*)rpos_device, 1,
                         "altro_cov_inflate_circles_device");
+}
+
+}  // extern "C"
+
+// ---- Monte-Carlo ensembles (include/altro_ensemble.h) -------------------------------------------------------------------
+static_assert(sizeof(altro_ensemble_stats) == sizeof(EnsembleStats) && sizeof(altro_ensemble_stats) == 56 &&
+                  offsetof(altro_ensemble_stats, violated) == offsetof(EnsembleStats, violated) &&
+                  offsetof(altro_ensemble_stats, cost_mean) == offsetof(EnsembleStats, cost_mean) &&
+                  offsetof(altro_ensemble_stats, max_du) == offsetof(EnsembleStats, max_du),
+              "altro_ensemble_stats and the kernel's EnsembleStats are one layout");
+namespace {
+
+// what the ensemble and the fill refuse alike, without a device
+altro_status EnsCheck(altro_handle h, int steps, int samples, int w_mode, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const int N = h->spec.desc.N;
+  if (steps < 1 || steps > N) {
+    h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
+    return ALTRO_INVALID_ARG;
+  }
+  if (samples < 1) {
+    h->err = std::string(who) + ": at least one sample per instance, got " + std::to_string(samples);
+    return ALTRO_INVALID_ARG;
+  }
+  if (w_mode < 0 || w_mode > (ALTRO_COV_W_PER_INSTANCE | ALTRO_COV_W_PER_KNOT)) {
+    h->err = std::string(who) + ": w_mode is a combination of ALTRO_COV_W_PER_INSTANCE and ALTRO_COV_W_PER_KNOT, got " + std::to_string(w_mode);
+    return ALTRO_INVALID_ARG;
+  }
+  return ALTRO_OK;
+}
+altro_status EnsStates(altro_handle h, const char* who) {
+  if (h->spec.desc.n > kEnsMaxN) {
+    h->err = std::string(who) + ": models of more than " + std::to_string(kEnsMaxN) + " states are not supported";
+    return ALTRO_UNSUPPORTED;
+  }
+  return ALTRO_OK;
+}
+altro_status MpcEnsembleImpl(altro_handle h, int steps, int samples, unsigned long long seed, unsigned long long instance_base,
+                             const double* Sigma0, int sigma0_per_instance, const double* W, int w_mode, const double* u_lo,
+                             const double* u_hi, double viol_tol, double* dev_mean, double* dev_mom2, int* alive, int* viol_count,
+                             altro_ensemble_stats* summary, altro_track_stats* stats, int on_device, const char* who) {
+  altro_status st = EnsCheck(h, steps, samples, w_mode, who);
+  if (st != ALTRO_OK) return st;
+  if ((u_lo == nullptr) != (u_hi == nullptr)) {
+    h->err = std::string(who) + ": u_lo and u_hi come together (both or neither)";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!(viol_tol >= 0.0) || !(viol_tol < std::numeric_limits<double>::infinity())) {  // (a NaN fails the first)
+    h->err = std::string(who) + ": viol_tol must be finite and not negative";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!dev_mean && !dev_mom2 && !alive && !viol_count && !summary && !stats) {
+    h->err = std::string(who) + ": at least one of dev_mean, dev_mom2, alive, viol_count, summary and stats is required";
+    return ALTRO_INVALID_ARG;
+  }
+  if ((st = EnsStates(h, who)) != ALTRO_OK) return st;
+  if (!h->has_gains) {
+    h->err = std::string(who) + ": no backward pass has produced gains on this handle yet (altro_solve_al, altro_solve_ilqr, "
+             "altro_backward_pass)";
+    return ALTRO_NOT_READY;
+  }
+  const TrackArgs t = TrackOpts(h);
+  EnsembleArgs g{};
+  g.steps = steps, g.S = samples, g.sigma0_per_instance = sigma0_per_instance ? 1 : 0, g.w_mode = w_mode;
+  g.seed = seed, g.instance_base = instance_base;
+  g.Sigma0 = Sigma0, g.W = W, g.u_lo = u_lo, g.u_hi = u_hi;
+  g.viol_tol = viol_tol;
+  g.dev_mean = dev_mean, g.dev_mom2 = dev_mom2, g.alive = alive, g.viol_count = viol_count;
+  g.summary = reinterpret_cast<EnsembleStats*>(summary);
+  g.stats = reinterpret_cast<TrackStats*>(stats);
+  g.check_bounds = t.check_bounds, g.state_max = t.state_max, g.control_max = t.control_max;
+  return Forward(h, [&](EngineBase& e) { return e.MpcEnsemble(g, on_device); });
+}
+altro_status NoiseFillImpl(altro_handle h, int steps, int samples, unsigned long long seed, unsigned long long instance_base,
+                           const double* Sigma0, int sigma0_per_instance, const double* W, int w_mode, double* dx0, double* w,
+                           int on_device, const char* who) {
+  altro_status st = EnsCheck(h, steps, samples, w_mode, who);
+  if (st != ALTRO_OK) return st;
+  if (!dx0 && !w) {
+    h->err = std::string(who) + ": at least one of dx0 and w is required";
+    return ALTRO_INVALID_ARG;
+  }
+  if ((st = EnsStates(h, who)) != ALTRO_OK) return st;
+  EnsembleArgs g{};
+  g.steps = steps, g.S = samples, g.sigma0_per_instance = sigma0_per_instance ? 1 : 0, g.w_mode = w_mode;
+  g.seed = seed, g.instance_base = instance_base;
+  g.Sigma0 = Sigma0, g.W = W, g.dx0 = dx0, g.w = w;
+  return Forward(h, [&](EngineBase& e) { return e.NoiseFill(g, on_device); });
+}
+
+}  // namespace
+
+extern "C" {
+
+altro_status altro_mpc_ensemble(altro_handle h, int steps, int samples, unsigned long long seed, unsigned long long instance_base,
+                                const double* Sigma0, int sigma0_per_instance, const double* W, int w_mode, const double* u_lo,
+                                const double* u_hi, double viol_tol, double* dev_mean, double* dev_mom2, int* alive,
+                                int* viol_count, altro_ensemble_stats* summary, altro_track_stats* stats) {
+  return MpcEnsembleImpl(h, steps, samples, seed, instance_base, Sigma0, sigma0_per_instance, W, w_mode, u_lo, u_hi, viol_tol, dev_mean,
+                         dev_mom2, alive, viol_count, summary, stats, 0, "altro_mpc_ensemble");
+}
+altro_status altro_mpc_ensemble_device(altro_handle h, int steps, int samples, unsigned long long seed,
+                                       unsigned long long instance_base, const void* Sigma0_device, int sigma0_per_instance,
+                                       const void* W_device, int w_mode, const void* u_lo_device, const void* u_hi_device,
+                                       double viol_tol, void* dev_mean_device, void* dev_mom2_device, void* alive_device,
+                                       void* viol_count_device, void* summary_device, void* stats_device) {
+  return MpcEnsembleImpl(h, steps, samples, seed, instance_base, (const double*)Sigma0_device, sigma0_per_instance,
+                         (const double*)W_device, w_mode, (const double*)u_lo_device, (const double*)u_hi_device, viol_tol,
+                         (double*)dev_mean_device, (double*)dev_mom2_device, (int*)alive_device, (int*)viol_count_device,
+                         (altro_ensemble_stats*)summary_device, (altro_track_stats*)stats_device, 1, "altro_mpc_ensemble_device");
+}
+altro_status altro_noise_fill(altro_handle h, int steps, int samples, unsigned long long seed, unsigned long long instance_base,
+                              const double* Sigma0, int sigma0_per_instance, const double* W, int w_mode, double* dx0, double* w) {
+  return NoiseFillImpl(h, steps, samples, seed, instance_base, Sigma0, sigma0_per_instance, W, w_mode, dx0, w, 0, "altro_noise_fill");
+}
+altro_status altro_noise_fill_device(altro_handle h, int steps, int samples, unsigned long long seed,
+                                     unsigned long long instance_base, const void* Sigma0_device, int sigma0_per_instance,
+                                     const void* W_device, int w_mode, void* dx0_device, void* w_device) {
+  return NoiseFillImpl(h, steps, samples, seed, instance_base, (const double*)Sigma0_device, sigma0_per_instance,
+                       (const double*)W_device, w_mode, (double*)dx0_device, (double*)w_device, 1, "altro_noise_fill_device");
+}
+altro_status altro_multistart_perturb_gaussian(altro_handle h, int starts, unsigned long long seed, unsigned long long instance_base,
+                                               const double* sigma, int keep_first) {
+  const char* who = "altro_multistart_perturb_gaussian";
+  const altro_status st = MsCheck(h, starts, false, who);
+  if (st != ALTRO_OK) return st;
+  if (!sigma) {
+    h->err = std::string(who) + ": sigma is required";
+    return ALTRO_INVALID_ARG;
+  }
+  for (int i = 0; i < h->spec.desc.m; ++i)
+    if (!(sigma[i] >= 0.0) || !(sigma[i] < std::numeric_limits<double>::infinity())) {  // (a NaN fails the first)
+      h->err = std::string(who) + ": sigma[" + std::to_string(i) + "] must be finite and not negative";
+      return ALTRO_INVALID_ARG;
+    }
+  return Forward(h, [&](EngineBase& e) { return e.MsPerturbGaussian(starts, seed, instance_base, sigma, keep_first); });
 }
 
 }  // extern "C"

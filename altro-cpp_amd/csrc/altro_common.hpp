@@ -171,6 +171,48 @@ struct CovArgs {
   double *Sigma, *sx, *su, *rpos;          // [B][steps + 1][n][n], [B][steps + 1][n], [B][steps][m], [B][steps + 1]
 };
 
+// ---- Monte-Carlo ensembles (include/altro_ensemble.h) --------------------------------------------------------------------
+// altro_ensemble_stats as k_ens_finish writes it (the C-ABI translation unit asserts that the two layouts agree)
+struct EnsembleStats {
+  int samples, stopped_state, stopped_control, violated;
+  double cost_mean, cost_max, violation_max, max_dx, max_du;
+};
+constexpr int kEnsMaxN = 32;         // states of a model the ensemble accepts (as kCovMaxN)
+constexpr int kEnsChunk = 64;        // samples of one chunk: a wavefront
+constexpr int kEnsFillWaves = 1024;  // wavefronts that fill the device (256 compute units x 4 SIMDs)
+constexpr int kEnsMaxSlabs = 16;     // most partials per instance: bounds the scratch and what k_ens_finish adds
+// fp64 sums per (instance, knot): n of e, n (n + 1) / 2 of the lower triangle of e e^T
+constexpr int EnsembleValues(int n) { return n * (n + 3) / 2; }
+// Slabs of one instance: a wavefront (one per workgroup) takes ONE slab -- `EnsembleChunksPerSlab` consecutive chunks of 64
+// samples of ONE instance, one after the other -- and leaves one partial per slab, which k_ens_finish adds in slab order.
+// A pure function of (B, S): the order of every sum, and with it every bit of the result, depends on nothing else.  One slab
+// once the instances alone fill the device (B >= kEnsFillWaves); otherwise as many as fill it, at most kEnsMaxSlabs and no
+// more than there are chunks, then lowered so that no slab is empty.
+inline int EnsembleChunksPerSlab(long long B, long long S) {
+  const long long chunks = (S + kEnsChunk - 1) / kEnsChunk, fill = (kEnsFillWaves + B - 1) / B;
+  const long long want = std::max<long long>(1, std::min<long long>(std::min<long long>(chunks, fill), kEnsMaxSlabs));
+  return (int)((chunks + want - 1) / want);
+}
+inline int EnsembleSlabs(long long B, long long S) {
+  const long long chunks = (S + kEnsChunk - 1) / kEnsChunk, per = EnsembleChunksPerSlab(B, S);
+  return (int)((chunks + per - 1) / per);
+}
+// One call of Engine::MpcEnsemble / Engine::NoiseFill.  Every pointer may be null; host or device memory as the call says.
+struct EnsembleArgs {
+  int steps, S, sigma0_per_instance, w_mode;
+  unsigned long long seed, instance_base;
+  const double *Sigma0, *W;   // as CovArgs
+  const double *u_lo, *u_hi;  // [m] each, both or neither
+  double viol_tol;
+  double *dev_mean, *dev_mom2;  // [B][steps + 1][n], [B][steps + 1][n][n]
+  int *alive, *viol_count;      // [B][steps + 1] each
+  EnsembleStats* summary;       // [B]
+  TrackStats* stats;            // [B][S]
+  double *dx0, *w;              // NoiseFill's outputs: [B][S][n], [B][S][steps][n]
+  int check_bounds;             // options.check_forwardpass_bounds, state_max, control_max
+  double state_max, control_max;
+};
+
 // ---- blocks carved into parts ---------------------------------------------------------------------------------------
 // Element counts of the K parts of one block -> the element every part starts at; off[K] is the size of the block.
 template <int K>
@@ -216,6 +258,28 @@ inline Parts<6> CovStageParts(int n, int m, size_t B, const CovArgs& c) {
           c.su ? B * st * m : 0,
           c.rpos ? B * (st + 1) : 0};
 }
+// Engine::MpcEnsemble: Sigma0 | W | u_lo, u_hi | dev_mean | dev_mom2 | alive | viol_count | summary | stats (ints two to a
+// double, rounded up).  Engine::NoiseFill: Sigma0 | W | dx0 | w
+inline Parts<9> EnsembleStageParts(int n, int m, size_t B, const EnsembleArgs& c) {
+  static_assert(sizeof(EnsembleStats) % sizeof(double) == 0, "the summaries are staged in a block of doubles");
+  const size_t st = (size_t)c.steps, nn = (size_t)n * n, ints = (B * (st + 1) + 1) / 2;
+  return {c.Sigma0 ? (c.sigma0_per_instance ? B : 1) * nn : 0,
+          c.W ? ((c.w_mode & 1) ? B : 1) * ((c.w_mode & 2) ? st : 1) * nn : 0,
+          c.u_lo ? 2 * (size_t)m : 0,
+          c.dev_mean ? B * (st + 1) * n : 0,
+          c.dev_mom2 ? B * (st + 1) * nn : 0,
+          c.alive ? ints : 0,
+          c.viol_count ? ints : 0,
+          c.summary ? B * (sizeof(EnsembleStats) / sizeof(double)) : 0,
+          c.stats ? B * (size_t)c.S * (sizeof(TrackStats) / sizeof(double)) : 0};
+}
+inline Parts<4> NoiseStageParts(int n, size_t B, const EnsembleArgs& c) {
+  const size_t st = (size_t)c.steps, nn = (size_t)n * n, L = B * (size_t)c.S;
+  return {c.Sigma0 ? (c.sigma0_per_instance ? B : 1) * nn : 0,
+          c.W ? ((c.w_mode & 1) ? B : 1) * ((c.w_mode & 2) ? st : 1) * nn : 0,
+          c.dx0 ? L * n : 0,
+          c.w ? L * st * n : 0};
+}
 // Engine::CovInflate: the base track [cols][rows][np] | rpos [B][knots];  Engine::MsPerturb: dU [cols][N][m];
 // Engine::Advance: x0 [B][n] | w [B][n];  Engine::SetReference: Xref | Uref, `points` = rows x columns of the path
 inline Parts<2> InflateStageParts(size_t cols, size_t rows, size_t np, size_t B, size_t knots) { return {cols * rows * np, B * knots}; }
@@ -230,6 +294,7 @@ inline Parts<6> TriggerStageParts(int m, size_t B, bool tracked, bool age, bool 
   return {tracked ? B * ts : 0, age ? ints : 0, bounds ? 2 * (size_t)m : 0, mask ? bytes : 0, reason ? ints : 0, ahead ? B * ts : 0};
 }
 inline Parts<1> PerturbStageParts(int m, size_t cols, size_t N) { return {cols * N * m}; }
+inline Parts<1> GaussStageParts(int m) { return {(size_t)m}; }  // Engine::MsPerturbGaussian: sigma [m]
 inline Parts<2> AdvanceStageParts(int n, size_t B, bool x0, bool w) { return {x0 ? B * n : 0, w ? B * n : 0}; }
 inline Parts<2> ReferenceStageParts(int n, int m, size_t points, bool U) { return {points * n, U ? points * m : 0}; }
 
@@ -635,6 +700,12 @@ class EngineBase {
   // event-triggered re-planning (include/altro_trigger.h): the rule for every instance (k_mpc_trigger; the lookahead through
   // k_mpc_track); changes nothing on the engine.  The loop kind kLoopTriggered keeps ages, masks and reasons on the device.
   virtual altro_status Trigger(const TriggerArgs& call, int on_device, bool ilqr_mode) = 0;
+  // Monte-Carlo ensembles (include/altro_ensemble.h): MpcEnsemble and NoiseFill change nothing on the engine; host arrays, or
+  // (on_device) memory of the engine's device.  MsPerturbGaussian: sigma [m] on the host.
+  virtual altro_status MpcEnsemble(const EnsembleArgs& call, int on_device) = 0;
+  virtual altro_status NoiseFill(const EnsembleArgs& call, int on_device) = 0;
+  virtual altro_status MsPerturbGaussian(int G, unsigned long long seed, unsigned long long instance_base, const double* sigma,
+                                         int keep_first) = 0;
   virtual const char* LastError() = 0;
 };
 

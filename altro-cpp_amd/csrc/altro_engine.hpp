@@ -910,6 +910,25 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(sg.finish());
     return ALTRO_OK;
   }
+  // U += sigma z with z drawn on the device (include/altro_ensemble.h): sigma [m] goes through the engine's staging block
+  altro_status MsPerturbGaussian(int G, unsigned long long seed, unsigned long long instance_base, const double* sigma,
+                                 int keep_first) override {
+    ALTRO_TRY(MsCheck(G));
+    if (!sigma) {
+      err_ = "altro_multistart_perturb_gaussian: sigma is required";
+      return ALTRO_INVALID_ARG;
+    }
+    ctg_replayable_ = false;
+    const Parts<1> p = GaussStageParts(m);
+    ALTRO_TRY(EnsureStage(p.total()));
+    Staged<1> sg(false, hm_.stage.get(), p, stream_);
+    const double* sd = sg.in(0, sigma);
+    const size_t total = (size_t)N_ * B_ * (R::mP / 2);
+    hipLaunchKernelGGL(k_ms_perturb_gauss<T>, dim3((unsigned)((total + kMsThreads - 1) / kMsThreads)), dim3(kMsThreads), 0, stream_, A_, sd, G,
+                       keep_first ? 1 : 0, seed, instance_base, m, R::mP);
+    ALTRO_HIP_CHECK(sg.finish());
+    return ALTRO_OK;
+  }
   // The winners' trajectories through k_rec_to_rows with the winner as the source column, their statistics through k_ms_stats.
   // A host caller's arrays are staged in ONE device block (X | U | stats) and come back with one copy each.
   altro_status MsGetBest(int G, double* X, double* U, altro_stats* stats, int* winner, int on_device, bool ilqr_mode) override {
@@ -1263,6 +1282,169 @@ class Engine final : public EngineBase {
     g.stats = sg.out(5, call.stats);
     if (!on_device) g.x_end = nullptr;  // (a device caller's only: what altro_mpc_run_tracked advances from)
     const altro_status st = sg.ok() ? LaunchTrack(g) : ALTRO_OK;
+    const hipError_t e = sg.finish(st == ALTRO_OK);
+    ALTRO_TRY(st);
+    ALTRO_HIP_CHECK(e);
+    return ALTRO_OK;
+  }
+
+  // ---- Monte-Carlo ensembles (include/altro_ensemble.h) --------------------------------------------
+  // The factors of the call's Sigma0 and W (device arrays) into `fac`, L0 | Lw, by k_ens_factor; the two status words come
+  // back before anything else is launched, and a refused matrix ends the call with its instance and knot in the text.
+  altro_status EnsFactors(const char* who, const EnsembleArgs& g, DevBlock<double>* fac, DevBlock<int>* word, const double** L0,
+                          const double** Lw) {
+    const size_t nn = (size_t)n * n;
+    const size_t c0 = g.Sigma0 ? (g.sigma0_per_instance ? (size_t)B_ : 1) : 0;
+    const size_t cw = g.W ? ((g.w_mode & 1) ? (size_t)B_ : 1) * ((g.w_mode & 2) ? (size_t)g.steps : 1) : 0;
+    *L0 = *Lw = nullptr;
+    if (c0 + cw == 0) return ALTRO_OK;
+    if (c0 > 0x7fffffffull || cw > 0x7fffffffull) {
+      err_ = std::string(who) + ": more than 2^31 - 1 covariance matrices";
+      return ALTRO_INVALID_ARG;
+    }
+    if (fac->alloc((c0 + cw) * nn) != hipSuccess || word->alloc(2) != hipSuccess) {
+      err_ = std::string(who) + ": out of device memory for " + std::to_string((c0 + cw) * nn * sizeof(double)) + " bytes of factors";
+      return ALTRO_HIP_ERROR;
+    }
+    ALTRO_HIP_CHECK(hipMemsetAsync(word->get(), 0, 2 * sizeof(int), stream_));
+    if (c0) {
+      *L0 = fac->get();
+      hipLaunchKernelGGL((k_ens_factor<0>), dim3((unsigned)((c0 + kEnsThreads - 1) / kEnsThreads)), dim3(kEnsThreads), 0, stream_, g.Sigma0,
+                         fac->get(), n, (int)c0, word->get());
+    }
+    if (cw) {
+      *Lw = fac->get() + c0 * nn;
+      hipLaunchKernelGGL((k_ens_factor<0>), dim3((unsigned)((cw + kEnsThreads - 1) / kEnsThreads)), dim3(kEnsThreads), 0, stream_, g.W,
+                         fac->get() + c0 * nn, n, (int)cw, word->get() + 1);
+    }
+    ALTRO_HIP_CHECK(hipGetLastError());
+    int bad[2] = {0, 0};
+    ALTRO_HIP_CHECK(CopySync(bad, word->get(), sizeof(bad), hipMemcpyDeviceToHost));
+    if (bad[0]) {
+      const size_t i = c0 - (size_t)bad[0];
+      err_ = std::string(who) + ": Sigma0 is not positive semidefinite" + (g.sigma0_per_instance ? " (instance " + std::to_string(i) + ")" : "");
+      return ALTRO_INVALID_ARG;
+    }
+    if (bad[1]) {
+      const size_t i = cw - (size_t)bad[1], per = (g.w_mode & 2) ? (size_t)g.steps : 1;
+      err_ = std::string(who) + ": W is not positive semidefinite (" + ((g.w_mode & 1) ? "instance " + std::to_string(i / per) : "every instance") +
+             ", " + ((g.w_mode & 2) ? "knot " + std::to_string(i % per) : "every knot") + ")";
+      return ALTRO_INVALID_ARG;
+    }
+    return ALTRO_OK;
+  }
+  bool EnsShapeOk(const char* who, const EnsembleArgs& c) {
+    if (c.steps < 1 || c.steps > N_ || c.S < 1 || (c.w_mode & ~3)) {
+      err_ = std::string(who) + ": steps must lie in [1, N], samples must be positive and w_mode lie in 0..3";
+      return false;
+    }
+    return true;
+  }
+  // Factors, one launch of k_mpc_ensemble over (instance, slab), k_ens_finish.  Host arrays are staged through ONE device block
+  // (EnsembleStageParts) that lives for the call, as do the factors and the slabs' partials; device arrays are used where
+  // they are.  Reads the engine's arrays only: no flag of the engine changes.
+  altro_status MpcEnsemble(const EnsembleArgs& call, int on_device) override {
+    const char* who = "altro_mpc_ensemble";
+    if (!EnsShapeOk(who, call)) return ALTRO_INVALID_ARG;
+    if ((call.u_lo == nullptr) != (call.u_hi == nullptr) || !(call.viol_tol >= 0.0) || !std::isfinite(call.viol_tol) ||
+        (!call.dev_mean && !call.dev_mom2 && !call.alive && !call.viol_count && !call.summary && !call.stats)) {
+      err_ = std::string(who) + ": u_lo / u_hi come together, viol_tol is finite and not negative, and an output is required";
+      return ALTRO_INVALID_ARG;
+    }
+    if (n > kEnsMaxN) {
+      err_ = std::string(who) + ": models of more than " + std::to_string(kEnsMaxN) + " states are not supported";
+      return ALTRO_UNSUPPORTED;
+    }
+    if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
+    const int slabs = EnsembleSlabs(B_, call.S);
+    if ((size_t)B_ * (size_t)slabs > 0x7fffffffull) {
+      err_ = std::string(who) + ": instances x slabs exceed one launch (2^31 - 1 wavefronts)";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    const Parts<9> p = EnsembleStageParts(n, m, (size_t)B_, call);
+    const size_t K1 = (size_t)call.steps + 1, waves = (size_t)B_ * slabs, V = (size_t)EnsembleValues(n);
+    DevBlock<double> stage, fac, part;
+    DevBlock<int> word, cnt;
+    DevBlock<EnsSlabSum> sums;
+    if ((!on_device && stage.alloc(p.total()) != hipSuccess) || part.alloc(waves * K1 * V) != hipSuccess ||
+        cnt.alloc(waves * K1 * 2) != hipSuccess || sums.alloc(waves) != hipSuccess) {
+      err_ = std::string(who) + ": out of device memory for " + std::to_string((p.total() + waves * K1 * (V + 1)) * sizeof(double)) +
+             " bytes of staged arrays and partial sums";
+      return ALTRO_HIP_ERROR;
+    }
+    Staged<9> sg(on_device != 0, stage.get(), p, stream_);
+    EnsLaunch q{};
+    q.g = call;
+    q.g.Sigma0 = sg.in(0, call.Sigma0);
+    q.g.W = sg.in(1, call.W);
+    q.g.u_lo = sg.in(2, call.u_lo, 0, m);
+    q.g.u_hi = sg.in(2, call.u_hi, m, m);
+    EnsFinishArgs f{};
+    f.dev_mean = sg.out(3, call.dev_mean);
+    f.dev_mom2 = sg.out(4, call.dev_mom2);
+    // (the int arrays are an odd number of words when B (steps + 1) is odd: their downloads are this call's, to the word)
+    f.alive = on_device || !call.alive ? call.alive : reinterpret_cast<int*>(sg.part(5));
+    f.viol_count = on_device || !call.viol_count ? call.viol_count : reinterpret_cast<int*>(sg.part(6));
+    f.summary = sg.out(7, call.summary);
+    q.g.stats = sg.out(8, call.stats);
+    altro_status st = sg.ok() ? EnsFactors(who, q.g, &fac, &word, &q.L0, &q.Lw) : ALTRO_OK;
+    hipError_t ec = hipSuccess;
+    if (st == ALTRO_OK && sg.ok()) {
+      q.part = part.get(), q.cnt = cnt.get(), q.sums = sums.get();
+      q.slabs = slabs, q.per_slab = EnsembleChunksPerSlab(B_, call.S);
+      if (KnotRouted(A_))
+        hipLaunchKernelGGL((k_mpc_ensemble_trk<T, M>), dim3((unsigned)waves), dim3(kEnsChunk), 0, stream_, A_, up_.d_pd, q);
+      else
+        hipLaunchKernelGGL((k_mpc_ensemble<T, M>), dim3((unsigned)waves), dim3(kEnsChunk), 0, stream_, A_, up_.d_pd, q);
+      f.part = part.get(), f.cnt = cnt.get(), f.sums = sums.get();
+      f.B = B_, f.steps = call.steps, f.slabs = slabs, f.n = n, f.S = call.S;
+      const size_t total = (size_t)B_ * K1 * V;
+      hipLaunchKernelGGL((k_ens_finish<0>), dim3((unsigned)((total + kEnsThreads - 1) / kEnsThreads)), dim3(kEnsThreads), 0, stream_, f);
+      ec = hipGetLastError();
+      const size_t ib = (size_t)B_ * K1 * sizeof(int);
+      if (!on_device && call.alive && ec == hipSuccess) ec = hipMemcpyAsync(call.alive, f.alive, ib, hipMemcpyDeviceToHost, stream_);
+      if (!on_device && call.viol_count && ec == hipSuccess) ec = hipMemcpyAsync(call.viol_count, f.viol_count, ib, hipMemcpyDeviceToHost, stream_);
+    }
+    const hipError_t e = sg.finish(st == ALTRO_OK);
+    ALTRO_TRY(st);
+    ALTRO_HIP_CHECK(ec);
+    ALTRO_HIP_CHECK(e);
+    return ALTRO_OK;
+  }
+  altro_status NoiseFill(const EnsembleArgs& call, int on_device) override {
+    const char* who = "altro_noise_fill";
+    if (!EnsShapeOk(who, call)) return ALTRO_INVALID_ARG;
+    if (!call.dx0 && !call.w) {
+      err_ = std::string(who) + ": at least one of dx0 and w is required";
+      return ALTRO_INVALID_ARG;
+    }
+    if (n > kEnsMaxN) {
+      err_ = std::string(who) + ": models of more than " + std::to_string(kEnsMaxN) + " states are not supported";
+      return ALTRO_UNSUPPORTED;
+    }
+    const size_t blocks = ((size_t)B_ * (size_t)call.S + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffull) {
+      err_ = std::string(who) + ": instances x samples exceed one launch (2^31 - 1 wavefronts)";
+      return ALTRO_INVALID_ARG;
+    }
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    const Parts<4> p = NoiseStageParts(n, (size_t)B_, call);
+    DevBlock<double> stage, fac;
+    DevBlock<int> word;
+    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
+      err_ = std::string(who) + ": out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
+      return ALTRO_HIP_ERROR;
+    }
+    Staged<4> sg(on_device != 0, stage.get(), p, stream_);
+    EnsembleArgs g = call;
+    g.Sigma0 = sg.in(0, call.Sigma0);
+    g.W = sg.in(1, call.W);
+    g.dx0 = sg.out(2, call.dx0);
+    g.w = sg.out(3, call.w);
+    const double *L0 = nullptr, *Lw = nullptr;
+    const altro_status st = sg.ok() ? EnsFactors(who, g, &fac, &word, &L0, &Lw) : ALTRO_OK;
+    if (st == ALTRO_OK && sg.ok()) hipLaunchKernelGGL((k_noise_fill<n>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, g, L0, Lw, B_);
     const hipError_t e = sg.finish(st == ALTRO_OK);
     ALTRO_TRY(st);
     ALTRO_HIP_CHECK(e);

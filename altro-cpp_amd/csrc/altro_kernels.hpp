@@ -29,8 +29,10 @@
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "altro_device.hpp"
+#include "altro_rng.hpp"
 
 namespace altro_hip {
 
@@ -6332,6 +6334,445 @@ __global__ __launch_bounds__(kBlock) void k_trigger_log(const unsigned char* __r
   st_log[b] = status[b];
   why_log[b] = in ? why[b] : 0;
   age[b] = (in ? 0 : age[b]) + 1;
+}
+
+// -------------------------------------------------------------------------------------------------
+// Monte-Carlo ensembles (include/altro_ensemble.h): the tracking of k_mpc_track with the initial error and the process noise
+// drawn in the kernel (altro_rng.hpp: Philox4x32-10, Box-Muller, L xi), reduced over the samples to per-knot sums.
+//
+// k_ens_factor    ONE LANE PER MATRIX of a Sigma0 / W array: the semidefinite factor L (altro_rng::psd_factor), row-major, full
+//                 (zeros above the diagonal).  A refused matrix raises the status word to count - index by an integer
+//                 atomicMax, so that the word names the FIRST refused matrix whatever the order the lanes run in; 0: none.
+// k_noise_fill    one lane per (instance, sample): the arrays altro_mpc_track takes, from the very altro_rng::noise the ensemble
+//                 inlines.  A lane's rows are contiguous, neighbouring lanes lie steps * n doubles apart (strided stores, as the
+//                 logs of k_mpc_track).
+// k_mpc_ensemble  ONE WAVEFRONT PER WORKGROUP; a wavefront belongs to ONE instance and one slab of its samples
+//                 (EnsembleSlabs, altro_common.hpp): blockIdx.x = instance * slabs + slab.  It runs the slab's chunks of 64
+//                 samples one after the other, a lane per sample; lanes past S run along and count for nothing.  Xbar_k, Ubar_k,
+//                 the gain record and L_k are one address per wave, requested one knot ahead as in mpc_track_kernel, whose loop
+//                 body this one repeats statement by statement (the bit-for-bit test against altro_mpc_track on the arrays of
+//                 k_noise_fill rests on that).  The draw of knot k -- ceil(n / 2) Philox calls, log, sincos, L xi -- does not
+//                 depend on the lane's state and sits at the top of the knot beside the record loads.
+//                 Reduction, per knot: V = n (n + 3) / 2 fp64 values per lane (e, and the lower triangle of e e^T; zero for a
+//                 lane that is not alive).  In tiles of kEnsTile values the lanes write red[value][lane] to LDS (row stride
+//                 65 doubles: conflict-free both ways), then lane v of the tile adds the 64 entries of its row in a fixed
+//                 order (four interleaved partial sums, ((a0 + a1) + (a2 + a3))) and adds the result to the slab's partial in
+//                 global memory, part[(blockIdx.x * (steps + 1) + k) * V + v]: the first chunk stores, the later ones add, always
+//                 the same lane of the same wave, so there is no atomic and the order is chunk order.  The two counts (alive,
+//                 violating at k) are __ballot + popcount, kept by lane 0 the same way.  LDS: min(V, kEnsTile) * 65 * 8 bytes
+//                 (4.7 KB for the unicycle, 16.6 KB from V = 32 on) whatever the horizon; the per-knot sums live in the
+//                 partial, (steps + 1) (8 V + 8) bytes per slab, which stays in the L2 between two chunks.
+//                 The per-sample summary (counts by ballot, cost sum and the four maxima by a __shfl_xor butterfly, whose order
+//                 is fixed too) is kept wave-uniform over the chunks and written once per slab.
+// k_ens_finish    one lane per (instance, knot, value): adds the slabs' partials IN SLAB ORDER, divides by the number alive
+//                 (nobody alive: quiet NaN), mirrors the triangle; the lanes of value 0 write the counts, and those of knot 0
+//                 the instance's summary.
+// k_ms_perturb_gauss  k_ms_perturb with the addend drawn: lane (knot, instance, pair j) makes ONE Philox call of stream 1 and
+//                 adds sigma[2 j] z_{2j}, sigma[2 j + 1] z_{2j+1} by one fma each; with keep_first the first start of every
+//                 problem is not touched at all.
+// -------------------------------------------------------------------------------------------------
+constexpr int kEnsThreads = 256;
+constexpr int kEnsTile = 32;  // values reduced through LDS at a time
+struct EnsSlabSum {  // what one slab leaves for k_ens_finish
+  int finished, stopped_state, stopped_control, violated;
+  double cost_sum, cost_max, viol_max, max_dx, max_du;
+};
+struct EnsLaunch {  // one launch of k_mpc_ensemble: every pointer in device memory
+  EnsembleArgs g;
+  const double *L0, *Lw;  // the factors of g.Sigma0 / g.W, in their layout; null: no draw
+  double* part;           // [B][slabs][steps + 1][V]
+  int* cnt;               // [B][slabs][steps + 1][2]: alive, violating
+  EnsSlabSum* sums;       // [B][slabs]
+  int slabs, per_slab;    // EnsembleSlabs, EnsembleChunksPerSlab
+};
+// the matrix of (instance b, knot k) in an array laid out by `mode` (bit 0 per instance, bit 1 per knot)
+__host__ __device__ inline size_t ens_matrix_index(int mode, int steps, size_t b, size_t k) {
+  return ((mode & 1) ? b : 0) * ((mode & 2) ? (size_t)steps : 1) + ((mode & 2) ? k : 0);
+}
+template <int kDummy>
+__global__ __launch_bounds__(kEnsThreads) void k_ens_factor(const double* __restrict__ W, double* __restrict__ L, int n, int count,
+                                                            int* __restrict__ status) {
+  const int i = (int)blockIdx.x * kEnsThreads + (int)threadIdx.x;
+  if (i >= count) return;
+  const size_t nn = (size_t)n * (size_t)n;
+  if (altro_rng::psd_factor(W + (size_t)i * nn, n, L + (size_t)i * nn)) atomicMax(status, count - i);
+}
+template <int n>
+__global__ __launch_bounds__(kBlock) void k_noise_fill(EnsembleArgs g, const double* __restrict__ L0, const double* __restrict__ Lw,
+                                                       int B) {
+  const size_t lane = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (lane >= (size_t)B * (size_t)g.S) return;
+  const size_t b = lane / (size_t)g.S;
+  const unsigned s = (unsigned)(lane - b * (size_t)g.S);
+  const unsigned long long inst = g.instance_base + b;
+  double out[n];
+  if (g.dx0) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) out[i] = 0.0;
+    if (L0) altro_rng::noise<n>(g.seed, altro_rng::kKnotInitial, s, inst, L0 + (g.sigma0_per_instance ? b : 0) * (size_t)(n * n), out);
+#pragma unroll
+    for (int i = 0; i < n; ++i) g.dx0[lane * n + i] = out[i];
+  }
+  if (!g.w) return;
+  double* const wl = g.w + lane * (size_t)g.steps * n;
+  for (int k = 0; k < g.steps; ++k) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) out[i] = 0.0;
+    if (Lw) altro_rng::noise<n>(g.seed, (unsigned)k, s, inst, Lw + ens_matrix_index(g.w_mode, g.steps, b, (size_t)k) * (size_t)(n * n), out);
+#pragma unroll
+    for (int i = 0; i < n; ++i) wl[(size_t)k * n + i] = out[i];
+  }
+}
+
+// value v of a lane: e[v] for v < n, then the lower triangle of e e^T row by row
+constexpr int ens_tri_row(int t) {
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  return i;
+}
+template <int n, int v>
+ALTRO_DEV double ens_value(const double* e) {
+  if constexpr (v < n) {
+    return e[v];
+  } else {
+    constexpr int t = v - n, i = ens_tri_row(t), j = t - i * (i + 1) / 2;
+    return e[i] * e[j];
+  }
+}
+template <int n, int V0, int... I>
+ALTRO_DEV void ens_write_tile(double (*red)[kEnsChunk + 1], int lane, const double* e, std::integer_sequence<int, I...>) {
+  ((red[I][lane] = ens_value<n, V0 + I>(e)), ...);
+}
+// adds the tiles from value V0 on of this knot to dst[0 .. V): see k_mpc_ensemble above
+template <int n, int V0>
+ALTRO_DEV void ens_reduce(double (*red)[kEnsChunk + 1], int lane, const double* e, double* __restrict__ dst, bool first) {
+  constexpr int V = EnsembleValues(n), cnt = V - V0 < kEnsTile ? V - V0 : kEnsTile;
+  __syncthreads();  // (the rows are free: the reads of the tile before are done)
+  ens_write_tile<n, V0>(red, lane, e, std::make_integer_sequence<int, cnt>());
+  __syncthreads();
+  if (lane < cnt) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+    for (int s = 0; s < kEnsChunk; s += 4) {
+      a0 += red[lane][s];
+      a1 += red[lane][s + 1];
+      a2 += red[lane][s + 2];
+      a3 += red[lane][s + 3];
+    }
+    const double sum = (a0 + a1) + (a2 + a3);
+    dst[V0 + lane] = first ? sum : dst[V0 + lane] + sum;
+  }
+  if constexpr (V0 + kEnsTile < V) ens_reduce<n, V0 + kEnsTile>(red, lane, e, dst, first);
+}
+ALTRO_DEV double ens_wave_sum(double x) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s);
+  return x;
+}
+ALTRO_DEV double ens_wave_max(double x) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    const double o = __shfl_xor(x, s);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+template <class T, class M, class Ctx>
+ALTRO_DEV void mpc_ensemble_kernel(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, const EnsLaunch& q) {
+  static_assert(sizeof(T) == 8, "the deviations are formed in the state's own type, fp64");
+  constexpr int n = M::n, m = M::m, V = EnsembleValues(n);
+  using R = Rec<T, n, m>;
+  using RS = rec_scalar_t<T, M>;
+  using RR = Rec<RS, n, m>;
+  __shared__ double red[V < kEnsTile ? V : kEnsTile][kEnsChunk + 1];
+  const EnsembleArgs& g = q.g;
+  const int lid = (int)threadIdx.x;
+  const int b = (int)(blockIdx.x / (unsigned)q.slabs), slab = (int)(blockIdx.x - (unsigned)b * (unsigned)q.slabs);
+  const unsigned Bp = A.Bp;
+  const int N = A.N, steps = g.steps;
+  const unsigned long long inst = g.instance_base + (unsigned long long)b;
+  const bool clip = g.u_lo != nullptr;
+  const T state_max2 = T(g.state_max * g.state_max), control_max2 = T(g.control_max * g.control_max);
+  const Ctx C(A, b);
+  double* const part = q.part + (size_t)blockIdx.x * (size_t)(steps + 1) * V;
+  int* const cnt = q.cnt + (size_t)blockIdx.x * (size_t)(steps + 1) * 2;
+  const double* const L0 = q.L0 ? q.L0 + (size_t)(g.sigma0_per_instance ? b : 0) * (size_t)(n * n) : nullptr;
+  const int chunks = (g.S + kEnsChunk - 1) / kEnsChunk, c0 = slab * q.per_slab, c1 = c0 + q.per_slab < chunks ? c0 + q.per_slab : chunks;
+  const double ninf = -__builtin_inf();
+
+  EnsSlabSum acc;  // (wave-uniform)
+  acc.finished = acc.stopped_state = acc.stopped_control = acc.violated = 0;
+  acc.cost_sum = 0.0, acc.cost_max = ninf, acc.viol_max = 0.0, acc.max_dx = 0.0, acc.max_du = 0.0;
+  for (int c = c0; c < c1; ++c) {
+    const bool first = c == c0;
+    const unsigned s = (unsigned)c * kEnsChunk + (unsigned)lid;
+    const bool mine = s < (unsigned)g.S;
+    const size_t lane = (size_t)b * (size_t)g.S + (size_t)s;
+
+    T x[R::nP], xk[R::nP], uk[R::mP], xkn[R::nP], ukn[R::mP], u[R::mP], xn[n], wk[n];
+    double e[n];
+    RS kd[RR::KP], kdn[RR::KP];
+    load_rec<T, R::nP>(A.x0 + (size_t)b * R::nP, x);
+    if (L0) {
+      double d0[n];
+      altro_rng::noise<n>(g.seed, altro_rng::kKnotInitial, s, inst, L0, d0);
+#pragma unroll
+      for (int i = 0; i < n; ++i) x[i] = T((double)x[i] + d0[i]);
+    }
+    load_rec<T, R::nP>(RECP(A.X, 0, R::nP), xk);
+    load_rec<T, R::mP>(RECP(A.U, 0, R::mP), uk);
+    load_rec<RS, RR::KP>(RECP((const RS*)A.KD, 0, RR::KP), kd);
+    T h = step_of(A, pd, 0);
+    float t = time_of(A, 0);
+    int md = model_of(A, 0);
+#pragma unroll
+    for (int i = 0; i < R::mP; ++i) u[i] = T(0);
+
+    double cost = 0.0;
+    T viol = T(0), mdx = T(0), mdu = T(0);
+    int status = ALTRO_UNSOLVED, done = steps;
+    bool alive = true;
+    for (int k = 0; k < steps; ++k) {
+      // what the next knot needs and the lane's state does not decide: the records, and the draw
+      const int kn = k + 1 < N ? k + 1 : N - 1;
+      load_rec<T, R::nP>(RECP(A.X, k + 1, R::nP), xkn);
+      load_rec<T, R::mP>(RECP(A.U, kn, R::mP), ukn);
+      load_rec<RS, RR::KP>(RECP((const RS*)A.KD, kn, RR::KP), kdn);
+      const T hn = step_of(A, pd, kn);
+      const float tn = time_of(A, kn);
+      const int mdn = model_of(A, kn);
+      if (q.Lw) {
+        double wn[n];
+        altro_rng::noise<n>(g.seed, (unsigned)k, s, inst, q.Lw + ens_matrix_index(g.w_mode, steps, (size_t)b, (size_t)k) * (size_t)(n * n), wn);
+#pragma unroll
+        for (int i = 0; i < n; ++i) wk[i] = T(wn[i]);
+      }
+      // u = Ubar + K (x - Xbar), then the saturation (mpc_track_kernel)
+      T dxm = T(0), dum = T(0);
+#pragma unroll
+      for (int l = 0; l < n; ++l) dxm = max_(dxm, abs_(x[l] - xk[l]));
+#pragma unroll
+      for (int i = 0; i < m; ++i) {
+        T sm = T(0);
+#pragma unroll
+        for (int l = 0; l < n; ++l) sm += T(kd[RR::oK + i + l * m]) * (x[l] - xk[l]);
+        T ui = uk[i] + sm;
+        if (clip) ui = min_(max_(ui, T(g.u_lo[i])), T(g.u_hi[i]));
+        u[i] = ui;
+        dum = max_(dum, abs_(ui - uk[i]));
+      }
+      if (alive) {
+        mdx = max_(mdx, dxm);
+        mdu = max_(mdu, dum);
+      }
+      T v = T(0);
+      {
+        int rb;
+        const KnotClass& kc = class_of_knot(A, pd, k, &rb);
+        decltype(auto) Ck = C.at(k);
+        const T Jk = quad_cost<T, n, m>(Ck, pd->grp[kc.cost_group], x, u);
+        knot_cost<T, n, m, true>(Ck, pd, kc, rb, x, u, &v);
+        if (alive) {
+          cost += (double)Jk;
+          viol = max_(viol, v);
+        }
+      }
+      // the sums of knot k over the samples alive at k
+      {
+        const bool live = alive && mine;
+#pragma unroll
+        for (int i = 0; i < n; ++i) {
+          double d = (double)(x[i] - xk[i]);
+          pin(d);  // (the products below are products of the rounded difference)
+          e[i] = live ? d : 0.0;
+        }
+        ens_reduce<n, 0>(red, lid, e, part + (size_t)k * V, first);
+        const int na = __popcll(__ballot(live)), nv = __popcll(__ballot(live && (double)v > g.viol_tol));
+        if (lid == 0) {
+          cnt[2 * k] = first ? na : cnt[2 * k] + na;
+          cnt[2 * k + 1] = first ? nv : cnt[2 * k + 1] + nv;
+        }
+      }
+      discrete_step<T, M>(x, u, h, xn, t, md);
+      if (q.Lw) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) xn[i] += wk[i];
+      }
+      if (g.check_bounds && alive) {  // (mpc_track_kernel)
+        T sx = T(0), su = T(0);
+#pragma unroll
+        for (int i = 0; i < n; ++i) sx += xn[i] * xn[i];
+#pragma unroll
+        for (int i = 0; i < m; ++i) su += u[i] * u[i];
+        if (sx > state_max2) {
+          status = ALTRO_STATE_LIMIT;
+          alive = false;
+          done = k;
+        } else if (su > control_max2) {
+          status = ALTRO_CONTROL_LIMIT;
+          alive = false;
+          done = k;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < n; ++i) x[i] = alive ? xn[i] : x[i];
+#pragma unroll
+      for (int i = 0; i < R::nP; ++i) xk[i] = xkn[i];
+#pragma unroll
+      for (int i = 0; i < R::mP; ++i) uk[i] = ukn[i];
+#pragma unroll
+      for (int i = 0; i < RR::KP; ++i) kd[i] = kdn[i];
+      h = hn;
+      t = tn;
+      md = mdn;
+    }
+    // the state the tracking ends in (xk holds Xbar[steps] by now); the terminal knot's cost and violation iff steps == N
+    if (alive) {
+#pragma unroll
+      for (int l = 0; l < n; ++l) mdx = max_(mdx, abs_(x[l] - xk[l]));
+    }
+    T vN = T(0);
+    if (steps == N) {
+#pragma unroll
+      for (int i = 0; i < R::mP; ++i) u[i] = T(0);
+      int rb;
+      const KnotClass& kc = class_of_knot(A, pd, N, &rb);
+      decltype(auto) CN = C.at(N);
+      const T JN = quad_cost<T, n, m>(CN, pd->grp[kc.cost_group], x, u);
+      knot_cost<T, n, m, true>(CN, pd, kc, rb, x, u, &vN);
+      if (alive) {
+        cost += (double)JN;
+        viol = max_(viol, vN);
+      }
+    }
+    {
+      const bool live = alive && mine;
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        double d = (double)(x[i] - xk[i]);
+        pin(d);
+        e[i] = live ? d : 0.0;
+      }
+      ens_reduce<n, 0>(red, lid, e, part + (size_t)steps * V, first);
+      const int na = __popcll(__ballot(live)), nv = __popcll(__ballot(live && steps == N && (double)vN > g.viol_tol));
+      if (lid == 0) {
+        cnt[2 * steps] = first ? na : cnt[2 * steps] + na;
+        cnt[2 * steps + 1] = first ? nv : cnt[2 * steps + 1] + nv;
+      }
+      // the samples of this chunk into the slab's summary
+      acc.finished += na;
+      acc.stopped_state += __popcll(__ballot(mine && status == ALTRO_STATE_LIMIT));
+      acc.stopped_control += __popcll(__ballot(mine && status == ALTRO_CONTROL_LIMIT));
+      acc.violated += __popcll(__ballot(mine && (double)viol > g.viol_tol));
+      acc.cost_sum += ens_wave_sum(live ? cost : 0.0);
+      const double cm = ens_wave_max(live ? cost : ninf);
+      acc.cost_max = cm > acc.cost_max ? cm : acc.cost_max;
+      const double vm = ens_wave_max(mine ? (double)viol : 0.0), xm = ens_wave_max(mine ? (double)mdx : 0.0),
+                   um = ens_wave_max(mine ? (double)mdu : 0.0);
+      acc.viol_max = vm > acc.viol_max ? vm : acc.viol_max;
+      acc.max_dx = xm > acc.max_dx ? xm : acc.max_dx;
+      acc.max_du = um > acc.max_du ? um : acc.max_du;
+    }
+    if (g.stats && mine) {
+      TrackStats st;
+      st.status = status;
+      st.steps_done = done;
+      st.cost = cost;
+      st.violation = (double)viol;
+      st.max_dx = (double)mdx;
+      st.max_du = (double)mdu;
+      g.stats[lane] = st;
+    }
+  }
+  if (lid == 0) q.sums[blockIdx.x] = acc;
+}
+template <class T, class M>
+__global__ __launch_bounds__(kEnsChunk) void k_mpc_ensemble(DevArrays<T> A, const ProblemDesc* __restrict__ pd, EnsLaunch q) {
+  mpc_ensemble_kernel<T, M, CtxTrack<T>>(A, pd, q);
+}
+template <class T, class M>
+__global__ __launch_bounds__(kEnsChunk) void k_mpc_ensemble_trk(DevArrays<T> A, const ProblemDesc* __restrict__ pd, EnsLaunch q) {
+  mpc_ensemble_kernel<T, M, CtxTrackK<T>>(A, pd, q);
+}
+struct EnsFinishArgs {
+  const double* part;
+  const int* cnt;
+  const EnsSlabSum* sums;
+  double *dev_mean, *dev_mom2;
+  int *alive, *viol_count;
+  EnsembleStats* summary;
+  int B, steps, slabs, n, S;
+};
+template <int kDummy>
+__global__ __launch_bounds__(kEnsThreads) void k_ens_finish(EnsFinishArgs g) {
+  const size_t V = (size_t)EnsembleValues(g.n), K1 = (size_t)g.steps + 1, total = (size_t)g.B * K1 * V;
+  const size_t i = (size_t)blockIdx.x * kEnsThreads + threadIdx.x;
+  if (i >= total) return;
+  const size_t b = i / (K1 * V), r = i - b * (K1 * V), k = r / V, v = r - k * V;
+  double sum = 0.0;
+  int na = 0, nv = 0;
+  for (int sl = 0; sl < g.slabs; ++sl) {
+    const size_t at = (b * (size_t)g.slabs + (size_t)sl) * K1 + k;
+    sum += g.part[at * V + v];
+    na += g.cnt[2 * at];
+    nv += g.cnt[2 * at + 1];
+  }
+  const double mean = na > 0 ? sum / (double)na : __builtin_nan("");
+  const size_t n = (size_t)g.n, bk = b * K1 + k;
+  if (v < n) {
+    if (g.dev_mean) g.dev_mean[bk * n + v] = mean;
+  } else if (g.dev_mom2) {
+    const int t = (int)(v - n), row = ens_tri_row(t), col = t - row * (row + 1) / 2;
+    g.dev_mom2[(bk * n + (size_t)row) * n + (size_t)col] = mean;
+    g.dev_mom2[(bk * n + (size_t)col) * n + (size_t)row] = mean;
+  }
+  if (v == 0) {
+    if (g.alive) g.alive[bk] = na;
+    if (g.viol_count) g.viol_count[bk] = nv;
+  }
+  if (v == 0 && k == 0 && g.summary) {
+    EnsembleStats o;
+    o.samples = g.S;
+    int fin = 0;
+    o.stopped_state = o.stopped_control = o.violated = 0;
+    double cs = 0.0, cm = -__builtin_inf();
+    o.violation_max = o.max_dx = o.max_du = 0.0;
+    for (int sl = 0; sl < g.slabs; ++sl) {
+      const EnsSlabSum p = g.sums[b * (size_t)g.slabs + (size_t)sl];
+      fin += p.finished;
+      o.stopped_state += p.stopped_state;
+      o.stopped_control += p.stopped_control;
+      o.violated += p.violated;
+      cs += p.cost_sum;
+      cm = p.cost_max > cm ? p.cost_max : cm;
+      o.violation_max = p.viol_max > o.violation_max ? p.viol_max : o.violation_max;
+      o.max_dx = p.max_dx > o.max_dx ? p.max_dx : o.max_dx;
+      o.max_du = p.max_du > o.max_du ? p.max_du : o.max_du;
+    }
+    o.cost_mean = fin > 0 ? cs / (double)fin : __builtin_nan("");
+    o.cost_max = fin > 0 ? cm : __builtin_nan("");
+    g.summary[b] = o;
+  }
+}
+template <class T>
+__global__ __launch_bounds__(kMsThreads) void k_ms_perturb_gauss(DevArrays<T> A, const double* __restrict__ sigma, int G, int keep_first,
+                                                                 unsigned long long seed, unsigned long long instance_base, int m,
+                                                                 int mP) {
+  static_assert(sizeof(T) == 8, "the controls are fp64 records: two to a 16-byte unit");
+  const size_t V = (size_t)(mP / 2), B = (size_t)A.B, per_knot = B * V, total = (size_t)A.N * per_knot;
+  const size_t i = (size_t)blockIdx.x * kMsThreads + threadIdx.x;
+  if (i >= total) return;
+  const size_t k = i / per_knot, r = i - k * per_knot, b = r / V, v = r - b * V;
+  if (keep_first && b % (size_t)G == 0) return;
+  const int e = 2 * (int)v;
+  if (e >= m) return;  // (padding)
+  double z0, z1;
+  altro_rng::normal_pair(seed, (unsigned)k, 0u, instance_base + b, altro_rng::kStreamControls, (unsigned)v, &z0, &z1);
+  double2* u = reinterpret_cast<double2*>(A.U + (k * (size_t)A.Bp + b) * (size_t)mP) + v;
+  double2 x = *u;
+  x.x = fma(sigma[e], z0, x.x);
+  if (e + 1 < m) x.y = fma(sigma[e + 1], z1, x.y);
+  *u = x;
 }
 
 }  // namespace altro_hip

@@ -41,6 +41,7 @@
 #include "../altro_multistart.h"
 #include "../altro_team.h"
 #include "../altro_covariance.h"
+#include "../altro_ensemble.h"
 #include "../altro_subset.h"
 #include "../altro_trigger.h"
 
@@ -1608,6 +1609,35 @@ class AugmentedLagrangianiLQR {
     ilqr_solver_.Push();
     detail::Check(Handle(), altro_cov_inflate_circles(Handle(), index, base, rows, per_instance ? 1 : 0, kappa, rpos),
                   "altro_cov_inflate_circles");
+  }
+  // Monte-Carlo ensembles (include/altro_ensemble.h): `samples` closed-loop runs per instance under Gaussian initial errors
+  // (Sigma0) and process noise (W, w_mode as PropagateCovariance) drawn ON THE DEVICE, reduced there to per-knot moments of
+  // x_k - Xbar_k and violation counts: dev_mean [B][steps+1][n], dev_mom2 [B][steps+1][n][n] (what PropagateCovariance's Sigma
+  // predicts), alive and viol_count [B][steps+1], summary [B], stats [B][samples]; each may be null, not all outputs.  Changes
+  // nothing on the solver; the bound checks follow GetOptions().  Thin calls giving the C calls' bits.
+  void TrackEnsemble(int steps, int samples, unsigned long long seed, unsigned long long instance_base, const double* Sigma0,
+                     bool sigma0_per_instance, const double* W, int w_mode, const double* u_lo, const double* u_hi, double viol_tol,
+                     double* dev_mean, double* dev_mom2, int* alive = nullptr, int* viol_count = nullptr,
+                     altro_ensemble_stats* summary = nullptr, altro_track_stats* stats = nullptr) {
+    ilqr_solver_.PushOptions();
+    detail::Check(Handle(), altro_mpc_ensemble(Handle(), steps, samples, seed, instance_base, Sigma0, sigma0_per_instance ? 1 : 0, W, w_mode,
+                                               u_lo, u_hi, viol_tol, dev_mean, dev_mom2, alive, viol_count, summary, stats),
+                  "altro_mpc_ensemble");
+  }
+  // ... the arrays TrackClosedLoop takes, dx0 [B][samples][n] and w [B][samples][steps][n], from the same draws
+  void FillNoise(int steps, int samples, unsigned long long seed, unsigned long long instance_base, const double* Sigma0,
+                 bool sigma0_per_instance, const double* W, int w_mode, double* dx0, double* w) {
+    ilqr_solver_.PushOptions();
+    detail::Check(Handle(), altro_noise_fill(Handle(), steps, samples, seed, instance_base, Sigma0, sigma0_per_instance ? 1 : 0, W, w_mode,
+                                             dx0, w),
+                  "altro_noise_fill");
+  }
+  // ... and PerturbControls with the addend drawn on the device: U[b][k][i] += sigma[i] z; sigma [m]
+  void PerturbControlsGaussian(int starts, unsigned long long seed, unsigned long long instance_base, const double* sigma,
+                               bool keep_first = true) {
+    detail::Check(Handle(), altro_multistart_perturb_gaussian(Handle(), starts, seed, instance_base, sigma, keep_first ? 1 : 0),
+                  "altro_multistart_perturb_gaussian");
+    ilqr_solver_.Pull(true, false);
   }
   // al_solver.hpp:287-302: duals and penalties reset as the options say, statistics reset, "viol" and "pen" logged
   void Init() {
