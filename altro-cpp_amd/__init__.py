@@ -980,6 +980,62 @@ class BatchSolver:
         self._call("cov_inflate_circles_device", C.c_int(index), C.c_void_p(base_ptr or None), C.c_int(rows),
                    C.c_int(1 if per_instance else 0), C.c_double(kappa), C.c_void_p(rpos_ptr or None))
 
+    # -- time-varying LQR tracking gains (include/altro_lqr.h) ---------------------------------------
+    def _lqr_weights(self, Q, R, Qf):
+        Q, R, Qf = _f64(Q), _f64(R), _f64(Qf)
+        if Q is None or R is None:
+            raise ValueError("Q and R are required")
+        if Q.shape != (self.n, self.n) or R.shape != (self.m, self.m) or (Qf is not None and Qf.shape != (self.n, self.n)):
+            raise ValueError(f"Q and Qf must have shape ({self.n}, {self.n}), R ({self.m}, {self.m})")
+        return Q, R, Qf
+
+    def lqr_gains(self, Q, R, Qf=None, install=False, want=("K", "P", "fail")):
+        """Time-varying LQR tracking gains about the plan on the device (altro_lqr_gains): P_N = Qf (None: Q),
+        K_k = -(R + B^T P B)^-1 B^T P A, P_k = Q + A^T P A + (B^T P A)^T K_k with [A | B] the discrete Jacobian of knot k at
+        the plan; only the lower triangles of the weights are read.  ``install``: the gains replace K of the handle's gain
+        record (d = 0) for every instance that did not fail.  Returns a dict of the arrays named in ``want``: K [B][N][m][n]
+        (as get_gains returns it), P [B][N+1][n][n], fail int32 [B] (-1, or the knot at which the instance failed: its K and
+        P from there down are NaN)."""
+        Q, R, Qf = self._lqr_weights(Q, R, Qf)
+        B, N, n, m = self.batch, self.N, self.n, self.m
+        unknown = [k for k in want if k not in ("K", "P", "fail")]
+        if unknown:
+            raise ValueError(f"want names K, P, fail; got {unknown}")
+        K = np.zeros((B, N, n, m)) if "K" in want else None  # column-major m x n per knot
+        Pm = np.zeros((B, N + 1, n, n)) if "P" in want else None
+        fail = np.zeros(max(B, 1), dtype=np.int32) if "fail" in want else None
+        self._call("lqr_gains", _dp(Q), _dp(R), _dp(Qf), C.c_int(1 if install else 0), _dp(K), _dp(Pm), self._ip(fail))
+        out = {}
+        if K is not None:
+            out["K"] = np.swapaxes(K, 2, 3)
+        if Pm is not None:
+            out["P"] = Pm
+        if fail is not None:
+            out["fail"] = fail[:B]
+        return out
+
+    def lqr_gains_device(self, Q_ptr, R_ptr, Qf_ptr=0, install=False, K_ptr=0, P_ptr=0, fail_ptr=0):
+        """lqr_gains with every array in memory of this handle's device (fp64; ``fail`` int32); K is [B][N][m n], column-major
+        m x n per knot.  Any output pointer may be 0."""
+        self._call("lqr_gains_device", C.c_void_p(Q_ptr or None), C.c_void_p(R_ptr or None), C.c_void_p(Qf_ptr or None),
+                   C.c_int(1 if install else 0), C.c_void_p(K_ptr or None), C.c_void_p(P_ptr or None), C.c_void_p(fail_ptr or None))
+
+    def set_lqr_policy(self, Q=None, R=None, Qf=None):
+        """While the policy is on, every whole solve of this handle ends with lqr_gains(Q, R, Qf, install=True) for the
+        instances it ran (altro_lqr_set_policy).  ``Q`` None: off."""
+        if Q is None:
+            self._call("lqr_set_policy", None, None, None)
+            return
+        Q, R, Qf = self._lqr_weights(Q, R, Qf)
+        self._call("lqr_set_policy", _dp(Q), _dp(R), _dp(Qf))
+
+    def get_lqr_policy(self):
+        """None while the policy is off, else the dict Q, R, Qf of the symmetric matrices it holds."""
+        on = C.c_int(0)
+        Q, R, Qf = np.zeros((self.n, self.n)), np.zeros((self.m, self.m)), np.zeros((self.n, self.n))
+        self._call("lqr_get_policy", C.byref(on), _dp(Q), _dp(R), _dp(Qf))
+        return dict(Q=Q, R=R, Qf=Qf) if on.value else None
+
     # -- Monte-Carlo ensembles (include/altro_ensemble.h) --------------------------------------------
     ENSEMBLE_OUTPUTS = ("dev_mean", "dev_mom2", "alive", "viol_count", "summary", "stats")
 

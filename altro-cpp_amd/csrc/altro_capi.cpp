@@ -42,12 +42,13 @@
 #include "../../include/altro_subset.h"
 #include "../../include/altro_trigger.h"
 #include "../../include/altro_ensemble.h"
+#include "../../include/altro_lqr.h"
 
 using namespace altro_hip;
 
 extern "C" int altro_chain_claim(int device, int delta);
 
-#define ALTRO_USER_PLUGIN_ABI_HOST 16  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
+#define ALTRO_USER_PLUGIN_ABI_HOST 17  // must equal ALTRO_USER_PLUGIN_ABI of altro_user_model.hpp
 
 struct altro_solver_s {
   ProblemSpec spec;
@@ -58,6 +59,7 @@ struct altro_solver_s {
   bool has_gains = false;  // a backward pass (a solve, altro_backward_pass) has left gains on the device: altro_mpc_track
   bool record_ctg = false;  // altro_set_record_ctg(h, 1) went through: masked solves, and so the trigger calls, refuse the handle
   bool has_solved = false;  // a whole solve (altro_solve_al, altro_solve_ilqr, altro_wait) has finished: altro_multistart_select
+  std::vector<double> lqr_policy;  // the gain policy (include/altro_lqr.h): packed weights (LqrPackWeights); empty: off
   std::string err;
   // Asynchronous solve (altro_solve_al_async): ONE worker thread per handle, created on first use and
   // parked on a condition variable between solves.  While a solve is pending the handle only answers
@@ -309,7 +311,10 @@ altro_status Ensure(altro_handle h) {
     h->engine.reset(e);
   }
   altro_status st = h->engine->Upload(h->spec, &h->err);
-  if (st == ALTRO_OK) h->uploaded = true;
+  if (st == ALTRO_OK) {
+    h->uploaded = true;
+    h->engine->LqrSetPolicy(h->lqr_policy);  // (a policy set before the device state existed)
+  }
   return st;
 }
 
@@ -1934,6 +1939,97 @@ altro_status altro_cov_inflate_circles_device(altro_handle h, int index, const v
                                               double kappa, const void* rpos_device) {
   return CovInflateImpl(h, index, (const double*)base_device, rows, per_instance, kappa, (const double*)rpos_device, 1,
                         "altro_cov_inflate_circles_device");
+}
+
+}  // extern "C"
+
+// ---- time-varying LQR tracking gains (include/altro_lqr.h) ---------------------------------------------------------------
+static_assert(ALTRO_LQR_MAX_STATES == kLqrMaxN && ALTRO_LQR_MAX_CONTROLS == kLqrMaxM, "the header states the kernels' limits");
+namespace {
+
+// what every call refuses alike, without a device: the handle, an asynchronous solve, the dimensions
+altro_status LqrCheck(altro_handle h, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  const int n = h->spec.desc.n, m = h->spec.desc.m;
+  if (m < 1 || m > kLqrMaxM || n > kLqrMaxN) {
+    h->err = std::string(who) + ": 1 .. " + std::to_string(kLqrMaxM) + " controls and at most " + std::to_string(kLqrMaxN) +
+             " states are supported, the handle has n = " + std::to_string(n) + ", m = " + std::to_string(m);
+    return ALTRO_UNSUPPORTED;
+  }
+  return ALTRO_OK;
+}
+altro_status LqrGainsImpl(altro_handle h, const double* Q, const double* R, const double* Qf, int install, double* K, double* P, int* fail,
+                          int on_device, const char* who) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (!Q || !R) {
+    h->err = std::string(who) + ": Q and R are required";
+    return ALTRO_INVALID_ARG;
+  }
+  if (!install && !K && !P) {
+    h->err = std::string(who) + ": nothing asked for: K or P is required unless the gains are installed";
+    return ALTRO_INVALID_ARG;
+  }
+  altro_status st = LqrCheck(h, who);
+  if (st != ALTRO_OK) return st;
+  if (!on_device) {  // (the engine packs them again for its launch; a device caller's weights are checked there)
+    std::vector<double> packed;
+    if (!LqrPackWeights(h->spec.desc.n, h->spec.desc.m, Q, R, Qf, &packed, &h->err, who)) return ALTRO_INVALID_ARG;
+  }
+  const LqrArgs g{Q, R, Qf, install ? 1 : 0, K, P, fail};
+  st = Forward(h, [&](EngineBase& e) { return e.LqrGains(g, on_device); });
+  if (install) return GainsAfter(h, st);
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+altro_status altro_lqr_gains(altro_handle h, const double* Q, const double* R, const double* Qf, int install, double* K, double* P,
+                             int* fail) {
+  return LqrGainsImpl(h, Q, R, Qf, install, K, P, fail, 0, "altro_lqr_gains");
+}
+altro_status altro_lqr_gains_device(altro_handle h, const void* Q_device, const void* R_device, const void* Qf_device, int install,
+                                    void* K_device, void* P_device, void* fail_device) {
+  return LqrGainsImpl(h, (const double*)Q_device, (const double*)R_device, (const double*)Qf_device, install, (double*)K_device,
+                      (double*)P_device, (int*)fail_device, 1, "altro_lqr_gains_device");
+}
+altro_status altro_lqr_set_policy(altro_handle h, const double* Q, const double* R, const double* Qf) {
+  const char* who = "altro_lqr_set_policy";
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  std::vector<double> packed;
+  if (Q) {
+    if (!R) {
+      h->err = std::string(who) + ": R is required with Q";
+      return ALTRO_INVALID_ARG;
+    }
+    const altro_status st = LqrCheck(h, who);
+    if (st != ALTRO_OK) return st;
+    if (!LqrPackWeights(h->spec.desc.n, h->spec.desc.m, Q, R, Qf, &packed, &h->err, who)) return ALTRO_INVALID_ARG;
+  }
+  h->lqr_policy = packed;
+  if (h->uploaded) h->engine->LqrSetPolicy(h->lqr_policy);
+  return ALTRO_OK;
+}
+altro_status altro_lqr_get_policy(altro_handle h, int* on, double* Q, double* R, double* Qf) {
+  if (!h) return ALTRO_INVALID_ARG;
+  if (Busy(h)) return ALTRO_NOT_READY;
+  if (!on) {
+    h->err = "altro_lqr_get_policy: on is required";
+    return ALTRO_INVALID_ARG;
+  }
+  *on = h->lqr_policy.empty() ? 0 : 1;
+  if (*on) {
+    const size_t nn = (size_t)h->spec.desc.n * h->spec.desc.n, mm = (size_t)h->spec.desc.m * h->spec.desc.m;
+    const double* w = h->lqr_policy.data();
+    if (Q) std::copy(w, w + nn, Q);
+    if (R) std::copy(w + nn, w + nn + mm, R);
+    if (Qf) std::copy(w + nn + mm, w + 2 * nn + mm, Qf);
+  }
+  return ALTRO_OK;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <initializer_list>
 #include <string>
@@ -170,6 +171,55 @@ struct CovArgs {
   const double *Sigma0, *W;                // [n][n] | [B][n][n];  [n][n] | [B][n][n] | [steps][n][n] | [B][steps][n][n]
   double *Sigma, *sx, *su, *rpos;          // [B][steps + 1][n][n], [B][steps + 1][n], [B][steps][m], [B][steps + 1]
 };
+
+// ---- time-varying LQR tracking gains (include/altro_lqr.h) -----------------------------------------------------------------
+constexpr int kLqrMaxN = 32;  // states (as kCovMaxN: k_lqr_recur has k_cov_recur's lane groups)
+constexpr int kLqrMaxM = 8;   // controls: every lane factors S = R + B^T P B on its own
+// One call of Engine::LqrGains.  Q, R (required) and Qf (null: Q) are [n][n], [m][m], [n][n]; K [B][N][m n], P [B][N + 1][n][n]
+// and fail [B] may be null; host or device memory as the call says.
+struct LqrArgs {
+  const double *Q, *R, *Qf;
+  int install;
+  double *K, *P;
+  int* fail;
+};
+// The weights as k_lqr_recur reads them: Q | R | Qf with every lower triangle mirrored, Qf = Q where it is null.  Refuses a
+// lower-triangle entry that is not finite and an R whose lower triangle has no Cholesky factor; `err` gets the text.
+inline bool LqrPackWeights(int n, int m, const double* Q, const double* R, const double* Qf, std::vector<double>* out, std::string* err,
+                           const char* who) {
+  out->assign((size_t)(2 * n * n + m * m), 0.0);
+  double *q = out->data(), *r = q + n * n, *qf = r + m * m;
+  auto mirror = [&](const double* src, int d, double* dst, const char* name) {
+    for (int i = 0; i < d; ++i)
+      for (int j = 0; j <= i; ++j) {
+        const double v = src[i * d + j];
+        if (!std::isfinite(v)) {
+          *err = std::string(who) + ": " + name + "[" + std::to_string(i) + "][" + std::to_string(j) + "] is not finite";
+          return false;
+        }
+        dst[i * d + j] = dst[j * d + i] = v;
+      }
+    return true;
+  };
+  if (!mirror(Q, n, q, "Q") || !mirror(R, m, r, "R") || !mirror(Qf ? Qf : Q, n, qf, "Qf")) return false;
+  std::vector<double> L(r, r + m * m);  // Cholesky of R by rows, in place in the lower triangle
+  for (int c = 0; c < m; ++c) {
+    double d = L[c * m + c];
+    for (int t = 0; t < c; ++t) d -= L[c * m + t] * L[c * m + t];
+    if (!(d > 0.0) || !std::isfinite(d)) {
+      *err = std::string(who) + ": R is not positive definite (the Cholesky pivot of row " + std::to_string(c) + " is " + std::to_string(d) + ")";
+      return false;
+    }
+    const double root = std::sqrt(d);
+    L[c * m + c] = root;
+    for (int a = c + 1; a < m; ++a) {
+      double v = L[a * m + c];
+      for (int t = 0; t < c; ++t) v -= L[a * m + t] * L[c * m + t];
+      L[a * m + c] = v / root;
+    }
+  }
+  return true;
+}
 
 // ---- Monte-Carlo ensembles (include/altro_ensemble.h) --------------------------------------------------------------------
 // altro_ensemble_stats as k_ens_finish writes it (the C-ABI translation unit asserts that the two layouts agree)
@@ -706,6 +756,11 @@ class EngineBase {
   virtual altro_status NoiseFill(const EnsembleArgs& call, int on_device) = 0;
   virtual altro_status MsPerturbGaussian(int G, unsigned long long seed, unsigned long long instance_base, const double* sigma,
                                          int keep_first) = 0;
+  // time-varying LQR tracking gains about the plan (include/altro_lqr.h).  LqrGains: host arrays, or (on_device) memory of the
+  // engine's device; with `install` the gains replace K of the gain record (d = 0) where the instance did not fail.  The policy
+  // (packed weights of LqrPackWeights; empty: off) makes every whole solve end with that pass, installed under the solve's mask.
+  virtual altro_status LqrGains(const LqrArgs& call, int on_device) = 0;
+  virtual void LqrSetPolicy(const std::vector<double>& packed) = 0;
   virtual const char* LastError() = 0;
 };
 

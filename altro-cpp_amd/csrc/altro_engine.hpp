@@ -1253,6 +1253,79 @@ class Engine final : public EngineBase {
     return ALTRO_OK;
   }
 
+  // ---- time-varying LQR tracking gains (include/altro_lqr.h) -----------------------------------------
+  // k_lqr_linearise over (instance, knot), k_lqr_recur along the knots, k_lqr_install over (instance, knot), all on the
+  // engine's stream, through the covariance's scratch block grown to [A | B] | K | P | weights | fail (the two users follow
+  // each other on one stream).  `w` (LqrPackWeights) must live until the stream is done.  K, P, fail: device memory or null.
+  altro_status LqrUnsupported() {
+    err_ = "altro_lqr_gains: 1 .. " + std::to_string(kLqrMaxM) + " controls and at most " + std::to_string(kLqrMaxN) + " states are supported";
+    return ALTRO_UNSUPPORTED;
+  }
+  altro_status LaunchLqr(const std::vector<double>& w, int install, const unsigned char* mask, double* K, double* P, int* fail) {
+    if constexpr (!lqr_supported(n, m)) {
+      return LqrUnsupported();
+    } else {
+      const size_t nab = (size_t)N_ * n * nm * Bp_, nk = (size_t)N_ * m * n * Bp_, np = (size_t)(N_ + 1) * n * n * Bp_;
+      const size_t nw = ((size_t)(2 * n * n + m * m) + 1) & ~(size_t)1, nfail = ((size_t)Bp_ + 1) / 2, need = nab + nk + np + nw + nfail;
+      if (need > hm_.cov_f.count() && hm_.cov_f.alloc(need) != hipSuccess) {
+        err_ = "altro_lqr_gains: out of device memory for " + std::to_string(need * sizeof(double)) + " bytes of linearisations and gains";
+        return ALTRO_HIP_ERROR;
+      }
+      double *AB = hm_.cov_f.get(), *Kt = AB + nab, *Pt = Kt + nk, *Wt = Pt + np;
+      int* const failS = reinterpret_cast<int*>(Wt + nw);
+      ALTRO_HIP_CHECK(hipMemcpyAsync(Wt, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+      hipLaunchKernelGGL((k_lqr_linearise<T, M>), dim3((B_ + kBlock - 1) / kBlock, N_), dim3(kBlock), 0, stream_, A_, up_.d_pd, AB);
+      constexpr int per_block = kBlock / cov_group(n);
+      hipLaunchKernelGGL((k_lqr_recur<n, m>), dim3((B_ + per_block - 1) / per_block), dim3(kBlock), 0, stream_, (const double*)AB,
+                         (const double*)Wt, Kt, Pt, failS, B_, (unsigned)Bp_, N_);
+      if (install) ctg_replayable_ = false;  // (a replayed backward pass would write the solver's gains back over these)
+      hipLaunchKernelGGL((k_lqr_install<RS, n, m>), dim3((B_ + kBlock - 1) / kBlock, N_ + 1), dim3(kBlock), 0, stream_, A_.KD,
+                         (const double*)Kt, (const double*)Pt, (const int*)failS, mask, install, K, P, fail, B_, (unsigned)Bp_, N_);
+      return ALTRO_OK;
+    }
+  }
+  altro_status LqrGains(const LqrArgs& call, int on_device) override {
+    const char* who = on_device ? "altro_lqr_gains_device" : "altro_lqr_gains";
+    if (!call.Q || !call.R || (!call.install && !call.K && !call.P)) {
+      err_ = std::string(who) + ": Q and R are required, and K or P unless the gains are installed";
+      return ALTRO_INVALID_ARG;
+    }
+    if (!lqr_supported(n, m)) return LqrUnsupported();
+    if (!StepOk()) return ALTRO_NOT_READY;
+    ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
+    // the weights of a device caller come to the host to be checked and mirrored, like a host caller's
+    std::vector<double> hq, hr, hf;
+    const double *Q = call.Q, *Rw = call.R, *Qf = call.Qf;
+    if (on_device) {
+      hq.resize(n * n), hr.resize(m * m), hf.resize(n * n);
+      ALTRO_HIP_CHECK(CopySync(hq.data(), call.Q, hq.size() * sizeof(double), hipMemcpyDeviceToHost));
+      ALTRO_HIP_CHECK(CopySync(hr.data(), call.R, hr.size() * sizeof(double), hipMemcpyDeviceToHost));
+      if (call.Qf) ALTRO_HIP_CHECK(CopySync(hf.data(), call.Qf, hf.size() * sizeof(double), hipMemcpyDeviceToHost));
+      Q = hq.data(), Rw = hr.data(), Qf = call.Qf ? hf.data() : nullptr;
+    }
+    if (!LqrPackWeights(n, m, Q, Rw, Qf, &lqr_w_, &err_, who)) return ALTRO_INVALID_ARG;
+    // the staged block of a host caller: K | P | fail (ints two to a double; they reach the caller through `hfail`)
+    const size_t B = (size_t)B_;
+    const Parts<3> p{call.K ? B * N_ * m * n : 0, call.P ? B * (N_ + 1) * n * n : 0, call.fail ? (B + 1) / 2 : 0};
+    DevBlock<double> stage;
+    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
+      err_ = std::string(who) + ": out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
+      return ALTRO_HIP_ERROR;
+    }
+    Staged<3> sg(on_device != 0, stage.get(), p, stream_);
+    std::vector<double> hfail(on_device ? 0 : p.cnt[2]);
+    double* const K = sg.out(0, call.K);
+    double* const P = sg.out(1, call.P);
+    int* const fail = on_device ? call.fail : reinterpret_cast<int*>(sg.out(2, p.cnt[2] ? hfail.data() : nullptr));
+    const altro_status s = LaunchLqr(lqr_w_, call.install, nullptr, K, P, fail);
+    const hipError_t e = sg.finish(s == ALTRO_OK);
+    ALTRO_TRY(s);
+    ALTRO_HIP_CHECK(e);
+    if (!on_device && call.fail) std::memcpy(call.fail, hfail.data(), B * sizeof(int));
+    return ALTRO_OK;
+  }
+  void LqrSetPolicy(const std::vector<double>& packed) override { lqr_policy_ = packed; }
+
   // ---- closed-loop tracking (include/altro_mpc.h) ---------------------------------------------------
   // One launch of k_mpc_track, one lane per (instance, sample).  Host arrays are staged through ONE device block that lives
   // for the call; device arrays are used where they are.  Reads the engine's arrays only: no flag of the engine changes.
@@ -2713,6 +2786,12 @@ class Engine final : public EngineBase {
     if (r.prof) AccountProfile(r);
     timing_.instance_iterations = -1;  // summed on demand (GetTiming): keeps a copy out of every solve
     timing_.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t0).count();
+    if (!lqr_policy_.empty()) {
+      // the gain policy (include/altro_lqr.h): the tracking gains of the plan this solve left replace the solver's, for the
+      // instances it ran
+      ALTRO_TRY(LaunchLqr(lqr_policy_, 1, mask_.on ? hm_.mask.get() : nullptr, nullptr, nullptr, nullptr));
+      ALTRO_TRY(Sync());
+    }
     return ALTRO_OK;
   }
   // host state of a solve: options, flags of the results, the bound on the sweeps and the counters that go with it
@@ -3472,7 +3551,8 @@ class Engine final : public EngineBase {
     DevBlock<int> d_counter;     // ... and its device twin (ReserveCounters)
     LoopRun run;                 // the closed-loop run in progress (LoopBegin .. LoopEnd)
     DevBlock<int> ms_win;        // winners of the last multi-start call, [B] (MsCheck)
-    DevBlock<double> cov_f;      // covariance: F | Kw of the last propagation, [steps][n n + m n][Bp] (LaunchCov)
+    DevBlock<double> cov_f;      // covariance: F | Kw of the last propagation, [steps][n n + m n][Bp] (LaunchCov); grown by
+                                 // LaunchLqr to [A | B] | K | P | weights | fail of the last LQR pass (one stream: never both)
     DevBlock<double> team_rad;   // teams: radius per instance [B] | clearances of a host call [B] (TeamRadius)
     // the solve mask (SetSolveMask): a byte per instance [B]; the masked-in instances of every chain slice, ascending, at the
     // slice's own place [B], then the slices' counts and their sum [kMaxSweepChains + 1] (k_mask_compact)
@@ -3501,6 +3581,8 @@ class Engine final : public EngineBase {
   DevOpts last_opts_{};          // options of the last whole solve (ReplayCtg)
   bool ctg_fresh_ = false;       // the cost-to-go records are those of the last backward pass
   bool ctg_replayable_ = false;  // ... or can be recomputed from what the last whole solve left in memory
+  std::vector<double> lqr_w_;       // packed weights of the LQR pass on the stream (LqrPackWeights); they outlive their copy
+  std::vector<double> lqr_policy_;  // ... of the gain policy (include/altro_lqr.h); empty: off
   ProblemDesc pd_{};
   DevArrays<T> A_{};
   void SegArrays(DevArrays<T>& A) const {  // the bookkeeping arrays of the segments into a launch's copy of A_

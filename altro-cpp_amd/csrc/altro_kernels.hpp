@@ -6068,25 +6068,33 @@ constexpr int cov_group(int n) {
   while (G < n) G *= 2;
   return G;
 }
+// [A_k | B_k] of instance b, column-major n x (n + m): the discrete Jacobian of knot k's own model, step and time at
+// (Xbar_k, Ubar_k), as expansion_body evaluates it.  Shared by k_cov_linearise and k_lqr_linearise.
+template <class T, class M>
+__device__ __forceinline__ void plan_jacobian(const DevArrays<T>& A, const ProblemDesc* __restrict__ pd, int b, int k, T* J) {
+  constexpr int n = M::n, m = M::m;
+  using R = Rec<T, n, m>;
+  const unsigned Bp = A.Bp;
+  T x[R::nP], u[R::mP];
+  load_rec<T, R::nP>(RECP(A.X, k, R::nP), x);
+  load_rec<T, R::mP>(RECP(A.U, k, R::mP), u);
+#pragma unroll
+  for (int e = 0; e < n * (n + m); ++e) J[e] = T(0);
+  discrete_jacobian<T, M>(x, u, step_of(A, pd, k), J, time_of(A, k), model_of(A, k));
+}
 template <class T, class M>
 __global__ __launch_bounds__(kBlock) void k_cov_linearise(DevArrays<T> A, const ProblemDesc* __restrict__ pd, double* __restrict__ F,
                                                           double* __restrict__ Kw) {
   constexpr int n = M::n, m = M::m;
-  using R = Rec<T, n, m>;
   using RS = rec_scalar_t<T, M>;
   using RR = Rec<RS, n, m>;
   const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
   if (b >= A.B) return;
   const unsigned Bp = A.Bp;
-  T x[R::nP], u[R::mP];
   RS kd[RR::KP];
-  load_rec<T, R::nP>(RECP(A.X, k, R::nP), x);
-  load_rec<T, R::mP>(RECP(A.U, k, R::mP), u);
   load_rec<RS, RR::KP>(RECP((const RS*)A.KD, k, RR::KP), kd);
   T J[n * (n + m)];
-#pragma unroll
-  for (int e = 0; e < n * (n + m); ++e) J[e] = T(0);
-  discrete_jacobian<T, M>(x, u, step_of(A, pd, k), J, time_of(A, k), model_of(A, k));
+  plan_jacobian<T, M>(A, pd, b, k, J);
   double* const Fk = F + (size_t)k * (size_t)(n * n) * Bp + (unsigned)b;
 #pragma unroll
   for (int i = 0; i < n; ++i)
@@ -6236,6 +6244,265 @@ __global__ __launch_bounds__(kTeamThreads) void k_cov_inflate(double* __restrict
   dst[0] = src[0];
   dst[1] = src[1];
   dst[2] = src[2] + kappa * rpos[b * (size_t)(N + 1) + (size_t)at];
+}
+
+// -------------------------------------------------------------------------------------------------
+// Time-varying LQR tracking gains about the plan (include/altro_lqr.h): P_N = Qf, and for k = N - 1 .. 0
+//     S = R + B^T P B,  G = B^T P A,  K_k = -S^-1 G,  P_k = Q + A^T P A + G^T K_k        (P = P_{k+1}, [A | B] of knot k)
+// in fp64 throughout.  Everything between the three kernels is stored with the INSTANCE FASTEST, as k_cov_linearise does.
+//
+// k_lqr_linearise  ONE LANE PER (instance, knot), knot = blockIdx.y < N: plan_jacobian, stored column-major as it comes,
+//                  AB[(k * n (n + m) + e) * Bp + b].
+// k_lqr_recur      serial over the knots, model-independent, in the shape of k_cov_recur: an instance is a group of
+//                  G = cov_group(n) adjacent lanes of a one-wave workgroup, lane i holding row i (= column i) of P in registers.
+//                  Per knot: lane i forms row i of W = P [A | B] ([A | B] from LDS, one address per group); the rows go through
+//                  LDS once; lane c takes column c of W_A and forms column c of Q + A^T W_A and of G = B^T W_A; EVERY lane forms
+//                  the lower triangle of S = R + B^T W_B, factors it (S = L D L^T, the Cholesky factorisation without its square
+//                  roots: the pivots d have the sign of Cholesky's, m reciprocals are all the chain divides by) and solves for its
+//                  own column of K; the columns of G go through LDS, lane c adds G^T K[:, c] to its column, the columns go
+//                  through LDS and lane i takes element (i, l) from the lane that owns its lower-triangle twin: P_k is symmetric
+//                  bit for bit.  [A | B] of knot k - 1 is requested at the top of the step and moved into the other half of a
+//                  double LDS buffer at its end.  K_k and P_k are stored off the chain.  An instance FAILS at the largest k at
+//                  which a pivot is not positive or a value of K_k or P_k is not finite (the lanes of a group agree through a
+//                  ballot): K and P from that knot down are quiet NaN, fail[b] = k, otherwise -1.  Every register array is
+//                  indexed by unrolled constants only: no scratch.  The order of every sum is a function of (n, m) alone.
+//                  LDS: 2 * (64 / G) * (n (n + m) | 1) + 64 * ((n + m) | 1) doubles, at most 61952 bytes (n = 32, m = 8): every
+//                  (n, m) with n <= kLqrMaxN, 1 <= m <= kLqrMaxM fits 64 KiB (lqr_lds_bytes).
+// k_lqr_install    one lane per (instance, knot <= N): where fail[b] < 0 and the mask (if any) is set it writes K_k | d = 0 into
+//                  the gain record in its storage type; it transposes K, P and fail into the caller's instance-major arrays.
+// -------------------------------------------------------------------------------------------------
+static_assert(kLqrMaxN == kCovMaxN, "k_lqr_recur takes its groups from cov_group");
+constexpr bool lqr_supported(int n, int m) { return n >= 1 && n <= kLqrMaxN && m >= 1 && m <= kLqrMaxM; }
+constexpr size_t lqr_lds_bytes(int n, int m) {
+  return sizeof(double) * (size_t)(2 * (kBlock / cov_group(n)) * ((n * (n + m)) | 1) + kBlock * ((n + m) | 1));
+}
+template <class T, class M>
+__global__ __launch_bounds__(kBlock) void k_lqr_linearise(DevArrays<T> A, const ProblemDesc* __restrict__ pd, double* __restrict__ AB) {
+  constexpr int n = M::n, m = M::m, E = n * (n + m);
+  const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
+  if (b >= A.B) return;
+  const unsigned Bp = A.Bp;
+  T J[E];
+  plan_jacobian<T, M>(A, pd, b, k, J);
+  double* const dst = AB + (size_t)k * (size_t)E * Bp + (unsigned)b;
+#pragma unroll
+  for (int e = 0; e < E; ++e) dst[(size_t)e * Bp] = (double)J[e];
+}
+
+// Wt: Q [n][n] | R [m][m] | Qf [n][n], each symmetric (the host mirrors the lower triangles)
+template <int n, int m>
+__global__ __launch_bounds__(kBlock) void k_lqr_recur(const double* __restrict__ AB, const double* __restrict__ Wt, double* __restrict__ Kt,
+                                                      double* __restrict__ Pt, int* __restrict__ fail, int B, unsigned Bp, int N) {
+  if constexpr (lqr_supported(n, m)) {
+    static_assert(lqr_lds_bytes(n, m) <= 65536, "k_lqr_recur: the double [A | B] buffer and the exchange rows fit 64 KiB of LDS");
+    constexpr int G = cov_group(n), IPB = kBlock / G, E = n * (n + m), AS = E | 1, NS = (n + m) | 1, FE = (E + G - 1) / G;
+    constexpr int SP = m * (m + 1) / 2;  // S, then its factor, packed by rows: (a, c), a >= c, at a (a + 1) / 2 + c
+    __shared__ double sAB[2][IPB][AS];
+    __shared__ double sX[IPB][G][NS];
+    const int grp = threadIdx.x / G, i_raw = threadIdx.x % G, b_raw = blockIdx.x * IPB + grp;
+    const bool live = b_raw < B && i_raw < n;
+    const int b = b_raw < B ? b_raw : B - 1, i = i_raw < n ? i_raw : n - 1;
+    const unsigned long long group_lanes = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (grp * G);
+    const double* const ABb = AB + (unsigned)b;
+    const double qnan = __builtin_nan("");
+    double an[FE], p[n], q[n], r[SP];
+#pragma unroll
+    for (int t = 0; t < FE; ++t) {
+      const int e = i_raw + G * t;
+      if (e < E) sAB[0][grp][e] = ABb[((size_t)(N - 1) * E + (size_t)e) * Bp];
+    }
+#pragma unroll
+    for (int l = 0; l < n; ++l) {
+      q[l] = Wt[i * n + l];
+      p[l] = Wt[n * n + m * m + i * n + l];
+    }
+#pragma unroll
+    for (int a = 0; a < m; ++a)
+#pragma unroll
+      for (int c = 0; c <= a; ++c) r[a * (a + 1) / 2 + c] = Wt[n * n + a * m + c];
+    if (live) {
+      double* const dst = Pt + ((size_t)N * (n * n) + (size_t)(i * n)) * Bp + (unsigned)b;
+#pragma unroll
+      for (int l = 0; l < n; ++l) dst[(size_t)l * Bp] = p[l];
+    }
+    __syncthreads();
+    int cur = 0, failed = -1;
+    for (int k = N - 1; k >= 0; --k) {
+      const bool prefetch = k > 0;
+      if (prefetch) {
+#pragma unroll
+        for (int t = 0; t < FE; ++t) {
+          const int e = i_raw + G * t;
+          an[t] = e < E ? ABb[((size_t)(k - 1) * E + (size_t)e) * Bp] : 0.0;
+        }
+      }
+      const double* const J = sAB[cur][grp];
+      // row i of W = P [A | B]
+#pragma unroll
+      for (int j = 0; j < n + m; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; ++l) acc += p[l] * J[l + j * n];
+        sX[grp][i_raw][j] = acc;
+      }
+      __syncthreads();
+      // column i of W_A; with it column i of Q + A^T W_A and of G = B^T W_A
+      double wa[n], v[n], g[m];
+#pragma unroll
+      for (int l = 0; l < n; ++l) wa[l] = sX[grp][l][i];
+#pragma unroll
+      for (int rr = 0; rr < n; ++rr) {
+        double acc = q[rr];
+#pragma unroll
+        for (int l = 0; l < n; ++l) acc += J[l + rr * n] * wa[l];
+        v[rr] = acc;
+      }
+#pragma unroll
+      for (int a = 0; a < m; ++a) {
+        double acc = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; ++l) acc += J[n * n + l + a * n] * wa[l];
+        g[a] = acc;
+      }
+      // the lower triangle of S = R + B^T W_B, on every lane
+      double s[SP];
+#pragma unroll
+      for (int a = 0; a < m; ++a)
+#pragma unroll
+        for (int c = 0; c <= a; ++c) {
+          double acc = r[a * (a + 1) / 2 + c];
+#pragma unroll
+          for (int l = 0; l < n; ++l) acc += J[n * n + l + a * n] * sX[grp][l][n + c];
+          s[a * (a + 1) / 2 + c] = acc;
+        }
+      // S = L D L^T in place: s(a, c), a > c, becomes L(a, c); the pivots and their reciprocals go to dd and dinv; un[] is
+      // column c before its division, ld[] is row c of L D
+      bool bad = false;
+      double dd[m], dinv[m];
+#pragma unroll
+      for (int c = 0; c < m; ++c) {
+        double un[m], ld[m];
+#pragma unroll
+        for (int t = 0; t < c; ++t) ld[t] = s[c * (c + 1) / 2 + t] * dd[t];
+#pragma unroll
+        for (int a = c; a < m; ++a) {
+          double acc = s[a * (a + 1) / 2 + c];
+#pragma unroll
+          for (int t = 0; t < c; ++t) acc -= s[a * (a + 1) / 2 + t] * ld[t];
+          un[a] = acc;
+        }
+        bad = bad || !(un[c] > 0.0);
+        dd[c] = un[c];
+        dinv[c] = 1.0 / un[c];
+#pragma unroll
+        for (int a = c + 1; a < m; ++a) s[a * (a + 1) / 2 + c] = un[a] * dinv[c];
+      }
+      // column i of K = -S^-1 G: L y = -g, z = D^-1 y, L^T x = z
+      double kc[m];
+#pragma unroll
+      for (int a = 0; a < m; ++a) {
+        double acc = -g[a];
+#pragma unroll
+        for (int t = 0; t < a; ++t) acc -= s[a * (a + 1) / 2 + t] * kc[t];
+        kc[a] = acc;
+      }
+#pragma unroll
+      for (int a = 0; a < m; ++a) kc[a] *= dinv[a];
+#pragma unroll
+      for (int a = m - 1; a >= 0; --a) {
+        double acc = kc[a];
+#pragma unroll
+        for (int t = a + 1; t < m; ++t) acc -= s[t * (t + 1) / 2 + a] * kc[t];
+        kc[a] = acc;
+      }
+      __syncthreads();
+      // the columns of G through LDS; column i of the new P
+#pragma unroll
+      for (int a = 0; a < m; ++a) sX[grp][i_raw][a] = g[a];
+      __syncthreads();
+#pragma unroll
+      for (int rr = 0; rr < n; ++rr) {
+        double acc = v[rr];
+#pragma unroll
+        for (int a = 0; a < m; ++a) acc += sX[grp][rr][a] * kc[a];
+        v[rr] = acc;
+      }
+      // the instance fails here if any of its lanes says so; from then on it hands out quiet NaN
+#pragma unroll
+      for (int a = 0; a < m; ++a) bad = bad || !__builtin_isfinite(kc[a]);
+#pragma unroll
+      for (int rr = 0; rr < n; ++rr) bad = bad || !__builtin_isfinite(v[rr]);
+      if ((__ballot(bad) & group_lanes) != 0ull && failed < 0) failed = k;
+      if (failed >= 0) {
+#pragma unroll
+        for (int a = 0; a < m; ++a) kc[a] = qnan;
+#pragma unroll
+        for (int rr = 0; rr < n; ++rr) v[rr] = qnan;
+      }
+      if (live) {
+        double* const dst = Kt + ((size_t)k * (m * n) + (size_t)(i * m)) * Bp + (unsigned)b;
+#pragma unroll
+        for (int a = 0; a < m; ++a) dst[(size_t)a * Bp] = kc[a];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int rr = 0; rr < n; ++rr) sX[grp][i_raw][rr] = v[rr];
+      if (prefetch) {
+#pragma unroll
+        for (int t = 0; t < FE; ++t) {
+          const int e = i_raw + G * t;
+          if (e < E) sAB[cur ^ 1][grp][e] = an[t];
+        }
+      }
+      __syncthreads();
+      // element (i, l) from the lane that owns its lower-triangle twin
+#pragma unroll
+      for (int l = 0; l < n; ++l) p[l] = l <= i ? sX[grp][l][i] : sX[grp][i][l];
+      if (live) {
+        double* const dst = Pt + ((size_t)k * (n * n) + (size_t)(i * n)) * Bp + (unsigned)b;
+#pragma unroll
+        for (int l = 0; l < n; ++l) dst[(size_t)l * Bp] = p[l];
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+    if (live && i_raw == 0) fail[b] = failed;
+  }
+}
+
+template <class RS, int n, int m>
+__global__ __launch_bounds__(kBlock) void k_lqr_install(void* __restrict__ KD, const double* __restrict__ Kt, const double* __restrict__ Pt,
+                                                        const int* __restrict__ fail, const unsigned char* __restrict__ mask, int install,
+                                                        double* __restrict__ K, double* __restrict__ P, int* __restrict__ fail_out, int B,
+                                                        unsigned Bp, int N) {
+  using RR = Rec<RS, n, m>;
+  const int b = blockIdx.x * kBlock + threadIdx.x, k = blockIdx.y;
+  if (b >= B) return;
+  if (P) {
+    const double* const src = Pt + (size_t)k * (n * n) * Bp + (unsigned)b;
+    double* const dst = P + ((size_t)b * (size_t)(N + 1) + (size_t)k) * (n * n);
+#pragma unroll
+    for (int e = 0; e < n * n; ++e) dst[e] = src[(size_t)e * Bp];
+  }
+  if (k == N) {
+    if (fail_out) fail_out[b] = fail[b];
+    return;
+  }
+  double kk[m * n];
+  const double* const src = Kt + (size_t)k * (m * n) * Bp + (unsigned)b;
+#pragma unroll
+  for (int e = 0; e < m * n; ++e) kk[e] = src[(size_t)e * Bp];
+  if (K) {
+    double* const dst = K + ((size_t)b * (size_t)N + (size_t)k) * (m * n);
+#pragma unroll
+    for (int e = 0; e < m * n; ++e) dst[e] = kk[e];
+  }
+  if (install && fail[b] < 0 && (!mask || mask[b])) {
+    RS rec[RR::KP];
+#pragma unroll
+    for (int e = 0; e < RR::KP; ++e) rec[e] = e < m * n ? (RS)kk[e < m * n ? e : 0] : RS(0);
+    store_rec<RS, RR::KP>(RECP((RS*)KD, k, RR::KP), rec);
+  }
 }
 
 // -------------------------------------------------------------------------------------------------

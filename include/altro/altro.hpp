@@ -44,6 +44,7 @@
 #include "../altro_ensemble.h"
 #include "../altro_subset.h"
 #include "../altro_trigger.h"
+#include "../altro_lqr.h"
 
 namespace altro {
 
@@ -1610,6 +1611,22 @@ class AugmentedLagrangianiLQR {
     detail::Check(Handle(), altro_cov_inflate_circles(Handle(), index, base, rows, per_instance ? 1 : 0, kappa, rpos),
                   "altro_cov_inflate_circles");
   }
+  // Time-varying LQR tracking gains about the plan (include/altro_lqr.h), ON THE DEVICE: what a caller of the reference composes
+  // on the host from the knots' dynamics Jacobians, P_N = Qf, K_k = -(R + B^T P B)^-1 B^T P A, P_k = Q + A^T P A + (B^T P A)^T K_k.
+  // Q [n][n], R [m][m], Qf [n][n] (null: Q), lower triangles; K [B][N][m n] (column-major m x n, as GetFeedbackGain's),
+  // P [B][N+1][n][n], fail [B] (-1, or the knot at which the instance failed); each may be null.  `install`: the gains replace
+  // the solver's in the closed loop (TrackClosedLoop, PropagateCovariance, TrackEnsemble, the Run* loops) for every instance
+  // that did not fail.  A thin call giving the C call's bits.
+  void ComputeLqrGains(const double* Q, const double* R, const double* Qf, bool install, double* K, double* P = nullptr,
+                       int* fail = nullptr) {
+    ilqr_solver_.Push();
+    detail::Check(Handle(), altro_lqr_gains(Handle(), Q, R, Qf, install ? 1 : 0, K, P, fail), "altro_lqr_gains");
+  }
+  // ... as a policy: every Solve and every solve of a Run* loop ends with ComputeLqrGains(Q, R, Qf, true) for the instances it ran
+  void SetLqrGainPolicy(const double* Q, const double* R, const double* Qf = nullptr) {
+    detail::Check(Handle(), altro_lqr_set_policy(Handle(), Q, R, Qf), "altro_lqr_set_policy");
+  }
+  void ClearLqrGainPolicy() { detail::Check(Handle(), altro_lqr_set_policy(Handle(), nullptr, nullptr, nullptr), "altro_lqr_set_policy"); }
   // Monte-Carlo ensembles (include/altro_ensemble.h): `samples` closed-loop runs per instance under Gaussian initial errors
   // (Sigma0) and process noise (W, w_mode as PropagateCovariance) drawn ON THE DEVICE, reduced there to per-knot moments of
   // x_k - Xbar_k and violation counts: dev_mean [B][steps+1][n], dev_mom2 [B][steps+1][n][n] (what PropagateCovariance's Sigma
