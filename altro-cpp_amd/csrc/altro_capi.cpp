@@ -376,6 +376,41 @@ altro_status SolvedAfter(altro_handle h, altro_status st) {
   return GainsAfter(h, st);
 }
 
+// The refusals several entry points share, one text each: true, and the error text set, for an argument that is refused.
+bool StepsRefused(altro_handle h, int steps, const char* who) {
+  const int N = h->spec.desc.N;
+  if (steps >= 1 && steps <= N) return false;
+  h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
+  return true;
+}
+bool WModeRefused(altro_handle h, int w_mode, const char* who) {
+  if (w_mode >= 0 && w_mode <= (ALTRO_COV_W_PER_INSTANCE | ALTRO_COV_W_PER_KNOT)) return false;
+  h->err = std::string(who) + ": w_mode is a combination of ALTRO_COV_W_PER_INSTANCE and ALTRO_COV_W_PER_KNOT, got " + std::to_string(w_mode);
+  return true;
+}
+bool BoundsRefused(altro_handle h, const double* u_lo, const double* u_hi, const char* who) {
+  if ((u_lo == nullptr) == (u_hi == nullptr)) return false;
+  h->err = std::string(who) + ": u_lo and u_hi come together (both or neither)";
+  return true;
+}
+bool NegativeRefused(altro_handle h, double v, const std::string& what, const char* who) {
+  if (v >= 0.0 && v < std::numeric_limits<double>::infinity()) return false;  // (a NaN fails the first)
+  h->err = std::string(who) + ": " + what + " must be finite and not negative";
+  return true;
+}
+// `lookahead`: the trigger's wording, whose lookahead is what needs the gains
+bool GainsMissing(altro_handle h, const char* who, bool lookahead = false) {
+  if (h->has_gains) return false;
+  h->err = std::string(who) + (lookahead ? ": the lookahead needs gains, and " : ": ") + "no backward pass has produced " +
+           (lookahead ? "any" : "gains") + " on this handle yet (altro_solve_al, altro_solve_ilqr, altro_backward_pass)";
+  return true;
+}
+bool NotKnotConstraint(altro_handle h, int index, const char* who) {
+  if (index >= 0 && index < (int)h->spec.cons.size() && h->spec.cons[index].knot) return false;
+  h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
+  return true;
+}
+
 altro_status DefChanged(altro_handle h) {
   if (h->uploaded) {
     h->err = "the problem definition cannot change after the first compute call; create a new handle";
@@ -848,10 +883,7 @@ altro_status altro_add_knot_constraint(altro_handle h, int kind, int user_type, 
 namespace {
 // what both track setters refuse before any device work; the ConSpec of the constraint through *out
 altro_status TrackCheck(altro_handle h, int index, const void* P, int rows, const char* who, ConSpec** out) {
-  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
-    h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
-    return ALTRO_INVALID_ARG;
-  }
+  if (NotKnotConstraint(h, index, who)) return ALTRO_INVALID_ARG;
   if (!P || rows < 1) {
     h->err = std::string(who) + ": the track needs at least one row";
     return ALTRO_INVALID_ARG;
@@ -925,10 +957,7 @@ altro_status altro_get_track_offset(altro_handle h, int* offset) {
 altro_status altro_get_knot_params(altro_handle h, int index, double* out) {
   if (!h || !out) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
-    h->err = "altro_get_knot_params: constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
-    return ALTRO_INVALID_ARG;
-  }
+  if (NotKnotConstraint(h, index, "altro_get_knot_params")) return ALTRO_INVALID_ARG;
   return Forward(h, [&](EngineBase& e) { return e.GetKnotParams(index, out); });
 }
 altro_status altro_set_initial_state(altro_handle h, const double* x0, int per_instance) {
@@ -1262,24 +1291,13 @@ altro_status MpcTrackImpl(altro_handle h, int steps, int samples, const double* 
                           const double* u_hi, double* X_cl, double* U_cl, altro_track_stats* stats, int on_device, const char* who) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  const int N = h->spec.desc.N;
-  if (steps < 1 || steps > N) {
-    h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
-    return ALTRO_INVALID_ARG;
-  }
+  if (StepsRefused(h, steps, who)) return ALTRO_INVALID_ARG;
   if (samples < 1) {
     h->err = std::string(who) + ": at least one sample per instance, got " + std::to_string(samples);
     return ALTRO_INVALID_ARG;
   }
-  if ((u_lo == nullptr) != (u_hi == nullptr)) {
-    h->err = std::string(who) + ": u_lo and u_hi come together (both or neither)";
-    return ALTRO_INVALID_ARG;
-  }
-  if (!h->has_gains) {
-    h->err = std::string(who) + ": no backward pass has produced gains on this handle yet (altro_solve_al, altro_solve_ilqr, "
-             "altro_backward_pass)";
-    return ALTRO_NOT_READY;
-  }
+  if (BoundsRefused(h, u_lo, u_hi, who)) return ALTRO_INVALID_ARG;
+  if (GainsMissing(h, who)) return ALTRO_NOT_READY;
   TrackArgs g = TrackOpts(h);
   g.steps = steps;
   g.S = samples;
@@ -1406,10 +1424,7 @@ altro_status altro_mpc_run_tracked(altro_handle h, int cycles, int shift, const 
     h->err = "altro_mpc_run_tracked: at least one cycle";
     return ALTRO_INVALID_ARG;
   }
-  if ((u_lo == nullptr) != (u_hi == nullptr)) {
-    h->err = "altro_mpc_run_tracked: u_lo and u_hi come together (both or neither)";
-    return ALTRO_INVALID_ARG;
-  }
+  if (BoundsRefused(h, u_lo, u_hi, "altro_mpc_run_tracked")) return ALTRO_INVALID_ARG;
   LoopSpec spec = MakeLoopSpec(h, kLoopTracked, cycles, shift, w);
   spec.u_lo = u_lo;
   spec.u_hi = u_hi;
@@ -1538,10 +1553,7 @@ altro_status TeamCheck(altro_handle h, int agents, int index, const double* radi
              std::to_string(agents);
     return ALTRO_INVALID_ARG;
   }
-  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
-    h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
-    return ALTRO_INVALID_ARG;
-  }
+  if (NotKnotConstraint(h, index, who)) return ALTRO_INVALID_ARG;
   const ConSpec& c = h->spec.cons[index];
   if (c.kind != ALTRO_CON_CIRCLE || c.nparams != 3 * (agents - 1)) {
     h->err = std::string(who) + ": constraint " + std::to_string(index) + " must be an ALTRO_CON_CIRCLE with nparams = 3 (agents - 1) = " +
@@ -1555,10 +1567,7 @@ altro_status TeamCheck(altro_handle h, int agents, int index, const double* radi
   rad->resize((size_t)B);
   for (int b = 0; b < B; ++b) {
     const double r = radius[radius_per_instance ? b : b % agents];
-    if (!(r >= 0.0) || !(r < std::numeric_limits<double>::infinity())) {
-      h->err = std::string(who) + ": every radius must be finite and not negative";
-      return ALTRO_INVALID_ARG;
-    }
+    if (NegativeRefused(h, r, "every radius", who)) return ALTRO_INVALID_ARG;
     (*rad)[(size_t)b] = r;
   }
   return ALTRO_OK;
@@ -1754,10 +1763,7 @@ altro_status TriggerRuleCheck(altro_handle h, const altro_trigger_rule* rule, co
     h->err = w + ": ahead_tol must not be negative with a lookahead";
     return ALTRO_INVALID_ARG;
   }
-  if ((u_lo == nullptr) != (u_hi == nullptr)) {
-    h->err = w + ": u_lo and u_hi come together (both or neither)";
-    return ALTRO_INVALID_ARG;
-  }
+  if (BoundsRefused(h, u_lo, u_hi, who)) return ALTRO_INVALID_ARG;
   return ALTRO_OK;
 }
 // a handle that records the cost-to-go: masked solves refuse it (include/altro_subset.h), and so does everything built on them
@@ -1779,11 +1785,7 @@ altro_status MpcTriggerImpl(altro_handle h, const altro_trigger_rule* rule, cons
     return ALTRO_UNSUPPORTED;
   }
   if (TriggerCtgRefused(h, who) != ALTRO_OK) return ALTRO_UNSUPPORTED;
-  if (rule->lookahead > 0 && !h->has_gains) {
-    h->err = std::string(who) + ": the lookahead needs gains, and no backward pass has produced any on this handle yet "
-             "(altro_solve_al, altro_solve_ilqr, altro_backward_pass)";
-    return ALTRO_NOT_READY;
-  }
+  if (rule->lookahead > 0 && GainsMissing(h, who, true)) return ALTRO_NOT_READY;
   if (ReferenceMissing(h)) return ALTRO_NOT_READY;
   TriggerArgs g{};
   g.rule = RuleOf(*rule);
@@ -1855,28 +1857,17 @@ altro_status CovPropagateImpl(altro_handle h, int steps, const double* Sigma0, i
                               double* Sigma, double* sx, double* su, double* rpos, int on_device, const char* who) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  const int N = h->spec.desc.N;
-  if (steps < 1 || steps > N) {
-    h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
-    return ALTRO_INVALID_ARG;
-  }
+  if (StepsRefused(h, steps, who)) return ALTRO_INVALID_ARG;
   if (!Sigma && !sx && !su && !rpos) {
     h->err = std::string(who) + ": at least one of Sigma, sx, su and rpos is required";
     return ALTRO_INVALID_ARG;
   }
-  if (w_mode < 0 || w_mode > (ALTRO_COV_W_PER_INSTANCE | ALTRO_COV_W_PER_KNOT)) {
-    h->err = std::string(who) + ": w_mode is a combination of ALTRO_COV_W_PER_INSTANCE and ALTRO_COV_W_PER_KNOT, got " + std::to_string(w_mode);
-    return ALTRO_INVALID_ARG;
-  }
+  if (WModeRefused(h, w_mode, who)) return ALTRO_INVALID_ARG;
   if (rpos && h->spec.desc.n < 2) {
     h->err = std::string(who) + ": rpos is the spread of the position (x[0], x[1]) and needs at least two states";
     return ALTRO_INVALID_ARG;
   }
-  if (!h->has_gains) {
-    h->err = std::string(who) + ": no backward pass has produced gains on this handle yet (altro_solve_al, altro_solve_ilqr, "
-             "altro_backward_pass)";
-    return ALTRO_NOT_READY;
-  }
+  if (GainsMissing(h, who)) return ALTRO_NOT_READY;
   CovArgs g{};
   g.steps = steps;
   g.sigma0_per_instance = sigma0_per_instance ? 1 : 0;
@@ -1893,10 +1884,7 @@ altro_status CovInflateImpl(altro_handle h, int index, const double* base, int r
                             int on_device, const char* who) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  if (index < 0 || index >= (int)h->spec.cons.size() || !h->spec.cons[index].knot) {
-    h->err = std::string(who) + ": constraint " + std::to_string(index) + " is not a knot constraint (altro_add_knot_constraint)";
-    return ALTRO_INVALID_ARG;
-  }
+  if (NotKnotConstraint(h, index, who)) return ALTRO_INVALID_ARG;
   if (h->spec.cons[index].kind != ALTRO_CON_CIRCLE || h->spec.cons[index].nparams % 3 != 0) {
     h->err = std::string(who) + ": constraint " + std::to_string(index) + " must be an ALTRO_CON_CIRCLE";
     return ALTRO_INVALID_ARG;
@@ -1909,10 +1897,7 @@ altro_status CovInflateImpl(altro_handle h, int index, const double* base, int r
     h->err = std::string(who) + ": the base track needs at least one row, got " + std::to_string(rows);
     return ALTRO_INVALID_ARG;
   }
-  if (!(kappa >= 0.0) || !(kappa < std::numeric_limits<double>::infinity())) {  // (a NaN fails the first)
-    h->err = std::string(who) + ": kappa must be finite and not negative";
-    return ALTRO_INVALID_ARG;
-  }
+  if (NegativeRefused(h, kappa, "kappa", who)) return ALTRO_INVALID_ARG;
   return Forward(h, [&](EngineBase& e) { return e.CovInflate(index, base, rows, per_instance ? 1 : 0, kappa, rpos, on_device); });
 }
 
@@ -2046,19 +2031,12 @@ namespace {
 altro_status EnsCheck(altro_handle h, int steps, int samples, int w_mode, const char* who) {
   if (!h) return ALTRO_INVALID_ARG;
   if (Busy(h)) return ALTRO_NOT_READY;
-  const int N = h->spec.desc.N;
-  if (steps < 1 || steps > N) {
-    h->err = std::string(who) + ": steps must lie in [1, N] = [1, " + std::to_string(N) + "], got " + std::to_string(steps);
-    return ALTRO_INVALID_ARG;
-  }
+  if (StepsRefused(h, steps, who)) return ALTRO_INVALID_ARG;
   if (samples < 1) {
     h->err = std::string(who) + ": at least one sample per instance, got " + std::to_string(samples);
     return ALTRO_INVALID_ARG;
   }
-  if (w_mode < 0 || w_mode > (ALTRO_COV_W_PER_INSTANCE | ALTRO_COV_W_PER_KNOT)) {
-    h->err = std::string(who) + ": w_mode is a combination of ALTRO_COV_W_PER_INSTANCE and ALTRO_COV_W_PER_KNOT, got " + std::to_string(w_mode);
-    return ALTRO_INVALID_ARG;
-  }
+  if (WModeRefused(h, w_mode, who)) return ALTRO_INVALID_ARG;
   return ALTRO_OK;
 }
 altro_status EnsStates(altro_handle h, const char* who) {
@@ -2074,24 +2052,14 @@ altro_status MpcEnsembleImpl(altro_handle h, int steps, int samples, unsigned lo
                              altro_ensemble_stats* summary, altro_track_stats* stats, int on_device, const char* who) {
   altro_status st = EnsCheck(h, steps, samples, w_mode, who);
   if (st != ALTRO_OK) return st;
-  if ((u_lo == nullptr) != (u_hi == nullptr)) {
-    h->err = std::string(who) + ": u_lo and u_hi come together (both or neither)";
-    return ALTRO_INVALID_ARG;
-  }
-  if (!(viol_tol >= 0.0) || !(viol_tol < std::numeric_limits<double>::infinity())) {  // (a NaN fails the first)
-    h->err = std::string(who) + ": viol_tol must be finite and not negative";
-    return ALTRO_INVALID_ARG;
-  }
+  if (BoundsRefused(h, u_lo, u_hi, who)) return ALTRO_INVALID_ARG;
+  if (NegativeRefused(h, viol_tol, "viol_tol", who)) return ALTRO_INVALID_ARG;
   if (!dev_mean && !dev_mom2 && !alive && !viol_count && !summary && !stats) {
     h->err = std::string(who) + ": at least one of dev_mean, dev_mom2, alive, viol_count, summary and stats is required";
     return ALTRO_INVALID_ARG;
   }
   if ((st = EnsStates(h, who)) != ALTRO_OK) return st;
-  if (!h->has_gains) {
-    h->err = std::string(who) + ": no backward pass has produced gains on this handle yet (altro_solve_al, altro_solve_ilqr, "
-             "altro_backward_pass)";
-    return ALTRO_NOT_READY;
-  }
+  if (GainsMissing(h, who)) return ALTRO_NOT_READY;
   const TrackArgs t = TrackOpts(h);
   EnsembleArgs g{};
   g.steps = steps, g.S = samples, g.sigma0_per_instance = sigma0_per_instance ? 1 : 0, g.w_mode = w_mode;
@@ -2162,10 +2130,7 @@ altro_status altro_multistart_perturb_gaussian(altro_handle h, int starts, unsig
     return ALTRO_INVALID_ARG;
   }
   for (int i = 0; i < h->spec.desc.m; ++i)
-    if (!(sigma[i] >= 0.0) || !(sigma[i] < std::numeric_limits<double>::infinity())) {  // (a NaN fails the first)
-      h->err = std::string(who) + ": sigma[" + std::to_string(i) + "] must be finite and not negative";
-      return ALTRO_INVALID_ARG;
-    }
+    if (NegativeRefused(h, sigma[i], "sigma[" + std::to_string(i) + "]", who)) return ALTRO_INVALID_ARG;
   return Forward(h, [&](EngineBase& e) { return e.MsPerturbGaussian(starts, seed, instance_base, sigma, keep_first); });
 }
 

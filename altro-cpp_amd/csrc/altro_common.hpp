@@ -278,24 +278,37 @@ struct Parts {
   }
   size_t total() const { return off[K]; }
 };
+// doubles that hold `count` elements of V: how a layout counted in doubles sizes a part of ints, bytes or structs
+template <class V>
+constexpr size_t DoublesFor(size_t count) {
+  return (count * sizeof(V) + sizeof(double) - 1) / sizeof(double);
+}
 // the block Engine::MpcTrack stages for a host caller, in doubles: dx0 | w | u_lo, u_hi | X_cl | U_cl | stats.  L = B S lanes;
 // an array the caller leaves out takes no room.
 inline Parts<6> TrackStageParts(int n, int m, size_t L, size_t steps, bool dx0, bool w, bool bounds, bool X_cl, bool U_cl, bool stats) {
   static_assert(sizeof(TrackStats) % sizeof(double) == 0, "the statistics are staged in a block of doubles");
   return {dx0 ? L * n : 0,          w ? L * steps * n : 0,
           bounds ? 2 * (size_t)m : 0, X_cl ? L * (steps + 1) * n : 0,
-          U_cl ? L * steps * m : 0, stats ? L * (sizeof(TrackStats) / sizeof(double)) : 0};
+          U_cl ? L * steps * m : 0, stats ? DoublesFor<TrackStats>(L) : 0};
 }
 // the block of a tracked closed-loop run, in doubles: X log | U log | one cycle's X, U | its last state | its disturbance |
 // u_lo, u_hi | statistics [cycles][B]
 inline Parts<8> TrackedRunParts(int n, int m, size_t B, size_t cycles, size_t shift) {
   const size_t Lk = cycles * shift;
   return {B * (Lk + 1) * n, B * Lk * m, B * (shift + 1) * n, B * shift * m, B * n, B * shift * n, 2 * (size_t)m,
-          cycles * B * (sizeof(TrackStats) / sizeof(double))};
+          DoublesFor<TrackStats>(cycles * B)};
 }
 // the block of every other closed-loop run: X log | U log | w [cycles][B][n] | dU (`nd` doubles) | clearances (`nclear`)
 inline Parts<5> PlainRunParts(int n, int m, size_t B, size_t cycles, size_t shift, bool w, size_t nd, size_t nclear) {
   return {B * (cycles * shift + 1) * n, B * cycles * shift * m, w ? cycles * B * n : 0, nd, nclear};
+}
+// The int block of a closed-loop run, counted in INTS: iterations [B][cycles] | statuses | winners [B / G][cycles] (a multi-
+// start run: `winners` = B / G, else 0) | reason log [cycles][B] | ages [B] | reasons [B] | next mask (bytes [B], rounded up to
+// ints); the last four only for a triggered run.  Winners and reason log are parts of their own: no run has both, so the
+// block is as large as when the two shared one place.  (The tracked kinds record iterations and statuses [cycles][B].)
+inline Parts<7> RunIntParts(size_t B, size_t cycles, size_t winners, bool triggered) {
+  const size_t t = triggered ? 1 : 0;
+  return {B * cycles, B * cycles, winners * cycles, t * B * cycles, t * B, t * B, t * ((B + sizeof(int) - 1) / sizeof(int))};
 }
 // the blocks the other calls stage for a host caller, in doubles; an array the caller leaves out takes no room.
 // Engine::CovPropagate: Sigma0 | W | Sigma | sx | su | rpos
@@ -308,11 +321,11 @@ inline Parts<6> CovStageParts(int n, int m, size_t B, const CovArgs& c) {
           c.su ? B * st * m : 0,
           c.rpos ? B * (st + 1) : 0};
 }
-// Engine::MpcEnsemble: Sigma0 | W | u_lo, u_hi | dev_mean | dev_mom2 | alive | viol_count | summary | stats (ints two to a
-// double, rounded up).  Engine::NoiseFill: Sigma0 | W | dx0 | w
+// Engine::MpcEnsemble: Sigma0 | W | u_lo, u_hi | dev_mean | dev_mom2 | alive | viol_count | summary | stats (alive and
+// viol_count are ints [B][steps + 1]: DoublesFor<int>).  Engine::NoiseFill: Sigma0 | W | dx0 | w
 inline Parts<9> EnsembleStageParts(int n, int m, size_t B, const EnsembleArgs& c) {
   static_assert(sizeof(EnsembleStats) % sizeof(double) == 0, "the summaries are staged in a block of doubles");
-  const size_t st = (size_t)c.steps, nn = (size_t)n * n, ints = (B * (st + 1) + 1) / 2;
+  const size_t st = (size_t)c.steps, nn = (size_t)n * n, ints = DoublesFor<int>(B * (st + 1));
   return {c.Sigma0 ? (c.sigma0_per_instance ? B : 1) * nn : 0,
           c.W ? ((c.w_mode & 1) ? B : 1) * ((c.w_mode & 2) ? st : 1) * nn : 0,
           c.u_lo ? 2 * (size_t)m : 0,
@@ -320,8 +333,8 @@ inline Parts<9> EnsembleStageParts(int n, int m, size_t B, const EnsembleArgs& c
           c.dev_mom2 ? B * (st + 1) * nn : 0,
           c.alive ? ints : 0,
           c.viol_count ? ints : 0,
-          c.summary ? B * (sizeof(EnsembleStats) / sizeof(double)) : 0,
-          c.stats ? B * (size_t)c.S * (sizeof(TrackStats) / sizeof(double)) : 0};
+          c.summary ? DoublesFor<EnsembleStats>(B) : 0,
+          c.stats ? DoublesFor<TrackStats>(B * (size_t)c.S) : 0};
 }
 inline Parts<4> NoiseStageParts(int n, size_t B, const EnsembleArgs& c) {
   const size_t st = (size_t)c.steps, nn = (size_t)n * n, L = B * (size_t)c.S;
@@ -337,12 +350,17 @@ inline Parts<2> InflateStageParts(size_t cols, size_t rows, size_t np, size_t B,
 inline Parts<3> MsBestStageParts(int n, int m, size_t P, size_t N, bool X, bool U, size_t stats_doubles) {
   return {X ? P * (N + 1) * n : 0, U ? P * N * m : 0, P * stats_doubles};
 }
-// Engine::Trigger: tracked | age | u_lo, u_hi | mask | reason (a host caller's; ints and bytes packed into doubles) | the
-// lookahead's statistics [B] (every caller's: they live for the call)
+// Engine::Trigger: tracked [B] | age (ints [B]) | u_lo, u_hi | mask (bytes [B]) | reason (ints [B]), a host caller's | the
+// lookahead's statistics [B] (every caller's: scratch that lives for the call)
 inline Parts<6> TriggerStageParts(int m, size_t B, bool tracked, bool age, bool bounds, bool mask, bool reason, bool ahead) {
-  const size_t ts = sizeof(TrackStats) / sizeof(double), ints = (B + 1) / 2, bytes = (B + 7) / 8;
-  return {tracked ? B * ts : 0, age ? ints : 0, bounds ? 2 * (size_t)m : 0, mask ? bytes : 0, reason ? ints : 0, ahead ? B * ts : 0};
+  const size_t ts = DoublesFor<TrackStats>(B), ints = DoublesFor<int>(B), bytes = DoublesFor<unsigned char>(B);
+  return {tracked ? ts : 0, age ? ints : 0, bounds ? 2 * (size_t)m : 0, mask ? bytes : 0, reason ? ints : 0, ahead ? ts : 0};
 }
+// Engine::LqrGains: K [B][N][m][n] | P [B][N + 1][n][n] | fail (ints [B]);  Engine::SetSolveMask: the mask (bytes [B])
+inline Parts<3> LqrStageParts(int n, int m, size_t B, size_t N, bool K, bool P, bool fail) {
+  return {K ? B * N * m * n : 0, P ? B * (N + 1) * n * n : 0, fail ? DoublesFor<int>(B) : 0};
+}
+inline Parts<1> MaskStageParts(size_t B) { return {DoublesFor<unsigned char>(B)}; }
 inline Parts<1> PerturbStageParts(int m, size_t cols, size_t N) { return {cols * N * m}; }
 inline Parts<1> GaussStageParts(int m) { return {(size_t)m}; }  // Engine::MsPerturbGaussian: sigma [m]
 inline Parts<2> AdvanceStageParts(int n, size_t B, bool x0, bool w) { return {x0 ? B * n : 0, w ? B * n : 0}; }

@@ -1,4 +1,5 @@
-// altro_devmem.hpp — who owns the engine's device memory, and how a host caller's arrays get to the device and back.
+// altro_devmem.hpp — who owns the engine's device memory, and how a host caller's arrays (doubles, ints, bytes, statistics
+// structs: each copied with its own element count) get to the device and back.
 // Host code only: the HIP API header, the standard library and Parts (altro_common.hpp).  The one place of the solver library
 // that calls hipMalloc / hipFree / hipHostMalloc / hipHostFree: every block is held by an owner whose destructor frees it.
 // Whoever lets a block go while a copy on the engine's stream may still touch it waits for that stream first (Staged does).
@@ -77,9 +78,12 @@ class DevPool {
   std::vector<DevBlock<unsigned char>> blocks_;
 };
 
-// One host call's arrays in ONE device block carved by a Parts<K> layout.  in() enqueues the upload of a present input part
-// on the stream and out() books the download of a present output part; both hand back what the launch is given for that
-// part -- null for an array the caller left out.  After the caller's launches, finish() enqueues the booked downloads and
+// One host call's arrays in ONE device block carved by a Parts<K> layout.  The block and its parts are counted in doubles;
+// what a part holds may be doubles, ints, bytes or statistics structs (a layout sizes such a part with DoublesFor<V>), and
+// in() / out() copy the caller's elements to the byte, straight from and into the caller's arrays.  in() enqueues the upload
+// of a present input part on the stream and out() books the download of a present output part; both hand back what the
+// launch is given for that part -- null for an array the caller left out.  part() is for what no caller brings: scratch
+// that lives in the block for a direct caller too.  After the caller's launches, finish() enqueues the booked downloads and
 // ALWAYS waits for the stream, also after a failure (the block must not go under a copy in flight), and reports the first
 // error.  A Staged that goes without finish() while it has uploads on the stream waits for it too.
 // `direct`: the caller's arrays are device memory already; they are handed back as they came and nothing is copied.
@@ -91,23 +95,36 @@ class Staged {
   ~Staged() { (void)(!done_ && copies_ > 0 && hipStreamSynchronize(s_) != hipSuccess); }
   // part i on the device (a staged block only; null for a part that takes no room)
   double* part(int i) const { return p_.cnt[i] ? blk_ + p_.off[i] : nullptr; }
-  // input part i, or `count` doubles of it from element `first` on (two host arrays that share a part)
-  const double* in(int i, const double* host, size_t first = 0, size_t count = ~(size_t)0) {
+  // input part i: `count` elements of V from the host array, put at element `first` of the part (two host arrays that share
+  // a part: first, then count, as ever).  Exactly count * sizeof(V) bytes go up.  Null, and nothing copied, for a part that
+  // cannot hold them.
+  template <class V>
+  const V* in(int i, const V* host, size_t first, size_t count) {
     if (direct_ || !host) return host;
-    if (!p_.cnt[i]) return nullptr;
-    double* const dev = blk_ + p_.off[i] + first;
-    const size_t bytes = std::min(count, p_.cnt[i] - first) * sizeof(double);
-    if (e_ == hipSuccess) e_ = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s_), ++copies_;
+    if (!p_.cnt[i] || (first + count) * sizeof(V) > p_.cnt[i] * sizeof(double)) return nullptr;
+    V* const dev = reinterpret_cast<V*>(blk_ + p_.off[i]) + first;
+    if (e_ == hipSuccess) e_ = hipMemcpyAsync(dev, host, count * sizeof(V), hipMemcpyHostToDevice, s_), ++copies_;
     return dev;
   }
-  // output part i (V: double, or a struct that is a whole number of doubles)
+  // output part i: exactly `count` elements of V come back into the host array, never a byte past host + count
+  template <class V>
+  V* out(int i, V* host, size_t count) {
+    if (direct_ || !host) return host;
+    if (!p_.cnt[i] || count * sizeof(V) > p_.cnt[i] * sizeof(double)) return nullptr;
+    V* const dev = reinterpret_cast<V*>(blk_ + p_.off[i]);
+    down_[ndown_++] = Down{host, dev, count * sizeof(V)};
+    return dev;
+  }
+  // the whole part, for a V that fills it to the byte: double, or a struct that is a whole number of doubles
+  template <class V>
+  const V* in(int i, const V* host) {
+    static_assert(sizeof(V) % sizeof(double) == 0, "ints and bytes are staged with their count");
+    return in(i, host, 0, p_.cnt[i] * sizeof(double) / sizeof(V));
+  }
   template <class V>
   V* out(int i, V* host) {
-    if (direct_ || !host) return host;
-    if (!p_.cnt[i]) return nullptr;
-    V* const dev = reinterpret_cast<V*>(blk_ + p_.off[i]);
-    down_[ndown_++] = Down{host, dev, p_.cnt[i] * sizeof(double)};
-    return dev;
+    static_assert(sizeof(V) % sizeof(double) == 0, "ints and bytes are staged with their count");
+    return out(i, host, p_.cnt[i] * sizeof(double) / sizeof(V));
   }
   bool ok() const { return e_ == hipSuccess; }
   int copies() const { return copies_; }  // uploads enqueued so far (a caller that launches nothing need not wait without any)

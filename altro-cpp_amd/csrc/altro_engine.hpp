@@ -620,18 +620,16 @@ class Engine final : public EngineBase {
     const int cols = per_instance ? B_ : 1;
     const size_t need = (size_t)rows * cols * kRefPT;
     if (need > up_.refpath.count()) ALTRO_HIP_CHECK(up_.refpath.alloc(need));
-    const Parts<2> p = ReferenceStageParts(n, m, (size_t)rows * cols, Uref != nullptr);
-    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
-    Staged<2> sg(on_device != 0, hm_.stage.get(), p, stream_);
-    const double *Xd = sg.in(0, Xref), *Ud = sg.in(1, Uref);
+    StagedCall<2> c(this, ReferenceStageParts(n, m, (size_t)rows * cols, Uref != nullptr), on_device, "altro_set_reference", kEngineBlock);
+    ALTRO_TRY(c.Refused());
+    const double *Xd = c.sg.in(0, Xref), *Ud = c.sg.in(1, Uref);
     hipLaunchKernelGGL((k_ref_pack<n, m>), dim3((cols + kBlock - 1) / kBlock, rows), dim3(kBlock), 0, stream_, Xd, Ud, up_.refpath.get(), rows,
                        cols);
     up_.ref_rows = rows;
     up_.ref_cols = cols;
     up_.ref_offset = 0;
     LaunchRefTerms();
-    ALTRO_HIP_CHECK(sg.finish());
-    return ALTRO_OK;
+    return c.Finish();
   }
   altro_status SetReferenceOffset(int offset) override {
     if (offset < 0) {
@@ -804,11 +802,10 @@ class Engine final : public EngineBase {
     g.rows = pd_.total_rows;
     g.row_src = map;
     g.reset_pen = reset_pen;
-    const Parts<2> p = AdvanceStageParts(n, (size_t)B_, x0 != nullptr, w != nullptr);
-    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
-    Staged<2> sg(on_device != 0, hm_.stage.get(), p, stream_);
-    g.x0 = sg.in(0, x0);
-    g.w = sg.in(1, w);
+    StagedCall<2> c(this, AdvanceStageParts(n, (size_t)B_, x0 != nullptr, w != nullptr), on_device, "altro_mpc_advance", kEngineBlock);
+    ALTRO_TRY(c.Refused());
+    g.x0 = c.sg.in(0, x0);
+    g.w = c.sg.in(1, w);
     if (log) {
       g.Xlog = log->X;
       g.Ulog = log->U;
@@ -826,8 +823,7 @@ class Engine final : public EngineBase {
       up_.track_offset = (int)std::min<long long>((long long)up_.track_offset + shift, 0x7fffffffLL);
       LaunchKnotParams();
     }
-    ALTRO_HIP_CHECK(sg.finish());
-    return ALTRO_OK;
+    return c.Finish();
   }
   // ---- multi-start (include/altro_multistart.h) -----------------------------------------------------
   // G adjacent columns are the starts of one problem.  Everything runs on the engine's stream; the winners live in a device
@@ -903,12 +899,10 @@ class Engine final : public EngineBase {
       return ALTRO_INVALID_ARG;
     }
     ctg_replayable_ = false;
-    const Parts<1> p = PerturbStageParts(m, (size_t)(per_instance ? B_ : G), (size_t)N_);
-    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
-    Staged<1> sg(on_device != 0, hm_.stage.get(), p, stream_);
-    LaunchMsPerturb(G, sg.in(0, dU), per_instance);
-    ALTRO_HIP_CHECK(sg.finish());
-    return ALTRO_OK;
+    StagedCall<1> c(this, PerturbStageParts(m, (size_t)(per_instance ? B_ : G), (size_t)N_), on_device, "altro_multistart_perturb", kEngineBlock);
+    ALTRO_TRY(c.Refused());
+    LaunchMsPerturb(G, c.sg.in(0, dU), per_instance);
+    return c.Finish();
   }
   // U += sigma z with z drawn on the device (include/altro_ensemble.h): sigma [m] goes through the engine's staging block
   altro_status MsPerturbGaussian(int G, unsigned long long seed, unsigned long long instance_base, const double* sigma,
@@ -919,15 +913,13 @@ class Engine final : public EngineBase {
       return ALTRO_INVALID_ARG;
     }
     ctg_replayable_ = false;
-    const Parts<1> p = GaussStageParts(m);
-    ALTRO_TRY(EnsureStage(p.total()));
-    Staged<1> sg(false, hm_.stage.get(), p, stream_);
-    const double* sd = sg.in(0, sigma);
+    StagedCall<1> c(this, GaussStageParts(m), 0, "altro_multistart_perturb_gaussian", kEngineBlock);
+    ALTRO_TRY(c.Refused());
+    const double* sd = c.sg.in(0, sigma);
     const size_t total = (size_t)N_ * B_ * (R::mP / 2);
     hipLaunchKernelGGL(k_ms_perturb_gauss<T>, dim3((unsigned)((total + kMsThreads - 1) / kMsThreads)), dim3(kMsThreads), 0, stream_, A_, sd, G,
                        keep_first ? 1 : 0, seed, instance_base, m, R::mP);
-    ALTRO_HIP_CHECK(sg.finish());
-    return ALTRO_OK;
+    return c.Finish();
   }
   // The winners' trajectories through k_rec_to_rows with the winner as the source column, their statistics through k_ms_stats.
   // A host caller's arrays are staged in ONE device block (X | U | stats) and come back with one copy each.
@@ -935,12 +927,11 @@ class Engine final : public EngineBase {
     ALTRO_TRY(MsCheck(G));
     const int P = B_ / G;
     static_assert(sizeof(altro_stats) % sizeof(double) == 0, "altro_stats is a whole number of doubles");
-    const Parts<3> p = MsBestStageParts(n, m, (size_t)P, (size_t)N_, X != nullptr, U != nullptr,
-                                         stats ? sizeof(altro_stats) / sizeof(double) : 0);
-    if (!on_device) ALTRO_TRY(EnsureStage(p.total()));
-    Staged<3> sg(on_device != 0, hm_.stage.get(), p, stream_);
-    double *dX = sg.out(0, X), *dU = sg.out(1, U);
-    altro_stats* dS = sg.out(2, stats);
+    StagedCall<3> c(this, MsBestStageParts(n, m, (size_t)P, (size_t)N_, X != nullptr, U != nullptr, stats ? DoublesFor<altro_stats>(1) : 0),
+                    on_device, "altro_multistart_get_best", kEngineBlock);
+    ALTRO_TRY(c.Refused());
+    double *dX = c.sg.out(0, X), *dU = c.sg.out(1, U);
+    altro_stats* dS = c.sg.out(2, stats);
     int* win = MsWinDev(winner, on_device);
     LaunchMsSelect(G, ilqr_mode, win, nullptr, 0, 0);
     const dim3 gp((P + kBlock - 1) / kBlock);
@@ -951,7 +942,7 @@ class Engine final : public EngineBase {
       hipLaunchKernelGGL((k_rec_to_rows<T>), dim3(gp.x, N_), dim3(kBlock), 0, stream_, (const T*)A_.U, dU, N_, R::mP, 0, m, P, Bp_,
                          (const int*)win, G);
     if (stats) hipLaunchKernelGGL(k_ms_stats<T>, gp, dim3(kBlock), 0, stream_, A_, (const int*)win, G, P, ilqr_mode ? 1 : 0, dS);
-    ALTRO_HIP_CHECK(sg.finish());  // (the one wait that MsWinOut would start with)
+    ALTRO_TRY(c.Finish());  // (the one wait that MsWinOut would start with)
     if (winner && !on_device) ALTRO_HIP_CHECK(CopySync(winner, hm_.ms_win.get(), (size_t)P * sizeof(int), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   }
@@ -1082,19 +1073,14 @@ class Engine final : public EngineBase {
       ALTRO_TRY(CompactMask(mask, s, nullptr));
       return Sync();
     }
-    // a host mask: staged as the other host arrays are (the bytes packed into doubles), its counts known here
-    const Parts<1> p = {((size_t)B_ + sizeof(double) - 1) / sizeof(double)};
-    ALTRO_TRY(EnsureStage(p.total() + 1));
-    std::vector<double> packed(p.total(), 0.0);
-    std::memcpy(packed.data(), mask, (size_t)B_);
+    // a host mask: staged as the other host arrays are (k_mask_compact reads bytes 0 .. B - 1 and no further), its counts known here
     int known[kMaxSweepChains] = {};
     for (int c = 0; c < s.n; ++c)
       for (int b = s.lo[c]; b < s.hi[c]; ++b) known[c] += mask[b] != 0;
-    Staged<1> sg(false, hm_.stage.get(), p, stream_);
-    const unsigned char* src = reinterpret_cast<const unsigned char*>(sg.in(0, packed.data()));
-    const altro_status st = sg.ok() ? CompactMask(src, s, known) : ALTRO_OK;
-    ALTRO_HIP_CHECK(sg.finish(st == ALTRO_OK));
-    return st;
+    StagedCall<1> c(this, MaskStageParts((size_t)B_), 0, "altro_set_solve_mask", kEngineBlock);
+    ALTRO_TRY(c.Refused());
+    const unsigned char* src = c.sg.in(0, mask, 0, (size_t)B_);
+    return c.Finish(c.sg.ok() ? CompactMask(src, s, known) : ALTRO_OK);
   }
   altro_status GetSolveMask(unsigned char* mask, int* count) override {
     if (!mask_.on) {  // no mask: everyone
@@ -1195,13 +1181,9 @@ class Engine final : public EngineBase {
     if (!StepOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     // the staged block of a host caller (CovStageParts); it goes when this call returns, behind the wait of finish()
-    const Parts<6> p = CovStageParts(n, m, (size_t)B_, call);
-    DevBlock<double> stage;
-    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
-      err_ = "altro_cov_propagate: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
-      return ALTRO_HIP_ERROR;
-    }
-    Staged<6> sg(on_device != 0, stage.get(), p, stream_);
+    StagedCall<6> c(this, CovStageParts(n, m, (size_t)B_, call), on_device, "altro_cov_propagate", kCallBlock);
+    ALTRO_TRY(c.Refused());
+    Staged<6>& sg = c.sg;
     CovArgs g = call;
     g.Sigma0 = sg.in(0, call.Sigma0);
     g.W = sg.in(1, call.W);
@@ -1209,11 +1191,7 @@ class Engine final : public EngineBase {
     g.sx = sg.out(3, call.sx);
     g.su = sg.out(4, call.su);
     g.rpos = sg.out(5, call.rpos);
-    const altro_status s = sg.ok() ? LaunchCov(g) : ALTRO_OK;
-    const hipError_t e = sg.finish(s == ALTRO_OK);
-    ALTRO_TRY(s);
-    ALTRO_HIP_CHECK(e);
-    return ALTRO_OK;
+    return c.Finish(sg.ok() ? LaunchCov(g) : ALTRO_OK);
   }
   // the spare buffer a kernel has just been launched to write becomes the constraint's track, one column per instance
   void AdoptSpare(KnotCon* c, int rows, int base, bool team) {
@@ -1233,15 +1211,11 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     ALTRO_TRY(Sync());
     const size_t need = (size_t)B_ * rows * c->np;
-    const Parts<2> p = InflateStageParts((size_t)(per_instance ? B_ : 1), (size_t)rows, (size_t)c->np, (size_t)B_, (size_t)N_ + 1);
-    DevBlock<double> stage;  // (goes behind the wait of `sg`)
-    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
-      err_ = "altro_cov_inflate_circles: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
-      return ALTRO_HIP_ERROR;
-    }
-    Staged<2> sg(on_device != 0, stage.get(), p, stream_);
-    base = sg.in(0, base);
-    rpos = sg.in(1, rpos);
+    StagedCall<2> sc(this, InflateStageParts((size_t)(per_instance ? B_ : 1), (size_t)rows, (size_t)c->np, (size_t)B_, (size_t)N_ + 1),
+                     on_device, "altro_cov_inflate_circles", kCallBlock);
+    ALTRO_TRY(sc.Refused());
+    base = sc.sg.in(0, base);
+    rpos = sc.sg.in(1, rpos);
     if (need > c->spare.count()) ALTRO_HIP_CHECK(c->spare.alloc(need));
     ctg_replayable_ = false;  // (as SetConstraintTrack)
     const int nobs = c->np / 3;
@@ -1249,8 +1223,7 @@ class Engine final : public EngineBase {
     hipLaunchKernelGGL((k_cov_inflate<0>), dim3((unsigned)((total + kTeamThreads - 1) / kTeamThreads)), dim3(kTeamThreads), 0, stream_,
                        c->spare.get(), base, rpos, B_, rows, nobs, per_instance ? B_ : 1, up_.track_offset, N_, kappa);
     AdoptSpare(c, rows, 0, false);
-    ALTRO_HIP_CHECK(sg.finish());
-    return ALTRO_OK;
+    return sc.Finish();
   }
 
   // ---- time-varying LQR tracking gains (include/altro_lqr.h) -----------------------------------------
@@ -1304,25 +1277,13 @@ class Engine final : public EngineBase {
       Q = hq.data(), Rw = hr.data(), Qf = call.Qf ? hf.data() : nullptr;
     }
     if (!LqrPackWeights(n, m, Q, Rw, Qf, &lqr_w_, &err_, who)) return ALTRO_INVALID_ARG;
-    // the staged block of a host caller: K | P | fail (ints two to a double; they reach the caller through `hfail`)
-    const size_t B = (size_t)B_;
-    const Parts<3> p{call.K ? B * N_ * m * n : 0, call.P ? B * (N_ + 1) * n * n : 0, call.fail ? (B + 1) / 2 : 0};
-    DevBlock<double> stage;
-    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
-      err_ = std::string(who) + ": out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
-      return ALTRO_HIP_ERROR;
-    }
-    Staged<3> sg(on_device != 0, stage.get(), p, stream_);
-    std::vector<double> hfail(on_device ? 0 : p.cnt[2]);
-    double* const K = sg.out(0, call.K);
-    double* const P = sg.out(1, call.P);
-    int* const fail = on_device ? call.fail : reinterpret_cast<int*>(sg.out(2, p.cnt[2] ? hfail.data() : nullptr));
-    const altro_status s = LaunchLqr(lqr_w_, call.install, nullptr, K, P, fail);
-    const hipError_t e = sg.finish(s == ALTRO_OK);
-    ALTRO_TRY(s);
-    ALTRO_HIP_CHECK(e);
-    if (!on_device && call.fail) std::memcpy(call.fail, hfail.data(), B * sizeof(int));
-    return ALTRO_OK;
+    // the staged block of a host caller (LqrStageParts)
+    StagedCall<3> c(this, LqrStageParts(n, m, (size_t)B_, (size_t)N_, call.K, call.P, call.fail), on_device, who, kCallBlock);
+    ALTRO_TRY(c.Refused());
+    double* const K = c.sg.out(0, call.K);
+    double* const P = c.sg.out(1, call.P);
+    int* const fail = c.sg.out(2, call.fail, (size_t)B_);
+    return c.Finish(LaunchLqr(lqr_w_, call.install, nullptr, K, P, fail));
   }
   void LqrSetPolicy(const std::vector<double>& packed) override { lqr_policy_ = packed; }
 
@@ -1337,14 +1298,10 @@ class Engine final : public EngineBase {
     if (!StepOk() || !RefOk()) return ALTRO_NOT_READY;
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     // the staged block of a host caller (TrackStageParts); it goes when this call returns, behind the wait of finish()
-    const Parts<6> p = TrackStageParts(n, m, (size_t)B_ * (size_t)call.S, (size_t)call.steps, call.dx0, call.w, call.u_lo, call.X_cl,
-                                       call.U_cl, call.stats);
-    DevBlock<double> stage;
-    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
-      err_ = "altro_mpc_track: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged inputs and logs";
-      return ALTRO_HIP_ERROR;
-    }
-    Staged<6> sg(on_device != 0, stage.get(), p, stream_);
+    StagedCall<6> c(this, TrackStageParts(n, m, (size_t)B_ * (size_t)call.S, (size_t)call.steps, call.dx0, call.w, call.u_lo, call.X_cl,
+                                          call.U_cl, call.stats), on_device, "altro_mpc_track", kCallBlock);
+    ALTRO_TRY(c.Refused());
+    Staged<6>& sg = c.sg;
     TrackArgs g = call;
     g.dx0 = sg.in(0, call.dx0);
     g.w = sg.in(1, call.w);
@@ -1354,11 +1311,7 @@ class Engine final : public EngineBase {
     g.U_cl = sg.out(4, call.U_cl);
     g.stats = sg.out(5, call.stats);
     if (!on_device) g.x_end = nullptr;  // (a device caller's only: what altro_mpc_run_tracked advances from)
-    const altro_status st = sg.ok() ? LaunchTrack(g) : ALTRO_OK;
-    const hipError_t e = sg.finish(st == ALTRO_OK);
-    ALTRO_TRY(st);
-    ALTRO_HIP_CHECK(e);
-    return ALTRO_OK;
+    return c.Finish(sg.ok() ? LaunchTrack(g) : ALTRO_OK);
   }
 
   // ---- Monte-Carlo ensembles (include/altro_ensemble.h) --------------------------------------------
@@ -1435,18 +1388,17 @@ class Engine final : public EngineBase {
       return ALTRO_INVALID_ARG;
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    const Parts<9> p = EnsembleStageParts(n, m, (size_t)B_, call);
     const size_t K1 = (size_t)call.steps + 1, waves = (size_t)B_ * slabs, V = (size_t)EnsembleValues(n);
-    DevBlock<double> stage, fac, part;
+    DevBlock<double> fac, part;
     DevBlock<int> word, cnt;
     DevBlock<EnsSlabSum> sums;
-    if ((!on_device && stage.alloc(p.total()) != hipSuccess) || part.alloc(waves * K1 * V) != hipSuccess ||
-        cnt.alloc(waves * K1 * 2) != hipSuccess || sums.alloc(waves) != hipSuccess) {
-      err_ = std::string(who) + ": out of device memory for " + std::to_string((p.total() + waves * K1 * (V + 1)) * sizeof(double)) +
-             " bytes of staged arrays and partial sums";
+    if (part.alloc(waves * K1 * V) != hipSuccess || cnt.alloc(waves * K1 * 2) != hipSuccess || sums.alloc(waves) != hipSuccess) {
+      err_ = std::string(who) + ": out of device memory for " + std::to_string(waves * K1 * (V + 1) * sizeof(double)) + " bytes of partial sums";
       return ALTRO_HIP_ERROR;
     }
-    Staged<9> sg(on_device != 0, stage.get(), p, stream_);
+    StagedCall<9> c(this, EnsembleStageParts(n, m, (size_t)B_, call), on_device, who, kCallBlock);
+    ALTRO_TRY(c.Refused());
+    Staged<9>& sg = c.sg;
     EnsLaunch q{};
     q.g = call;
     q.g.Sigma0 = sg.in(0, call.Sigma0);
@@ -1456,13 +1408,11 @@ class Engine final : public EngineBase {
     EnsFinishArgs f{};
     f.dev_mean = sg.out(3, call.dev_mean);
     f.dev_mom2 = sg.out(4, call.dev_mom2);
-    // (the int arrays are an odd number of words when B (steps + 1) is odd: their downloads are this call's, to the word)
-    f.alive = on_device || !call.alive ? call.alive : reinterpret_cast<int*>(sg.part(5));
-    f.viol_count = on_device || !call.viol_count ? call.viol_count : reinterpret_cast<int*>(sg.part(6));
+    f.alive = sg.out(5, call.alive, (size_t)B_ * K1);
+    f.viol_count = sg.out(6, call.viol_count, (size_t)B_ * K1);
     f.summary = sg.out(7, call.summary);
     q.g.stats = sg.out(8, call.stats);
-    altro_status st = sg.ok() ? EnsFactors(who, q.g, &fac, &word, &q.L0, &q.Lw) : ALTRO_OK;
-    hipError_t ec = hipSuccess;
+    const altro_status st = sg.ok() ? EnsFactors(who, q.g, &fac, &word, &q.L0, &q.Lw) : ALTRO_OK;
     if (st == ALTRO_OK && sg.ok()) {
       q.part = part.get(), q.cnt = cnt.get(), q.sums = sums.get();
       q.slabs = slabs, q.per_slab = EnsembleChunksPerSlab(B_, call.S);
@@ -1474,16 +1424,8 @@ class Engine final : public EngineBase {
       f.B = B_, f.steps = call.steps, f.slabs = slabs, f.n = n, f.S = call.S;
       const size_t total = (size_t)B_ * K1 * V;
       hipLaunchKernelGGL((k_ens_finish<0>), dim3((unsigned)((total + kEnsThreads - 1) / kEnsThreads)), dim3(kEnsThreads), 0, stream_, f);
-      ec = hipGetLastError();
-      const size_t ib = (size_t)B_ * K1 * sizeof(int);
-      if (!on_device && call.alive && ec == hipSuccess) ec = hipMemcpyAsync(call.alive, f.alive, ib, hipMemcpyDeviceToHost, stream_);
-      if (!on_device && call.viol_count && ec == hipSuccess) ec = hipMemcpyAsync(call.viol_count, f.viol_count, ib, hipMemcpyDeviceToHost, stream_);
     }
-    const hipError_t e = sg.finish(st == ALTRO_OK);
-    ALTRO_TRY(st);
-    ALTRO_HIP_CHECK(ec);
-    ALTRO_HIP_CHECK(e);
-    return ALTRO_OK;
+    return c.Finish(st);
   }
   altro_status NoiseFill(const EnsembleArgs& call, int on_device) override {
     const char* who = "altro_noise_fill";
@@ -1502,14 +1444,11 @@ class Engine final : public EngineBase {
       return ALTRO_INVALID_ARG;
     }
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
-    const Parts<4> p = NoiseStageParts(n, (size_t)B_, call);
-    DevBlock<double> stage, fac;
+    DevBlock<double> fac;  // (the factors outlive the frame's wait: declared ahead of it)
     DevBlock<int> word;
-    if (!on_device && stage.alloc(p.total()) != hipSuccess) {
-      err_ = std::string(who) + ": out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
-      return ALTRO_HIP_ERROR;
-    }
-    Staged<4> sg(on_device != 0, stage.get(), p, stream_);
+    StagedCall<4> c(this, NoiseStageParts(n, (size_t)B_, call), on_device, who, kCallBlock);
+    ALTRO_TRY(c.Refused());
+    Staged<4>& sg = c.sg;
     EnsembleArgs g = call;
     g.Sigma0 = sg.in(0, call.Sigma0);
     g.W = sg.in(1, call.W);
@@ -1518,10 +1457,7 @@ class Engine final : public EngineBase {
     const double *L0 = nullptr, *Lw = nullptr;
     const altro_status st = sg.ok() ? EnsFactors(who, g, &fac, &word, &L0, &Lw) : ALTRO_OK;
     if (st == ALTRO_OK && sg.ok()) hipLaunchKernelGGL((k_noise_fill<n>), dim3((unsigned)blocks), dim3(kBlock), 0, stream_, g, L0, Lw, B_);
-    const hipError_t e = sg.finish(st == ALTRO_OK);
-    ALTRO_TRY(st);
-    ALTRO_HIP_CHECK(e);
-    return ALTRO_OK;
+    return c.Finish(st);
   }
 
   // ---- event-triggered re-planning (include/altro_trigger.h) ----------------------------------------
@@ -1558,9 +1494,8 @@ class Engine final : public EngineBase {
                        (const int*)(ilqr_mode ? A_.status : A_.status_al), (const TrackStats*)(look ? ahead : nullptr), g.mask, g.reason, B_);
     return ALTRO_OK;
   }
-  // Host arrays are staged through ONE device block that lives for the call (ints and bytes packed into doubles on the
-  // host, as SetSolveMask packs its bytes); device arrays are used where they are.  The lookahead's statistics live in
-  // that block for either caller.  No flag of the engine changes.
+  // Host arrays are staged through ONE device block that lives for the call (TriggerStageParts); device arrays are used where
+  // they are.  The lookahead's statistics live in that block for either caller.  No flag of the engine changes.
   altro_status Trigger(const TriggerArgs& call, int on_device, bool ilqr_mode) override {
     const TriggerRule& r = call.rule;
     if (r.max_age < 1 || r.lookahead < 0 || r.lookahead > N_ || (call.u_lo == nullptr) != (call.u_hi == nullptr)) {
@@ -1572,32 +1507,18 @@ class Engine final : public EngineBase {
     ALTRO_HIP_CHECK(hipSetDevice(desc_.device_id));
     const bool host = !on_device;
     const size_t B = (size_t)B_;
-    const Parts<6> p = TriggerStageParts(m, B, host && call.tracked, host && call.age, host && call.u_lo, host && call.mask,
-                                         host && call.reason, r.lookahead > 0);
-    DevBlock<double> stage;
-    if (p.total() > 0 && stage.alloc(p.total()) != hipSuccess) {
-      err_ = "altro_mpc_trigger: out of device memory for " + std::to_string(p.total() * sizeof(double)) + " bytes of staged arrays";
-      return ALTRO_HIP_ERROR;
-    }
-    std::vector<double> age_h(p.cnt[1], 0.0), mask_h(p.cnt[3], 0.0), why_h(p.cnt[4], 0.0);
-    if (p.cnt[1]) std::memcpy(age_h.data(), call.age, B * sizeof(int));
-    Staged<6> sg(on_device != 0, stage.get(), p, stream_);
+    StagedCall<6> c(this, TriggerStageParts(m, B, host && call.tracked, host && call.age, host && call.u_lo, host && call.mask,
+                                            host && call.reason, r.lookahead > 0), on_device, "altro_mpc_trigger", kCallBlock, true);
+    ALTRO_TRY(c.Refused());
+    Staged<6>& sg = c.sg;
     TriggerArgs g = call;
-    if (host) {
-      g.tracked = reinterpret_cast<const TrackStats*>(sg.in(0, reinterpret_cast<const double*>(call.tracked)));
-      g.age = reinterpret_cast<const int*>(sg.in(1, p.cnt[1] ? age_h.data() : nullptr));
-      g.u_lo = sg.in(2, call.u_lo, 0, m);
-      g.u_hi = sg.in(2, call.u_hi, m, m);
-      g.mask = reinterpret_cast<unsigned char*>(sg.out(3, p.cnt[3] ? mask_h.data() : nullptr));
-      g.reason = reinterpret_cast<int*>(sg.out(4, p.cnt[4] ? why_h.data() : nullptr));
-    }
-    const altro_status st = sg.ok() ? LaunchTrigger(g, reinterpret_cast<TrackStats*>(sg.part(5)), ilqr_mode) : ALTRO_OK;
-    const hipError_t e = sg.finish(st == ALTRO_OK);
-    ALTRO_TRY(st);
-    ALTRO_HIP_CHECK(e);
-    if (p.cnt[3]) std::memcpy(call.mask, mask_h.data(), B);
-    if (p.cnt[4]) std::memcpy(call.reason, why_h.data(), B * sizeof(int));
-    return ALTRO_OK;
+    g.tracked = sg.in(0, call.tracked);
+    g.age = sg.in(1, call.age, 0, B);
+    g.u_lo = sg.in(2, call.u_lo, 0, m);
+    g.u_hi = sg.in(2, call.u_hi, m, m);
+    g.mask = sg.out(3, call.mask, B);
+    g.reason = sg.out(4, call.reason, B);
+    return c.Finish(sg.ok() ? LaunchTrigger(g, reinterpret_cast<TrackStats*>(sg.part(5)), ilqr_mode) : ALTRO_OK);
   }
 
   // ---- one closed-loop run (LoopSpec, altro_common.hpp) ----------------------------------------------
@@ -1652,14 +1573,20 @@ class Engine final : public EngineBase {
     const Parts<8> pt = TrackedRunParts(n, m, B, cycles, (size_t)s.shift);
     const Parts<5> pp = PlainRunParts(n, m, B, cycles, (size_t)s.shift, s.w && (ms || team),
                                       ms && s.dU ? (size_t)(s.dU_per_instance ? B_ : s.G) * N_ * m : 0, team ? (size_t)(B_ / s.A) * cycles : 0);
-    if (r.i.alloc(2 * B * cycles + (ms ? (size_t)(B_ / s.G) * cycles : 0) + (trig ? B * cycles + 2 * B + (B + 3) / 4 : 0)) != hipSuccess ||
+    const Parts<7> pi = RunIntParts(B, cycles, ms ? (size_t)(B_ / s.G) : 0, trig);
+    if (r.i.alloc(pi.total()) != hipSuccess ||
         r.d.alloc(tracked ? pt.total() : pp.total()) != hipSuccess ||
-        (trig && s.rule.lookahead > 0 && r.ahead.alloc(B * (sizeof(TrackStats) / sizeof(double))) != hipSuccess)) {
+        (trig && s.rule.lookahead > 0 && r.ahead.alloc(DoublesFor<TrackStats>(B)) != hipSuccess)) {
       err_ = "closed-loop run: out of device memory for the logs";
       return ALTRO_HIP_ERROR;
     }
+    // iterations | statuses | winners | reason log | ages | reasons | next mask (a part the run's kind lacks has no room)
     r.it = r.i.get();
-    r.win = r.it + 2 * B * cycles;
+    r.win = r.it + pi.off[2];
+    r.why_log = r.it + pi.off[3];
+    r.age = r.it + pi.off[4];
+    r.why = r.it + pi.off[5];
+    r.next_mask = reinterpret_cast<unsigned char*>(r.it + pi.off[6]);
     // the run's host inputs go up with the block carved (one wait for all of them, none without any; a block that goes on
     // a failure has no copy in flight)
     if (tracked) {
@@ -1685,10 +1612,6 @@ class Engine final : public EngineBase {
     }
     if (trig) {
       // cycle 0: everyone, reason kTrigFirst, age 0; the counts per slice are the slices' sizes
-      r.why_log = r.it + 2 * B * cycles;
-      r.age = r.why_log + B * cycles;
-      r.why = r.age + B;
-      r.next_mask = reinterpret_cast<unsigned char*>(r.why + B);
       ALTRO_TRY(MaskBlocks());
       ALTRO_HIP_CHECK(hipMemsetAsync(r.age, 0, B * sizeof(int), stream_));
       ALTRO_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.why), kTrigFirst, B, stream_));
@@ -1815,33 +1738,33 @@ class Engine final : public EngineBase {
         down(o.iterations, r.it, cb * sizeof(int));
         down(o.status, r.it + cb, cb * sizeof(int));
       } else {  // recorded [cycles][B], handed out [B][cycles]
-        if (o.iterations || o.status) {
+        if (o.iterations || o.status) {  // (neighbours in the block: one copy for the two)
           std::vector<int> h(2 * cb);
           down(h.data(), r.it, h.size() * sizeof(int));
-          for (size_t c = 0; c < cycles && e == hipSuccess; ++c)
-            for (size_t b = 0; b < B; ++b) {
-              if (o.iterations) o.iterations[b * cycles + c] = h[c * B + b];
-              if (o.status) o.status[b * cycles + c] = h[cb + c * B + b];
-            }
+          if (e == hipSuccess) CyclesToColumns(h.data(), o.iterations, B, cycles), CyclesToColumns(h.data() + cb, o.status, B, cycles);
         }
-        if (o.reason && s.kind == kLoopTriggered) {
-          std::vector<int> h(cb);
-          down(h.data(), r.why_log, h.size() * sizeof(int));
-          for (size_t c = 0; c < cycles && e == hipSuccess; ++c)
-            for (size_t b = 0; b < B; ++b) o.reason[b * cycles + c] = h[c * B + b];
-        }
-        if (o.track) {
-          std::vector<TrackStats> h(cb);
-          down(h.data(), r.stats, h.size() * sizeof(TrackStats));
-          for (size_t c = 0; c < cycles && e == hipSuccess; ++c)
-            for (size_t b = 0; b < B; ++b) o.track[b * cycles + c] = h[c * B + b];
-        }
+        if (s.kind == kLoopTriggered) DownCycleMajor(r.why_log, o.reason, B, cycles, &e);
+        DownCycleMajor(r.stats, o.track, B, cycles, &e);
       }
       if (s.kind == kLoopMultiStart) down(o.winner, r.win, (size_t)(B_ / s.G) * cycles * sizeof(int));
       if (s.kind == kLoopTeam) down(o.clear, r.clear, (size_t)(B_ / s.A) * cycles * sizeof(double));
     }
     ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
+  }
+  // a log recorded [cycles][B] on the host -> the caller's [B][cycles] (null: not asked for)
+  template <class V>
+  static void CyclesToColumns(const V* rows, V* out, size_t B, size_t cycles) {
+    for (size_t c = 0; out && c < cycles; ++c)
+      for (size_t b = 0; b < B; ++b) out[b * cycles + c] = rows[c * B + b];
+  }
+  // ... and the same from the device: one copy and its wait, unless an earlier copy failed (*e) or the log is not asked for
+  template <class V>
+  void DownCycleMajor(const V* dev, V* out, size_t B, size_t cycles, hipError_t* e) {
+    if (!out || *e != hipSuccess) return;
+    std::vector<V> h(B * cycles);
+    *e = CopySync(h.data(), dev, h.size() * sizeof(V), hipMemcpyDeviceToHost);
+    if (*e == hipSuccess) CyclesToColumns(h.data(), out, B, cycles);
   }
   altro_status GetInitialState(double* x0) override { return DownloadRec(A_.x0, 1, R::nP, 0, n, x0); }
   altro_status SetPenalties(const double* rho) override { return UploadRows(A_.pen, rho); }
@@ -2079,6 +2002,46 @@ class Engine final : public EngineBase {
   // Staging buffer of the host boundary: the caller's row layout on the device (see k_rec_to_rows / k_rows_to_rec).
   altro_status EnsureStage(size_t doubles) {
     if (doubles > hm_.stage.count()) ALTRO_HIP_CHECK(hm_.stage.alloc(doubles));
+    return ALTRO_OK;
+  }
+  // The frame of one staged call (Staged, altro_devmem.hpp): the block of the layout `p`, then `sg`, then Finish().  The block
+  // is the call's own (kCallBlock: it goes with the frame, behind the wait of Finish) or the engine's staging block, grown to
+  // fit (kEngineBlock).  A device caller (`on_device`) has no block unless the layout holds scratch parts (`scratch`), which
+  // every caller needs.  Refused() is to be asked before `sg` is used: the block could not be had, and the text is set.
+  enum StageBlock { kCallBlock, kEngineBlock };
+  template <int K>
+  class StagedCall {
+   public:
+    StagedCall(Engine* e, const Parts<K>& p, int on_device, const char* who, StageBlock which, bool scratch = false)
+        : e_(e),
+          st_(Block(p.total(), !on_device || scratch, who, which == kCallBlock)),
+          sg(on_device != 0, which == kCallBlock ? own_.get() : e->hm_.stage.get(), p, e->stream_) {}
+    altro_status Refused() const { return st_; }
+    // the tail of every staged call, behind its launches (`launched`: their status; a refused launch leaves nothing to
+    // download): the downloads, the one wait -- also after a failure -- and the first error
+    altro_status Finish(altro_status launched = ALTRO_OK) {
+      const hipError_t e = sg.finish(launched == ALTRO_OK);
+      if (launched != ALTRO_OK) return launched;
+      return e_->HipStatus(e);
+    }
+
+   private:
+    altro_status Block(size_t doubles, bool needed, const char* who, bool own) {
+      if (!needed || doubles == 0) return ALTRO_OK;
+      if (!own) return e_->EnsureStage(doubles);
+      if (own_.alloc(doubles) == hipSuccess) return ALTRO_OK;
+      e_->err_ = std::string(who) + ": out of device memory for " + std::to_string(doubles * sizeof(double)) + " bytes of staged arrays";
+      return ALTRO_HIP_ERROR;
+    }
+    Engine* const e_;
+    DevBlock<double> own_;
+    const altro_status st_;
+
+   public:
+    Staged<K> sg;
+  };
+  altro_status HipStatus(hipError_t e) {
+    ALTRO_HIP_CHECK(e);
     return ALTRO_OK;
   }
   // device records [knots][Bp][EP] (fields at off..off+E) -> host [B][knots][E]: converted on the device, one contiguous

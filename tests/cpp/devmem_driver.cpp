@@ -142,10 +142,39 @@ static void UploadOwner() {
 }
 
 // ---- the staging helper --------------------------------------------------------------------------------------------
-// One round trip through a layout.  ins / outs / halves: bit i set = part i is an input / an output / an input that two host
-// arrays share half and half (u_lo, u_hi).  present: bit i set = the caller brings that array.
+// What one part holds: elements of `size` bytes, `count` of them (size 0: doubles, as many as the part has).  The host
+// array of a part is a malloc of exactly count * size bytes, so a copy that is one byte too long in either direction is an
+// out-of-bounds access for the sanitizer build.
+struct Elem {
+  size_t size, count;
+};
+static unsigned char Pattern(int part, size_t j, int salt) { return (unsigned char)(salt + 31 * (part + 1) + 7 * j); }
 template <int K>
-static void RoundTrip(const char* name, const Parts<K>& p, unsigned ins, unsigned outs, unsigned halves, unsigned present, const char* tail) {
+static const void* In(Staged<K>& sg, int i, const void* host, Elem e, size_t count, size_t first, bool whole) {
+  switch (e.size) {
+    case sizeof(unsigned char): return sg.in(i, (const unsigned char*)host, first, count);
+    case sizeof(int): return sg.in(i, (const int*)host, first, count);
+    case sizeof(TrackStats): return sg.in(i, (const TrackStats*)host);
+    default: return whole ? sg.in(i, (const double*)host) : sg.in(i, (const double*)host, first, count);
+  }
+}
+template <int K>
+static void* Out(Staged<K>& sg, int i, void* host, Elem e) {
+  switch (e.size) {
+    case sizeof(unsigned char): return sg.out(i, (unsigned char*)host, e.count);
+    case sizeof(int): return sg.out(i, (int*)host, e.count);
+    case sizeof(TrackStats): return sg.out(i, (TrackStats*)host);
+    case sizeof(EnsembleStats): return sg.out(i, (EnsembleStats*)host);
+    default: return sg.out(i, (double*)host);
+  }
+}
+// One round trip through a layout.  ins / outs / halves: bit i set = part i is an input / an output / an input that two host
+// arrays share half and half (u_lo, u_hi).  present: bit i set = the caller brings that array.  elems: what the parts hold
+// (null: doubles throughout).
+template <int K>
+static void RoundTrip(const char* name, const Parts<K>& p, unsigned ins, unsigned outs, unsigned halves, unsigned present, const char* tail,
+                      const Elem* elems = nullptr) {
+  static_assert(sizeof(TrackStats) != sizeof(EnsembleStats), "In() and Out() tell the element by its size");
   ResetCounters();
   bool arrived = true, back = true, absent_null = true, absent_no_room = true;
   int n_in = 0, n_out = 0;
@@ -153,30 +182,43 @@ static void RoundTrip(const char* name, const Parts<K>& p, unsigned ins, unsigne
   {
     DevBlock<double> block;
     Must(block.alloc(p.total()));
-    std::vector<std::vector<double>> host(K), got(K);
-    const double* dev_in[K] = {};
-    double* dev_out[K] = {};
+    unsigned char* const dev = reinterpret_cast<unsigned char*>(block.get());
+    Elem el[K];
+    unsigned char *host[K] = {}, *host2[K] = {};  // (host2: the upper half of a shared part, an array of its own)
+    const void* dev_in[K] = {};
+    void* dev_out[K] = {};
     Staged<K> sg(false, block.get(), p, nullptr);
     for (int i = 0; i < K; ++i) {
+      el[i] = elems && elems[i].size ? elems[i] : Elem{sizeof(double), p.cnt[i]};
       const bool here = (present >> i) & 1u;
+      const size_t bytes = el[i].size * el[i].count;
       if (!here) absent_no_room = absent_no_room && p.cnt[i] == 0;
       if ((ins >> i) & 1u) {
-        host[i].resize(p.cnt[i]);
-        for (size_t j = 0; j < p.cnt[i]; ++j) host[i][j] = 1000.0 * (i + 1) + (double)j;
         if ((halves >> i) & 1u) {
-          const size_t h = p.cnt[i] / 2;
-          dev_in[i] = sg.in(i, here ? host[i].data() : nullptr, 0, h);
-          const double* hi = sg.in(i, here ? host[i].data() + h : nullptr, h, h);
-          if (here) arrived = arrived && hi == dev_in[i] + h, n_in += 2;
+          const size_t h = el[i].count / 2, hb = h * el[i].size;
+          if (here) {
+            host[i] = (unsigned char*)std::malloc(hb), host2[i] = (unsigned char*)std::malloc(hb);
+            for (size_t j = 0; j < hb; ++j) host[i][j] = Pattern(i, j, 1), host2[i][j] = Pattern(i, hb + j, 1);
+          }
+          dev_in[i] = In(sg, i, host[i], el[i], h, 0, false);
+          const void* hi = In(sg, i, host2[i], el[i], h, h, false);
+          if (here) arrived = arrived && hi == (const unsigned char*)dev_in[i] + hb, n_in += 2;
         } else {
-          dev_in[i] = sg.in(i, here ? host[i].data() : nullptr);
+          if (here) {
+            host[i] = (unsigned char*)std::malloc(bytes);
+            for (size_t j = 0; j < bytes; ++j) host[i][j] = Pattern(i, j, 1);
+          }
+          dev_in[i] = In(sg, i, host[i], el[i], el[i].count, 0, true);
           n_in += here;
         }
         if (!here) absent_null = absent_null && dev_in[i] == nullptr;
         if (here) arrived = arrived && dev_in[i] == block.get() + p.off[i];
       } else if ((outs >> i) & 1u) {
-        got[i].assign(p.cnt[i], -1.0);
-        dev_out[i] = sg.out(i, here ? got[i].data() : nullptr);
+        if (here) {
+          host[i] = (unsigned char*)std::malloc(bytes);
+          std::memset(host[i], 0xee, bytes);
+        }
+        dev_out[i] = Out(sg, i, host[i], el[i]);
         n_out += here;
         if (!here) absent_null = absent_null && dev_out[i] == nullptr;
         if (here) back = back && dev_out[i] == block.get() + p.off[i];
@@ -184,22 +226,47 @@ static void RoundTrip(const char* name, const Parts<K>& p, unsigned ins, unsigne
         absent_null = absent_null && sg.part(i) == nullptr;
       }
     }
-    // the "launch": every present input is where its part starts; every present output part is written whole
+    // the "launch": every present input is where its part starts, to the byte; every present output part is written whole
+    // (its rounding at the end too: that must not reach the caller)
     for (int i = 0; i < K; ++i) {
-      if (dev_in[i])
-        for (size_t j = 0; j < p.cnt[i]; ++j) arrived = arrived && block.get()[p.off[i] + j] == host[i][j];
+      const size_t bytes = el[i].size * el[i].count, at = p.off[i] * sizeof(double), half = bytes / 2;
+      if (dev_in[i] && host2[i]) arrived = arrived && !std::memcmp(dev + at, host[i], half) && !std::memcmp(dev + at + half, host2[i], half);
+      if (dev_in[i] && !host2[i]) arrived = arrived && !std::memcmp(dev + at, host[i], bytes);
       if (dev_out[i])
-        for (size_t j = 0; j < p.cnt[i]; ++j) dev_out[i][j] = 2000.0 * (i + 1) + (double)j;
+        for (size_t j = 0; j < p.cnt[i] * sizeof(double); ++j) dev[at + j] = Pattern(i, j, 2);
     }
     e = sg.finish();
-    for (int i = 0; i < K; ++i)
+    for (int i = 0; i < K; ++i) {
       if (dev_out[i])
-        for (size_t j = 0; j < p.cnt[i]; ++j) back = back && got[i][j] == 2000.0 * (i + 1) + (double)j;
+        for (size_t j = 0; j < el[i].size * el[i].count; ++j) back = back && host[i][j] == Pattern(i, j, 2);
+      std::free(host[i]);
+      std::free(host2[i]);
+    }
   }
   std::printf("\"%s\": {\"total\": %zu, \"arrived\": %s, \"back\": %s, \"absent_null\": %s, \"absent_no_room\": %s, \"h2d\": %d, \"want_h2d\": %d, "
               "\"d2h\": %d, \"want_d2h\": %d, \"syncs\": %d, \"error\": %d, \"live\": %zu}%s\n",
               name, p.total(), arrived ? "true" : "false", back ? "true" : "false", absent_null ? "true" : "false",
               absent_no_room ? "true" : "false", g_h2d, n_in, g_d2h, n_out, g_syncs, (int)e, g_live.size(), tail);
+}
+
+// a part that cannot hold what a call brings is a programming error; it is treated as a part without room: a null pointer,
+// no copy in either direction, no error.  A count that fills the part to the byte goes through.
+static void ShortPart() {
+  ResetCounters();
+  const Parts<2> p{1, 1};  // one double each: room for two ints
+  int up[3] = {1, 2, 3}, down[3] = {-1, -1, -1};
+  bool nulls, fits;
+  hipError_t e;
+  {
+    DevBlock<double> block;
+    Must(block.alloc(p.total()));
+    Staged<2> sg(false, block.get(), p, nullptr);
+    nulls = sg.in(0, up, 0, 3) == nullptr && sg.in(0, up, 2, 1) == nullptr && sg.out(1, down, 3) == nullptr;
+    fits = sg.in(0, up, 0, 2) == reinterpret_cast<int*>(block.get()) && sg.in(0, up + 2, 1, 1) == reinterpret_cast<int*>(block.get()) + 1;
+    e = sg.finish();
+  }
+  std::printf("\"short_part\": {\"nulls\": %s, \"fits\": %s, \"h2d\": %d, \"d2h\": %d, \"untouched\": %s, \"error\": %d},\n", nulls ? "true" : "false",
+              fits ? "true" : "false", g_h2d, g_d2h, down[0] == -1 && down[1] == -1 && down[2] == -1 ? "true" : "false", (int)e);
 }
 
 // a failed upload copy: the launch is skipped by the caller, nothing comes down, the stream is still waited for, and the
@@ -292,6 +359,33 @@ int main(int argc, char** argv) {
   // Xref | Uref
   RoundTrip("reference_stage", ReferenceStageParts(n, m, B * (steps + 1), true), 0x03, 0, 0, 0x03, ",");
   RoundTrip("reference_stage_sparse", ReferenceStageParts(n, m, B * (steps + 1), false), 0x03, 0, 0, 0x01, ",");
+  // the layouts that hold ints, bytes and statistics structs: every host array exactly as long as its elements
+  const Elem stats{sizeof(TrackStats), B}, summ{sizeof(EnsembleStats), B}, intsB{sizeof(int), B}, bytesB{sizeof(unsigned char), B};
+  // tracked | age | u_lo, u_hi | mask | reason | the lookahead's statistics (scratch: nobody's array)
+  const Elem trig[6] = {stats, intsB, {}, bytesB, intsB, {}};
+  RoundTrip("trigger_stage", TriggerStageParts(m, B, true, true, true, true, true, true), 0x07, 0x18, 0x04, 0x3f, ",", trig);
+  RoundTrip("trigger_stage_sparse", TriggerStageParts(m, B, false, false, false, false, false, true), 0x07, 0x18, 0x04, 0x20, ",", trig);
+  // Sigma0 | W | u_lo, u_hi | dev_mean | dev_mom2 | alive | viol_count | summary | stats, two samples
+  EnsembleArgs en{};
+  en.steps = (int)steps, en.S = 2, en.sigma0_per_instance = 1, en.w_mode = 3;
+  en.Sigma0 = en.W = en.u_lo = en.u_hi = &x;
+  en.dev_mean = en.dev_mom2 = en.dx0 = en.w = &x;
+  int ix = 0;
+  EnsembleStats ex{};
+  TrackStats tx{};
+  en.alive = en.viol_count = &ix, en.summary = &ex, en.stats = &tx;
+  const Elem intsK{sizeof(int), B * (steps + 1)}, lanes{sizeof(TrackStats), B * 2};
+  const Elem ens[9] = {{}, {}, {}, {}, {}, intsK, intsK, summ, lanes};
+  RoundTrip("ensemble_stage", EnsembleStageParts(n, m, B, en), 0x007, 0x1f8, 0x004, 0x1ff, ",", ens);
+  // Sigma0 | W | dx0 | w
+  RoundTrip("noise_stage", NoiseStageParts(n, B, en), 0x3, 0xc, 0, 0xf, ",");
+  RoundTrip("gauss_stage", GaussStageParts(m), 0x1, 0, 0, 0x1, ",");
+  // K | P | fail, a horizon of `steps` knots
+  const Elem lqr[3] = {{}, {}, intsB};
+  RoundTrip("lqr_stage", LqrStageParts(n, m, B, steps, true, true, true), 0, 0x7, 0, 0x7, ",", lqr);
+  RoundTrip("lqr_stage_sparse", LqrStageParts(n, m, B, steps, true, false, true), 0, 0x7, 0, 0x5, ",", lqr);
+  RoundTrip("mask_stage", MaskStageParts(B), 0x1, 0, 0, 0x1, ",", &bytesB);
+  ShortPart();
   FailedCopy();
   return 0;
 }

@@ -54,6 +54,17 @@ int main(int argc, char** argv) {
   Print("advance_stage", AdvanceStageParts(n, B, true, true), ",");
   Print("advance_stage_sparse", AdvanceStageParts(n, B, false, true), ",");
   Print("reference_stage", ReferenceStageParts(n, m, B * (shift + 1), true), ",");
-  Print("reference_stage_sparse", ReferenceStageParts(n, m, B * (shift + 1), false), "}");
+  Print("reference_stage_sparse", ReferenceStageParts(n, m, B * (shift + 1), false), ",");
+  // the int block of a run, in ints, for the four kinds: plain / tracked, multi-start with 5 starts, team (as plain), triggered
+  Print("run_ints", RunIntParts(B, cycles, 0, false), ",");
+  Print("run_ints_multistart", RunIntParts(B, cycles, B / 5, false), ",");
+  Print("run_ints_team", RunIntParts(B, cycles, 0, false), ",");
+  Print("run_ints_triggered", RunIntParts(B, cycles, 0, true), ",");
+  // a host caller's trigger evaluation with a lookahead, and a device caller's (only the lookahead's statistics)
+  Print("trigger_stage", TriggerStageParts(m, B, true, true, true, true, true, true), ",");
+  Print("trigger_stage_sparse", TriggerStageParts(m, B, false, false, false, false, false, true), ",");
+  Print("lqr_stage", LqrStageParts(n, m, B, shift, true, true, true), ",");  // a horizon of `shift` knots
+  Print("lqr_stage_sparse", LqrStageParts(n, m, B, shift, true, false, true), ",");
+  Print("mask_stage", MaskStageParts(B), "}");
   return 0;
 }

@@ -4,7 +4,8 @@ tests/cpp/devmem_driver.cpp includes the header and defines the HIP entry points
 a book of live blocks, memcpy, an allocation and a copy that can be told to fail at their k-th call -- so no GPU and no HIP
 runtime is involved.  It is built twice with plain g++ against the HIP API header, once with -Wall -Werror and once more with
 -fsanitize=address,undefined, and run directly both times; every expectation holds for both programs, and the sanitizer build
-must have nothing to report.  A staged block is exactly total() doubles, so a wrong offset is an out-of-bounds access there.
+must have nothing to report.  A staged block is exactly total() doubles, so a wrong offset is an out-of-bounds access there; a
+host array is exactly its elements (ints, bytes and statistics structs included), so a copy that is a byte too long is one too.
 Shapes: n = 3, m = 2, B = 5, steps = 2, cycles = 3, shift = 2 (tests/test_part_offsets.py has the offsets written out).
 """
 import json
@@ -21,7 +22,19 @@ ARGS = [str(v) for v in (3, 2, 5, 2, 3, 2)]  # n m B steps cycles shift
 LAYOUTS = dict(track_stage=139, track_stage_sparse=55, tracked_run=354, tracked_run_sparse=354, plain_run=233, plain_run_sparse=165,
                cov_stage=350, cov_stage_sparse=69, inflate_stage=45, inflate_stage_shared=21, ms_best_stage=100, ms_best_stage_sparse=20,
                perturb_stage=20, advance_stage=30, advance_stage_sparse=15, advance_stage_empty=0, reference_stage=75,
-               reference_stage_sparse=45)
+               reference_stage_sparse=45,
+               # the layouts with ints, bytes and statistics structs in them (DoublesFor: int[5] takes 3 doubles, unsigned char[5]
+               # takes 1, int[15] takes 8; TrackStats is 5 doubles, EnsembleStats 7); every host array exactly as long as its elements
+               # tracked: 5 5 | age: 3 | bounds: 2 2 | mask: 1 | reason: 3 | lookahead statistics: 5 5
+               trigger_stage=61,
+               trigger_stage_sparse=25,  # a device caller's: only the lookahead's statistics
+               # Sigma0: 5 9 | W: 5 2 9 | bounds: 4 | mean: 5 3 3 | mom2: 5 3 9 | alive: 8 | viol_count: 8 | summary: 5 7 | stats: 5 2 5
+               ensemble_stage=420,
+               noise_stage=225,          # Sigma0: 45 | W: 90 | dx0: 5 2 3 | w: 5 2 2 3
+               gauss_stage=2,            # sigma: m
+               lqr_stage=198,            # K: 5 2 2 3 | P: 5 3 9 | fail: 3
+               lqr_stage_sparse=63,      # K | no P | fail
+               mask_stage=1)             # 5 bytes
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
@@ -66,6 +79,13 @@ def test_staging_round_trip(report, name):
     assert r["absent_no_room"] or name == "tracked_run_sparse"
     assert r["h2d"] == r["want_h2d"] and r["d2h"] == r["want_d2h"]
     assert r["syncs"] == 1 and r["error"] == 0 and r["live"] == 0
+
+
+def test_a_part_too_small_for_the_count_is_treated_as_absent(report):
+    """A programming error, handled like a part without room: null pointers, nothing copied, no error; an exact fit goes through."""
+    s = report["short_part"]
+    assert s["nulls"] and s["fits"] and s["untouched"]
+    assert s["h2d"] == 2 and s["d2h"] == 0 and s["error"] == 0  # (the two copies are the ones that fit)
 
 
 def test_a_failed_upload_copy_still_synchronises(report):

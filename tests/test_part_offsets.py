@@ -100,3 +100,24 @@ def test_get_best_stage_block(parts):
     _is(parts["ms_best_stage"], [45, 20, 35])      # 5 3 3 | 5 2 2 | 5 7
     assert parts["ms_best_stage"]["off"] == [0, 45, 65, 100]
     _is(parts["ms_best_stage_sparse"], [0, 20, 0])
+
+
+def test_run_int_block(parts):
+    """iterations | statuses | winners | reason log | ages | reasons | next mask, in ints (B = 5, 3 cycles)"""
+    _is(parts["run_ints"], [15, 15, 0, 0, 0, 0, 0])                 # plain and tracked runs: two logs of 5 3
+    _is(parts["run_ints_team"], [15, 15, 0, 0, 0, 0, 0])
+    _is(parts["run_ints_multistart"], [15, 15, 3, 0, 0, 0, 0])      # winners: 1 problem (5 starts) x 3 cycles
+    #                                   reason log: 3 5 | ages: 5 | reasons: 5 | mask: 5 bytes in 2 ints
+    _is(parts["run_ints_triggered"], [15, 15, 0, 15, 5, 5, 2])
+    assert parts["run_ints_triggered"]["off"] == [0, 15, 30, 30, 45, 50, 55, 57]
+
+
+def test_int_and_byte_parts_are_rounded_up_to_doubles(parts):
+    """tracked | age | u_lo, u_hi | mask | reason | lookahead statistics;  K | P | fail;  the solve mask"""
+    #                             5 5 | ceil(5 / 2) | 2 2 | ceil(5 / 8) | ceil(5 / 2) | 5 5
+    _is(parts["trigger_stage"], [25, 3, 4, 1, 3, 25])
+    assert parts["trigger_stage"]["off"] == [0, 25, 28, 32, 33, 36, 61]
+    _is(parts["trigger_stage_sparse"], [0, 0, 0, 0, 0, 25])
+    _is(parts["lqr_stage"], [60, 135, 3])                            # K: 5 2 2 3 | P: 5 (2 + 1) 9 | fail: ceil(5 / 2)
+    _is(parts["lqr_stage_sparse"], [60, 0, 3])
+    _is(parts["mask_stage"], [1])                                    # ceil(5 / 8)
