@@ -6058,11 +6058,13 @@ ALTRO_DEV void mpc_track_kernel(const DevArrays<T>& A, const ProblemDesc* __rest
 //                  NEXT knot is requested from memory at the top of the step (n * n / G elements per lane) and moved to the
 //                  other half of a double LDS buffer at its end, as k_mpc_track does with its records.  Only the lower
 //                  triangles of Sigma0 and W are read.  Every register array is indexed by unrolled constants only (a
-//                  lane's own index selects through compares or through an LDS / memory address): no scratch.
+//                  lane's own index selects through compares or through an LDS / memory address): no scratch at any
+//                  measured shape, n = 32 included (profiles/recur_shapes_resources.txt).
 //                  Lanes of a group beyond n and groups beyond B run along with clamped indices and store nothing.
+//                  LDS: 2 * (64 / G) * n n + 64 * (n | 1) doubles, 49664 bytes at n = 32.
 // k_cov_inflate    one lane per (instance, row, circle) of the track, in the order of `out`.
 // -------------------------------------------------------------------------------------------------
-constexpr int kCovMaxN = 32;  // a group is at most half a wave, and the double F buffer stays within 32 KiB of LDS
+constexpr int kCovMaxN = 32;  // a group is at most half a wave; the double F buffer is 32 KiB of LDS there, 49664 bytes with the exchange rows
 constexpr int cov_group(int n) {
   int G = 1;
   while (G < n) G *= 2;
@@ -6265,8 +6267,10 @@ __global__ __launch_bounds__(kTeamThreads) void k_cov_inflate(double* __restrict
 //                  double LDS buffer at its end.  K_k and P_k are stored off the chain.  An instance FAILS at the largest k at
 //                  which a pivot is not positive or a value of K_k or P_k is not finite (the lanes of a group agree through a
 //                  ballot): K and P from that knot down are quiet NaN, fail[b] = k, otherwise -1.  Every register array is
-//                  indexed by unrolled constants only: no scratch.  The order of every sum is a function of (n, m) alone.
-//                  LDS: 2 * (64 / G) * (n (n + m) | 1) + 64 * ((n + m) | 1) doubles, at most 61952 bytes (n = 32, m = 8): every
+//                  indexed by unrolled constants only, so nothing goes to scratch while the arrays fit the register file: no
+//                  scratch up to (24, 3) and (16, 4) at 256 VGPRs; at (32, 8) the kernel spills 254 VGPRs, 1020 bytes of
+//                  scratch per lane (profiles/recur_shapes_resources.txt).  The order of every sum is a function of (n, m) alone.
+//                  LDS: 2 * (64 / G) * (n (n + m) | 1) + 64 * ((n + m) | 1) doubles, at most 61984 bytes (n = 32, m = 8): every
 //                  (n, m) with n <= kLqrMaxN, 1 <= m <= kLqrMaxM fits 64 KiB (lqr_lds_bytes).
 // k_lqr_install    one lane per (instance, knot <= N): where fail[b] < 0 and the mask (if any) is set it writes K_k | d = 0 into
 //                  the gain record in its storage type; it transposes K, P and fail into the caller's instance-major arrays.

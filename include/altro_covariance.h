@@ -15,7 +15,10 @@
  * in fp64 throughout.  Only the LOWER triangle (i >= j) of Sigma0 and of W is read, so an unsymmetric input cannot matter,
  * and every Sigma_k that comes out is symmetric bit for bit.  The plan, the gains and the Jacobians never leave the device.
  * Every model kind is accepted (per-knot steps, times and models, time-varying and discrete user models) up to 32 states
- * (more: ALTRO_UNSUPPORTED); nothing moves along the horizon.
+ * (more: ALTRO_UNSUPPORTED); nothing moves along the horizon.  What stands behind the limit: the whole call is tested
+ * against its numpy statement on models of n <= 13 states (groups of 1 .. 16 lanes); beyond that only the recursion kernel
+ * is, driven on its own (tests/cpp/recur_driver.hip: n = 16, 17, 24 and 32).  The linearisation of a model of more than 13
+ * states has never run, and a user-model plug-in of more than about 13 states takes minutes to compile.
  *
  * The second call turns the covariance into tightened constraints for the next solve: the track of a knot circle constraint
  * (include/altro_knot_params.h) becomes base radius + kappa * position spread at that knot.  A position is (x[0], x[1]), the

@@ -18,6 +18,11 @@
  * of every sum depends on (n, m) alone -- not on the batch, the launch or an instance's neighbours.  Every model kind is
  * accepted (per-knot steps, times and models, time-varying and discrete user models) with 1 <= m <= 8 controls and
  * n <= 32 states; every (n, m) in that range fits the 64 KiB of LDS the recursion may use, so none of them is refused.
+ * What stands behind these limits: the whole call is tested against its numpy statement on models of n <= 13 states and
+ * m <= 5 controls (groups of 1 .. 16 lanes); beyond that only the recursion kernel is, driven on its own
+ * (tests/cpp/recur_driver.hip: n = 16, 17, 24, 32 and m = 6, 8, up to (n, m) = (32, 8), where it spills registers to scratch:
+ * profiles/recur_shapes_resources.txt).  The linearisation of a model of more than 13 states has never run, and a user-model
+ * plug-in of more than about 13 states takes minutes to compile (13 states: about five).
  *
  * Outputs (each may be NULL):
  *     K     [B][N][m * n]     column-major m x n per knot, as altro_get_gains returns it

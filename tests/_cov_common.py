@@ -46,13 +46,15 @@ def propagate(A, Bm, K, steps, Sigma0=None, W=None, w_mode=0, dtype=np.float64):
 
 def spreads(Sigma, K, dtype=np.float64):
     """Sigma [B][steps + 1][n][n], K [B][N][m][n] -> sx [B][steps + 1][n], su [B][steps][m], rpos [B][steps + 1]; a negative
-    argument of a square root is clamped to zero."""
+    argument of a square root is clamped to zero.  rpos is None for n = 1 (a position is two states)."""
     Sigma, K = np.asarray(Sigma).astype(dtype), np.asarray(K).astype(dtype)
     steps = Sigma.shape[1] - 1
     root = lambda v: np.sqrt(np.maximum(v, dtype(0)))  # noqa: E731
     sx = root(np.diagonal(Sigma, axis1=2, axis2=3))
     Kk = K[:, :steps]
     su = root(np.einsum("bkia,bkac,bkic->bki", Kk, Sigma[:, :steps], Kk))
+    if Sigma.shape[2] < 2:
+        return sx, su, None
     a, b, c = Sigma[:, :, 0, 0], Sigma[:, :, 1, 0], Sigma[:, :, 1, 1]
     rpos = root((a + c) / 2 + np.sqrt(((a - c) / 2) ** 2 + b ** 2))
     return sx, su, rpos

@@ -1,9 +1,13 @@
 """Shared by tests/test_lqr_abi.py, tests/test_lqr_gpu.py and tests/test_lqr_facade_gpu.py: include/altro_lqr.h stated in numpy.
 Every function takes ``dtype`` so that the same code runs in float64 and in np.longdouble (the reference's own rounding
 sensitivity is the difference of the two)."""
+import json
+
 import numpy as np
 
-from _cov_common import lower_sym
+from _cov_common import lower_sym, matrix_rel
+
+EPS = 2.0 ** -52
 
 
 def ldl(S, dtype=np.float64):
@@ -73,6 +77,69 @@ def gains(A, Bm, Q, R, Qf=None, dtype=np.float64):
             if (~dead).any():
                 kappa = max(kappa, float(np.linalg.cond(lower_sym(S[~dead]).astype(np.float64)).max()))
     return K, P, fail, kappa
+
+
+def reference(A, Bm, Q, R, Qf):
+    """the statement in float64 and in longdouble on the same Jacobians; neither may fail"""
+    K, Pm, fail, kappa = gains(A, Bm, Q, R, Qf)
+    KL, PL, failL, _ = gains(A, Bm, Q, R, Qf, dtype=np.longdouble)
+    assert (fail == -1).all() and (failL == -1).all()
+    return dict(K=K, P=Pm, KL=KL, PL=PL, kappa=kappa)
+
+
+def parity(name, ref, got, N, n, m, fractions, out=None):
+    """K and P of one call (``got``: K [B][N][m][n], P [B][N + 1][n][n], fail [B]) against ``ref`` (reference()).  The error of
+    a matrix is max |gpu - numpy| / max |numpy| per (instance, knot); its bar is the larger of 8 x the same quantity between
+    the float64 and the longdouble run of the statement and 4 N (n + m) 2^-52 max(1, kappa_S).  The largest error as a
+    fraction of its bar goes to fractions[name] and, where ``out`` names a file, the whole of ``fractions`` goes there."""
+    print(f"{name}: kappa_S {ref['kappa']:.3g}")
+    assert ref["kappa"] < 1e3, ref["kappa"]  # (the weights of the parity tests keep the one solve per knot well conditioned)
+    floor = 4 * N * (n + m) * EPS * max(1.0, ref["kappa"])
+    missed, worst = [], {}
+    for key in ("K", "P"):
+        r, rl = ref[key], ref[key + "L"]
+        assert got[key].shape == r.shape, (key, got[key].shape, r.shape)
+        own = (np.abs(r.astype(np.longdouble) - rl).max(axis=(-1, -2))
+               / np.maximum(np.abs(rl).max(axis=(-1, -2)), np.longdouble(1e-300))).astype(np.float64)
+        bar = np.maximum(8.0 * own, floor)
+        err = matrix_rel(got[key], r)
+        worst[key] = (float(err.max()), float((err / bar).max()))
+        for idx in np.argwhere(~(err <= bar)):
+            missed.append((key, tuple(idx), float(err[tuple(idx)]), float(bar[tuple(idx)])))
+    print(f"{name}: " + ", ".join(f"{k} err {v[0]:.2e} ({v[1]:.3f} of its bar)" for k, v in worst.items()))
+    fractions[name] = {k: v[1] for k, v in worst.items()}
+    if out:
+        with open(out, "w") as f:
+            json.dump(fractions, f, indent=1, sort_keys=True)
+    assert not missed, (name, missed[:6])
+    assert (got["fail"] == -1).all()
+
+
+def mixed_failure_qf(A, Bm, Q, R, qf_of):
+    """Qf = qf_of(v), indefinite through its one entry -v, with v found by the statement: a coarse sweep brackets the weights
+    between "nobody fails" and "everybody fails", a fine one inside the bracket takes the first v at which a quarter to three
+    quarters of the instances fail and for which v (1 -+ 1e-6) give the very same fail vector -- no pivot sits within rounding
+    of the edge.  -> (Qf, v)"""
+    fails_at = lambda v: gains(A, Bm, Q, R, qf_of(v))[2]  # noqa: E731
+    coarse = np.geomspace(1.0, 1e4, 41)
+    count = [int((fails_at(v) >= 0).sum()) for v in coarse]
+    B = A.shape[0]
+    lo = max(i for i, v in enumerate(count) if v == 0)
+    hi = min(i for i, v in enumerate(count) if v == B)
+    assert lo < hi, count
+    fine = np.linspace(coarse[lo], coarse[hi], 41)
+    for _ in range(4):
+        fails = [fails_at(v) for v in fine]
+        for v, f in zip(fine, fails):
+            if 0.25 * B <= (f >= 0).sum() <= 0.75 * B and (fails_at(v * (1 - 1e-6)) == f).all() and (fails_at(v * (1 + 1e-6)) == f).all():
+                return qf_of(v), float(v)
+        # a small batch whose instances give way within one fine step of each other (5 instances: from none to 4 of 5 in one
+        # step): the same 41 points again between the last v with too few failures and the first with too many
+        count = [int((f >= 0).sum()) for f in fails]
+        over = min(i for i, v in enumerate(count) if v > 0.75 * B)
+        under = max(i for i, v in enumerate(count[:over]) if v < 0.25 * B)
+        fine = np.linspace(fine[under], fine[over], 41)
+    raise AssertionError(count)
 
 
 def gains_loops(A, Bm, Q, R, Qf=None):

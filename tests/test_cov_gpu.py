@@ -109,6 +109,7 @@ def _check(tag, got, c, steps, Sigma0, W, w_mode, N, n):
                 missed.append((name, idx, float(err[idx]), float(bar[idx])))
     print(f"{tag}: " + ", ".join(f"{k} err {v[0]:.2e} ({v[1]:.2f} of its bar)" for k, v in worst.items()))
     assert not missed, (tag, missed[:6])
+    return {k: v[1] for k, v in worst.items()}  # (the largest error of each array as a fraction of its bar)
 
 
 def _parity(A, P, hip_make, oracle_make, name, seed):

@@ -8,7 +8,6 @@ the larger of
   * 8 x the same quantity between the float64 and the np.longdouble run of the statement on the same inputs, and
   * 4 N (n + m) 2^-52 max(1, kappa_S): the length of the accumulation times the conditioning of the one solve per knot.
 Every parity handle and every reference is built once and shared; a test that installs gains builds its own handle."""
-import json
 import os
 
 import numpy as np
@@ -25,7 +24,7 @@ from test_user_model_gpu import CARTPOLE, cartpole_oracle  # noqa: F401  (the fi
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -52
+EPS = LC.EPS
 N = 24
 
 
@@ -79,37 +78,15 @@ _REFS, _FRACTIONS = {}, {}
 def _reference(name, c, Q, R, Qf):
     """the statement in float64 and longdouble on the case's Jacobians, once"""
     if name not in _REFS:
-        K, Pm, fail, kappa = LC.gains(c["A"], c["B"], Q, R, Qf)
-        KL, PL, failL, _ = LC.gains(c["A"], c["B"], Q, R, Qf, dtype=np.longdouble)
-        assert (fail == -1).all() and (failL == -1).all()
-        _REFS[name] = dict(K=K, P=Pm, KL=KL, PL=PL, kappa=kappa)
+        _REFS[name] = LC.reference(c["A"], c["B"], Q, R, Qf)
     return _REFS[name]
 
 
 def _parity(name, c, got, Q, R, Qf):
+    """the bar of tests/_lqr_common.py: parity, which tests/test_recur_shapes_gpu.py and tests/test_recur_kernels_gpu.py share"""
     g = c["g"]
-    ref = _reference(name, c, Q, R, Qf)
-    print(f"{name}: kappa_S {ref['kappa']:.3g}")
-    assert ref["kappa"] < 1e3, ref["kappa"]  # (the weights of the parity tests keep the one solve per knot well conditioned)
-    floor = 4 * g.N * (g.n + g.m) * EPS * max(1.0, ref["kappa"])
-    missed, worst = [], {}
-    for key in ("K", "P"):
-        r, rl = ref[key], ref[key + "L"]
-        assert got[key].shape == r.shape, (key, got[key].shape, r.shape)
-        own = (np.abs(r.astype(np.longdouble) - rl).max(axis=(-1, -2))
-               / np.maximum(np.abs(rl).max(axis=(-1, -2)), np.longdouble(1e-300))).astype(np.float64)
-        bar = np.maximum(8.0 * own, floor)
-        err = CC.matrix_rel(got[key], r)
-        worst[key] = (float(err.max()), float((err / bar).max()))
-        for idx in np.argwhere(~(err <= bar)):
-            missed.append((key, tuple(idx), float(err[tuple(idx)]), float(bar[tuple(idx)])))
-    print(f"{name}: " + ", ".join(f"{k} err {v[0]:.2e} ({v[1]:.3f} of its bar)" for k, v in worst.items()))
-    _FRACTIONS[name] = {k: v[1] for k, v in worst.items()}
-    if os.environ.get("ALTRO_LQR_PARITY_OUT"):  # (how profiles/lqr_gains_parity.json is made)
-        with open(os.environ["ALTRO_LQR_PARITY_OUT"], "w") as f:
-            json.dump(_FRACTIONS, f, indent=1, sort_keys=True)
-    assert not missed, (name, missed[:6])
-    assert (got["fail"] == -1).all()
+    LC.parity(name, _reference(name, c, Q, R, Qf), got, g.N, g.n, g.m, _FRACTIONS,
+              os.environ.get("ALTRO_LQR_PARITY_OUT"))  # (how profiles/lqr_gains_parity.json is made)
 
 
 # ---- 1. parity with the numpy statement ------------------------------------------------------------------------------------------
@@ -256,22 +233,8 @@ def test_no_step_is_refused(A, P, hip_make):
 
 # ---- 4. the failure path ---------------------------------------------------------------------------------------------------------------
 def _mixed_failure_qf(c, Q, R):
-    """Qf = diag(-v, 50, 1) with v found by the statement: a coarse sweep brackets the weights between "nobody fails" and
-    "everybody fails", a fine one inside the bracket takes the first v at which a quarter to three quarters of the instances
-    fail and for which v (1 -+ 1e-6) give the very same fail vector -- no pivot sits within rounding of the edge."""
-    fails_at = lambda v: LC.gains(c["A"], c["B"], Q, R, np.diag([-v, 50.0, 1.0]))[2]  # noqa: E731
-    coarse = np.geomspace(1.0, 1e4, 41)
-    count = [int((fails_at(v) >= 0).sum()) for v in coarse]
-    B = c["A"].shape[0]
-    lo = max(i for i, v in enumerate(count) if v == 0)
-    hi = min(i for i, v in enumerate(count) if v == B)
-    assert lo < hi, count
-    fine = np.linspace(coarse[lo], coarse[hi], 41)
-    fails = [fails_at(v) for v in fine]
-    for v, f in zip(fine, fails):
-        if 0.25 * B <= (f >= 0).sum() <= 0.75 * B and (fails_at(v * (1 - 1e-6)) == f).all() and (fails_at(v * (1 + 1e-6)) == f).all():
-            return np.diag([-v, 50.0, 1.0])
-    raise AssertionError([int((f >= 0).sum()) for f in fails])
+    """Qf = diag(-v, 50, 1) with v found by the statement (tests/_lqr_common.py: mixed_failure_qf)"""
+    return LC.mixed_failure_qf(c["A"], c["B"], Q, R, lambda v: np.diag([-v, 50.0, 1.0]))[0]
 
 
 def test_failure_path(A, P, hip_make, oracle_make):
